@@ -11,8 +11,13 @@ for `--batch` polynomial pairs per GPU ([batch][L][N] 32-byte containers, 30-bit
 Prints ONE JSON line on rank 0.  `value` = polynomial products per second over all GPUs (weak
 scaling: every rank multiplies its own `--batch` pairs; the path has no exchange step, so RCCL is used
 only for the barriers and the max-over-ranks of the timings).  `roofline` is measured live with HIP
-events on the engine's stream; `cpu_baseline` times the CPU oracle (a port, not the product) on a
-bounded sample.
+events on the engine's stream.
+
+A plain run only sets up, warms up, times the `--steps` steps and prints the line.  `--full` adds everything
+else: the per-rank checksum and CPU-oracle spot check of the results, the forward+inverse pair leg, the other
+modulus widths, the other BASELINE workloads and the batch-1 latencies (child runs), and `cpu_baseline`, which
+times the CPU oracle (a port, not the product) on a bounded sample.  `--dump-outputs DIR` writes what the timed
+path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import importlib
@@ -113,7 +118,13 @@ def parse():
                          "modulo q_l, l = r (mod G), of every polynomial (ops multiply / fwdinv / ct only; no collective either way)")
     ap.add_argument("--timeout", type=float, default=float(os.environ.get("FHE_BENCH_TIMEOUT", "1500")),
                     help="self-launched ranks (--gpus N without a launcher): kill every rank and exit non-zero after this many seconds")
-    ap.add_argument("--no-verify", action="store_true", help="skip the per-rank result checksum / oracle spot check (outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: result checksums + oracle spot check, the extra legs, the other workloads and latencies, "
+                         "the CPU baseline (the --no-* options below turn single parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, a fixed "
+                         "seeded sample of the batch, at most 32 MiB in all)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the per-rank result checksum / oracle spot check (outside the timed region)")
     ap.add_argument("--no-extra-workloads", action="store_true",
                     help="skip the child runs of the other BASELINE configurations (profiling scripts pass it: children would add their own counter files)")
     ap.add_argument("--no-extras", action="store_true",
@@ -212,6 +223,33 @@ def download_poly(pkg, buf, b, S):
     return out.reshape(-1, 4)
 
 
+DUMP_BUDGET = 32 << 20                               # bytes of all --dump-outputs arrays together
+
+
+def dump_outputs(pkg, dirname, results, moduli, n, B):
+    """--dump-outputs: the polynomials the timed path left in its result buffers after its last step, as dirname/<name>.npy, float64.
+    The same fixed, seeded sample of batch indices (sorted) for every output and every run with the same arguments, as many as fit
+    in DUMP_BUDGET.  Moduli < 2^53: [sample][L][n] residues (exact in float64; -1 where a 32-byte container holds a value >= 2^53);
+    wider moduli: [sample][L][n][8], the eight 32-bit words of every container, least significant first."""
+    import numpy as np
+    L = len(moduli); S = 32 * n * L
+    words = 1 if max(moduli) < (1 << 53) else 8
+    per_poly = L * n * words * 8
+    k = min(B, DUMP_BUDGET // (per_poly * len(results)))
+    if k < 1:
+        raise SystemExit(f"bench.py: --dump-outputs: one polynomial of each of the {len(results)} outputs exceeds {DUMP_BUDGET >> 20} MiB")
+    idx = np.sort(np.random.default_rng(20240607).choice(B, size=k, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, buf in results:
+        c = np.stack([download_poly(pkg, buf, int(b), S) for b in idx]).reshape(k, L, n, 4)
+        if words == 1:
+            fits = (c[..., 1:] == 0).all(axis=-1) & (c[..., 0] < np.uint64(1 << 53))
+            arr = np.where(fits, c[..., 0].astype(np.float64), -1.0)
+        else:
+            arr = np.ascontiguousarray(c).view(np.uint32).reshape(k, L, n, 8).astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def verify_shard(pkg, op, moduli, n, B, ins, outs, in_seeds, relin=None):
     """Outside the timed region: SHA-256 over a sample of THIS rank's result polynomials (first, middle, last of the shard)
     and, for the ops the CPU oracle restates, the same hash over the oracle's results for the same operands (downloaded from the
@@ -297,7 +335,7 @@ def extra_workloads():
     out = []
     for name, extra in specs:
         try:
-            args = [sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--steps", "10", "--warmup", "3"] + extra
+            args = [sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "10", "--warmup", "3"] + extra
             res = subprocess.run(args, capture_output=True, text=True, timeout=300)
             d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
             r = d["roofline"]
@@ -320,7 +358,7 @@ def extra_latency():
     out = []
     for name, extra, per_step in specs:
         try:
-            args = [sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--steps", "200", "--warmup", "20"] + extra
+            args = [sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "200", "--warmup", "20"] + extra
             res = subprocess.run(args, capture_output=True, text=True, timeout=300)
             d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
             # blindrotate: a step of the bench is a loop of several external products; value = external products per second at batch 1
@@ -554,6 +592,11 @@ def main():
 
     wall, ev_ms = timed(step, args.steps, args.warmup)
     ms_per_step = wall * 1e3 / args.steps
+    if args.dump_outputs:                            # before any leg of --full touches the buffers
+        names = {"multiply": ("r",), "fwdinv": ("a",), "ct": ("c0", "c1", "c2"), "relin": ("c0", "c1"), "ctrelin": ("c0", "c1"),
+                 "blindrotate": ("acc0", "acc1")}[args.op]
+        bufs = ins if args.op in ("fwdinv", "relin") else outs          # these two work in place
+        dump_outputs(pkg, args.dump_outputs, [(name + (f".rank{rank}" if world > 1 else ""), buf) for name, buf in zip(names, bufs)], moduli, n, B)
     per_unit = args.br_steps if args.op == "blindrotate" else 1
     units_per_step = B * per_unit                    # units one rank processes per step
     total_units = units_per_step * world
@@ -603,13 +646,13 @@ def main():
         out["roofline"]["traffic"] = tr["bytes"]
         out["roofline"]["traffic_source"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (per-shape factors: profiles/r03_fetch_calibration.txt), "
                                              "profiles/" + tr["source"] + ": " + " + ".join(tr["kernels"]))
-    if not args.no_extras and args.op == "multiply":
+    if args.full and not args.no_extras and args.op == "multiply":
         w2, e2 = timed(lambda: (eng.forward(dA, B), eng.inverse(dA, B)), args.steps, args.warmup)
         pair_ms = e2 / args.steps
         out["extra_fwd_inv_pairs"] = {"pairs_per_s": (B if args.shard == "limb" else B * world) / (w2 / args.steps), "achieved_GBps": 4 * S * B / (pair_ms * 1e-3) / 1e9,
                                       "frac": 4 * S * B / (pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
     # every rank proves its own shard (outside the timed region): result checksum + oracle spot check, gathered to rank 0
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         csum, want = verify_shard(pkg, args.op, moduli, n, B, ins, outs, [(sd, all_moduli, my_limbs) for sd in in_seeds], relin=relin_host)
         sums = sharding.gather_ints(dist, csum, device=red_dev)
         wants = sharding.gather_ints(dist, -1 if want is None else want, device=red_dev)
@@ -624,12 +667,12 @@ def main():
     else:
         out["ranks_seen"] = len(set(sharding.gather_ints(dist, rank, device=red_dev)))
     out["dist_backend"] = None if dist is None else (args.dist_backend + (" (RCCL over xGMI)" if args.dist_backend == "nccl" else " (CPU rehearsal)"))
-    if rank == 0 and world == 1 and not args.no_extras and args.op == "multiply":
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.op == "multiply":
         out["extra_width_classes"] = extra_width_classes(pkg)
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_extra_workloads and args.op == "multiply" and args.shard == "batch":
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_extra_workloads and args.op == "multiply" and args.shard == "batch":
         out["extra_workloads"] = extra_workloads()
         out["extra_latency"] = extra_latency()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.op == "multiply":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.op == "multiply":
         out["cpu_baseline"] = cpu_baseline(n, moduli)
     if rank == 0:
         print(json.dumps(out), flush=True)

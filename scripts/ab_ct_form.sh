@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B: tensor product of the 8-byte fields as one launch (four live arrays) or two (FHE_HIP_CT_FORM=one|two), alone and inside the one-call multiply
-run() { python bench.py "$@" --no-cpu-baseline --no-extras | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['frac'])"; }
+run() { python bench.py --full "$@" --no-cpu-baseline --no-extras | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['frac'])"; }
 for n in ${SIZES:-8192 4096 2048}; do
 for cfg in "40 3 20" "60 2 32" "64 2 32"; do set -- $cfg
   for op in ct ctrelin; do

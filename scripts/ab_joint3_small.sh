@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B: three-array one-workgroup-per-limb kernels (default where use_joint3 says so) against the split forms (FHE_HIP_SPLIT_KEYSWITCH=1), 8-byte residues
-run() { python bench.py "$@" --no-cpu-baseline --no-extras | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['frac'])"; }
+run() { python bench.py --full "$@" --no-cpu-baseline --no-extras | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['frac'])"; }
 for n in ${SIZES:-8192 4096 2048}; do
 for cfg in "40 3 20" "60 2 32" "64 2 32"; do set -- $cfg
   for op in relin ctrelin blindrotate; do

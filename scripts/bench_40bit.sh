@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=gpurun_out/matrix_40bit.jsonl; : > $OUT
-run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
+run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
 ENVV="X=1"
 run --steps 10 --warmup 2 --op multiply --batch 1024 --bits 40 --limbs 3
 run --steps 10 --warmup 2 --op multiply --batch 512 --n 16384 --limbs 6 --bits 40

@@ -3,7 +3,7 @@
 TAG=${1:-r01}
 OUT=gpurun_out/ab_twiddles_$TAG.jsonl
 : > $OUT
-run() { echo "== $*" >&2; timeout -k 10 600 python bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
+run() { echo "== $*" >&2; timeout -k 10 600 python bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
 for v in 0 1 0 1; do
   if [ $v = 1 ]; then export FHE_HIP_NO_LDS_TWIDDLES=1; else unset FHE_HIP_NO_LDS_TWIDDLES; fi
   run --steps 10 --warmup 2 --op relin --batch 1024

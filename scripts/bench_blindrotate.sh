@@ -3,7 +3,7 @@
 TAG=${1:-r01}
 OUT=gpurun_out/blindrotate_$TAG.jsonl
 : > $OUT
-run() { echo "== $*" >&2; timeout -k 10 600 python bench.py --no-cpu-baseline --op blindrotate "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
+run() { echo "== $*" >&2; timeout -k 10 600 python bench.py --full --no-cpu-baseline --op blindrotate "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
 run --steps 5 --warmup 1 --batch 1024 --n 8192  --limbs 4 --bits 30
 run --steps 5 --warmup 1 --batch 128  --n 16384 --limbs 6 --bits 30
 run --steps 5 --warmup 1 --batch 512  --n 16384 --limbs 6 --bits 30

@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=gpurun_out/matrix_relin.jsonl; : > $OUT
-run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
+run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
 for ENVV in "X=1" "FHE_HIP_KS16=1"; do
 run --steps 10 --warmup 2 --op relin   --batch 1024
 run --steps 10 --warmup 2 --op ctrelin --batch 1024

@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=gpurun_out/matrix_relin8.jsonl; : > $OUT
-run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
+run() { echo "== $ENVV $*" >&2; timeout -k 10 600 env $ENVV python bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT || echo "FAILED: $*" >&2; }
 for ENVV in "X=1" "FHE_HIP_NO_FUSED_KEYSWITCH=1"; do
 run --steps 5 --warmup 1 --op relin   --batch 128 --n 16384 --limbs 6 --bits 40
 run --steps 5 --warmup 1 --op relin   --batch 512 --bits 40 --limbs 3

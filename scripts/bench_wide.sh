@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/wide.jsonl}; : > "$OUT"
 for bits in 250 120 128; do
   L=2
   for op in multiply fwdinv; do
-    python bench.py --no-extra-workloads --steps 5 --warmup 2 --op $op --batch 128 --bits $bits --limbs $L 2>/dev/null | tail -1 >> "$OUT"
+    python bench.py --full --no-extra-workloads --steps 5 --warmup 2 --op $op --batch 128 --bits $bits --limbs $L 2>/dev/null | tail -1 >> "$OUT"
   done
 done
 python3 - "$OUT" <<'PY'

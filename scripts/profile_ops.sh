@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/${TAG}_ops
 mkdir -p "$OUT"; export TMPDIR=/tmp; cd "$ROOT"
 prof() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1 || { echo "FAILED $name"; return 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1 || { echo "FAILED $name"; return 1; }
   grep '^{' "$OUT/$name.log" > "$OUT/$name.json"
   cp "$OUT/$name"/*/*_kernel_stats.csv "$OUT/${name}_kernel_stats.csv"
   rm -rf "$OUT/$name"

@@ -6,9 +6,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/${TAG}_sq
 mkdir -p "$OUT"; export TMPDIR=/tmp; cd "$ROOT"
 CNT="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"
-rocprofv3 --pmc $CNT --output-format csv -d "$OUT/multiply" -- python3 bench.py --steps 2 --warmup 1 --batch 1024 --no-cpu-baseline > "$OUT/multiply.log" 2>&1 \
- && rocprofv3 --pmc $CNT --output-format csv -d "$OUT/ctrelin" -- python3 bench.py --steps 2 --warmup 1 --batch 1024 --op ctrelin --no-cpu-baseline > "$OUT/ctrelin.log" 2>&1 \
- && rocprofv3 --pmc $CNT --output-format csv -d "$OUT/fwdinv" -- python3 bench.py --steps 2 --warmup 1 --batch 1024 --op fwdinv --no-cpu-baseline > "$OUT/fwdinv.log" 2>&1
+rocprofv3 --pmc $CNT --output-format csv -d "$OUT/multiply" -- python3 bench.py --full --steps 2 --warmup 1 --batch 1024 --no-cpu-baseline > "$OUT/multiply.log" 2>&1 \
+ && rocprofv3 --pmc $CNT --output-format csv -d "$OUT/ctrelin" -- python3 bench.py --full --steps 2 --warmup 1 --batch 1024 --op ctrelin --no-cpu-baseline > "$OUT/ctrelin.log" 2>&1 \
+ && rocprofv3 --pmc $CNT --output-format csv -d "$OUT/fwdinv" -- python3 bench.py --full --steps 2 --warmup 1 --batch 1024 --op fwdinv --no-cpu-baseline > "$OUT/fwdinv.log" 2>&1
 echo "rc=$?"
 python3 - <<PY
 import csv, glob, collections

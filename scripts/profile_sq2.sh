@@ -9,8 +9,8 @@ rocprofv3 --list-avail > "$OUT/avail.txt" 2>&1
 grep -o "SQ_[A-Z0-9_]*" "$OUT/avail.txt" | sort -u > "$OUT/sq_names.txt"
 CNT1="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 CNT2="SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_INSTS_VALU"
-rocprofv3 --pmc $CNT1 --output-format csv -d "$OUT/relin1" -- python3 bench.py --steps 2 --warmup 1 --batch 1024 --op relin --no-cpu-baseline > "$OUT/relin1.log" 2>&1 \
- && rocprofv3 --pmc $CNT2 --output-format csv -d "$OUT/relin2" -- python3 bench.py --steps 2 --warmup 1 --batch 1024 --op relin --no-cpu-baseline > "$OUT/relin2.log" 2>&1
+rocprofv3 --pmc $CNT1 --output-format csv -d "$OUT/relin1" -- python3 bench.py --full --steps 2 --warmup 1 --batch 1024 --op relin --no-cpu-baseline > "$OUT/relin1.log" 2>&1 \
+ && rocprofv3 --pmc $CNT2 --output-format csv -d "$OUT/relin2" -- python3 bench.py --full --steps 2 --warmup 1 --batch 1024 --op relin --no-cpu-baseline > "$OUT/relin2.log" 2>&1
 echo "rc=$?"
 python3 - <<PY
 import csv, glob, collections

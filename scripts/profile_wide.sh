@@ -12,10 +12,10 @@ mkdir -p "$OUT"; export TMPDIR=/tmp; cd "$ROOT"
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 rc=0
 for op in multiply fwdinv; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${op}_trace" -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_trace.log" 2>&1 \
-  && rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/${op}_pmc_fetch" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_pmc_fetch.log" 2>&1 \
-  && rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/${op}_pmc_write" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_pmc_write.log" 2>&1 \
-  && rocprofv3 --pmc $SQ --output-format csv -d "$OUT/${op}_sq" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_sq.log" 2>&1 \
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${op}_trace" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_trace.log" 2>&1 \
+  && rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/${op}_pmc_fetch" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_pmc_fetch.log" 2>&1 \
+  && rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/${op}_pmc_write" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_pmc_write.log" 2>&1 \
+  && rocprofv3 --pmc $SQ --output-format csv -d "$OUT/${op}_sq" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --op $op $ARGS > "$OUT/${op}_sq.log" 2>&1 \
   || { rc=1; break; }
 done
 echo "profile rc=$rc"

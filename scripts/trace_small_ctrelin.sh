@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.." || exit 1
 OUT=${1:-gpurun_out/trace_small}; rm -rf "$OUT"; mkdir -p "$OUT"
 for op in ctrelin multiply; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$op" -- python3 bench.py --no-extra-workloads --no-cpu-baseline --op $op --batch 1 --steps 300 --warmup 20 > "$OUT/$op.log" 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$op" -- python3 bench.py --full --no-extra-workloads --no-cpu-baseline --op $op --batch 1 --steps 300 --warmup 20 > "$OUT/$op.log" 2>&1 || exit 1
   python3 - "$OUT/$op" "$op" <<'PY'
 import csv, glob, os, sys
 f = sorted(glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True), key=lambda p: -os.path.getsize(p))[0]

@@ -1,5 +1,5 @@
-"""GPU test: bench.py prints ONE JSON line that carries every field of the driver's contract (metric, value, roofline,
-cpu_baseline ...) -- run small, in a child process, exactly as the driver runs it."""
+"""GPU test: bench.py prints ONE JSON line that carries every field of the driver's contract (metric, value, roofline; with --full
+also cpu_baseline, the extra legs and the oracle check ...) -- run small, in a child process, exactly as the driver runs it."""
 import json
 import os
 import subprocess
@@ -20,7 +20,7 @@ def _run(*args):
 
 @pytest.mark.gpu
 def test_default_workload_line_has_every_contract_field():
-    d = _run("--steps", "3", "--warmup", "1", "--batch", "128")
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--batch", "128")
     assert d["metric"].startswith("NTT-polymul/sec (N=8192, 4 RNS limbs)") and d["unit"] == "polymul/s"
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "u32"
@@ -62,7 +62,7 @@ def test_default_workload_line_has_every_contract_field():
 def test_gpus_2_spawns_two_ranks_and_verifies_both_shards():
     """`bench.py --gpus 2` with no launcher around it starts the two ranks itself (here both on device 0 over gloo: the one-GPU
     rehearsal of the driver's multi-GPU run) and reports both ranks' checksums, each equal to the CPU oracle's."""
-    d = _run("--gpus", "2", "--dist-backend", "gloo", "--device-override", "0", "--batch", "256", "--steps", "3", "--warmup", "1")
+    d = _run("--full", "--gpus", "2", "--dist-backend", "gloo", "--device-override", "0", "--batch", "256", "--steps", "3", "--warmup", "1")
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["verified"] is True
     assert len(d["shard_checksums"]) == 2 and d["shard_checksums"] == d["oracle_checksums"]
     assert d["shard_checksums"][0] != d["shard_checksums"][1]            # every rank works on its own data
@@ -78,7 +78,7 @@ def test_one_rank_rccl_group_carries_the_barriers_and_gathers():
     env = dict(os.environ, FHE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--no-extras"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--no-extras"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
@@ -100,7 +100,7 @@ def test_gpus_n_without_a_device_fails_loudly():
 @pytest.mark.gpu
 @pytest.mark.parametrize("op,unit", [("ctrelin", "ct-mul/s"), ("blindrotate", "extprod/s"), ("fwdinv", "ntt-pair/s")])
 def test_other_workloads_report_their_own_units(op, unit):
-    d = _run("--steps", "2", "--warmup", "1", "--batch", "16", "--op", op, "--no-cpu-baseline")
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--batch", "16", "--op", op, "--no-cpu-baseline")
     assert d["unit"] == unit and d["value"] > 0 and d["config"]["op"] == op and "cpu_baseline" not in d
     r = d["roofline"]; S = 32 * 8192 * 4
     assert r["secondary"]["bound"] == "valu-int-mul" and r["secondary"]["frac"] > 0
@@ -117,9 +117,37 @@ def test_other_workloads_report_their_own_units(op, unit):
 def test_limb_shard_rehearsal_two_ranks_union_is_the_product():
     """--gpus 2 --shard limb on the one GPU (gloo): rank 0 computes limbs {0, 2}, rank 1 limbs {1, 3} of the same global polynomials on
     engines built on those prime subsets; each rank's checksum equals the oracle's for ITS limbs, no collective carries payload."""
-    d = _run("--gpus", "2", "--shard", "limb", "--dist-backend", "gloo", "--device-override", "0", "--batch", "64", "--steps", "3", "--warmup", "1")
+    d = _run("--full", "--gpus", "2", "--shard", "limb", "--dist-backend", "gloo", "--device-override", "0", "--batch", "64", "--steps", "3", "--warmup", "1")
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["verified"] is True and d["scaling"] == "strong"
     assert d["shard_checksums"] == d["oracle_checksums"] and d["shard_checksums"][0] != d["shard_checksums"][1]
     assert d["config"]["parallelism"].startswith("limb-shard x2") and d["config"]["limbs_of_rank0"] == [0, 2]
     assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6          # the ranks jointly produce 64 whole products per step
     assert d["roofline"]["algorithmic_bytes_per_launch"] == 3 * 32 * 8192 * 2 * 64
+
+
+def test_full_and_dump_outputs_are_options():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs DIR" in res.stdout, res.stdout + res.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(pkg, oracle, tmp_path):
+    """Without --full the line carries the headline and its roofline only; --dump-outputs writes the sampled products of the last
+    timed step, equal to the oracle's products of the seeded operands and identical from run to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    d = _run("--steps", "4", "--warmup", "1", "--batch", "64", "--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "polymul/s" and d["dtype"] == "u32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6 and d["roofline"]["bound"] == "hbm"
+    assert not [k for k in d if k.startswith("extra_")] and "cpu_baseline" not in d and "verified" not in d and d["ranks_seen"] == 1
+    assert sorted(os.listdir(tmp_path / "a")) == ["r.npy"]
+    r = np.load(tmp_path / "a" / "r.npy")
+    assert r.dtype == np.float64 and r.shape == (64, 4, 8192)           # 16 MiB: the whole batch fits the budget
+    moduli = pkg.find_ntt_primes(30, 8192, 4)
+    rp = oracle.RnsPlan(8192, moduli)
+    for b in (0, 37, 63):                                               # operands: fill_device seeds 1000 (a) and 5000 (b)
+        a_, b_ = (bench.host_poly(sd, moduli, 8192, b).reshape(1, 4, 8192, 4) for sd in (1000, 5000))
+        assert np.array_equal(r[b], rp.polymul(a_, b_)[0, ..., 0].astype(np.float64)), b
+    _run("--steps", "4", "--warmup", "1", "--batch", "64", "--dump-outputs", str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "r.npy"), r)
