@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -702,21 +703,36 @@ static int lds_width_id(const fhe_rns_ntt *h) {
 // Two-pass transforms of the word-sized classes (log2 n = 13 + sub_top): one launch of the LOGN = 13 instance per pass.  Between the
 // two launches the polynomials are COMPACT (sizeof(residue) bytes per coefficient, d_ws3); *_compact tell which pointers are.
 static size_t residue_bytes(const fhe_rns_ntt *h) { return h->width == FHE_WIDTH_32 ? 4 : 8; }
+static const char *const lds_op_name[] = {"forward", "inverse", "multiply", "tensor product", "key switch", "external product",
+                                          "pass forward", "pass inverse", "sub forward", "sub inverse", "sub multiply"};
+static const char *const lds_form_name[] = {"one-launch", "square", "16-per-thread", "four-workgroup", "two-launch", "three-launch", "split",
+                                            "three-array", "paired", "single (LDS twiddles)", "single (L2 twiddles)", "per-digit parts", "per-digit-pair parts"};
+// one call of the (field, log_n) instance: the instance launches exactly the form A asks for, or nothing and says so
+static int lds_launch(fhe_rns_ntt *h, const fhe_dev::LdsArgs &A, const char *what, int log_n = 0) {
+    if (!log_n) log_n = (int)h->log_n;
+    fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), log_n);
+    if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
+    if (!fn(A)) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "no LDS kernel for the %s in the %s form (%s inputs, %s outputs) at width %d, log2 N = %d", lds_op_name[A.op], lds_form_name[A.form],
+                 A.in_compact ? "compact" : "container", A.out_compact ? "compact" : "container", lds_width_id(h), log_n);
+        return fail(FHE_ERR_UNSUPPORTED, buf);
+    }
+    return post_launch(A.stream, what);
+}
 static int lds_big(fhe_rns_ntt *h, int op, void *dst, bool dst_compact, const void *src, bool src_compact, const void *src2, uint32_t polys, bool rconst,
                    const char *what) {
-    fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), 13);
-    if (!fn) return fail(FHE_ERR_UNSUPPORTED, "no LDS instance for the two-pass transform");
     const uint32_t chunk_max = (65535u / h->L) * h->L;      // grid.y of the pass kernel; chunks keep the limb phase
     const size_t dstep = (size_t)h->n * (dst_compact ? residue_bytes(h) : 32), sstep = (size_t)h->n * (src_compact ? residue_bytes(h) : 32);
     for (uint32_t done = 0; done < polys;) {
         const uint32_t chunk = polys - done < chunk_max ? polys - done : chunk_max;
-        fhe_dev::LdsArgs A{op, (char *)dst + done * dstep, nullptr, nullptr, (const char *)src + done * sstep, nullptr,
+        fhe_dev::LdsArgs A{op, 0, (char *)dst + done * dstep, nullptr, nullptr, (const char *)src + done * sstep, nullptr,
                            src2 ? (const char *)src2 + done * sstep : nullptr, nullptr, h->d_limbs, h->L, chunk, h->stream};
         A.top = h->sub_top; A.rconst = rconst;
-        fn(A);
+        int rc = lds_launch(h, A, what, 13); if (rc) return rc;
         done += chunk;
     }
-    return post_launch(h->stream, what);
+    return FHE_OK;
 }
 static int big_forward(fhe_rns_ntt *h, void *dst, const void *src, uint32_t polys) {
     int rc = ensure_ws3(h, (size_t)polys * h->n * residue_bytes(h)); if (rc) return rc;
@@ -729,66 +745,144 @@ static int big_inverse(fhe_rns_ntt *h, void *data, uint32_t polys) {
     return lds_big(h, fhe_dev::LDS_PASS_INV, data, false, h->d_ws3, true, nullptr, polys, false, "word_pass_kernel");
 }
 
-// Few ciphertexts on the paired key-switch kernel: one workgroup per digit pair and a combining launch (ntt_lds_small.hip.h) -- sets A.pair_ws.
-static int split_pairs_workspace(fhe_rns_ntt *h, fhe_dev::LdsArgs &A) {
-    if (h->width != FHE_WIDTH_32 || h->single_transforms || !fhe_dev::lds_paired_keyswitch(4, (int)h->log_n)) return FHE_OK;
-    const uint32_t NP = (h->L * A.K + 1) / 2;
-    if (NP < 2 || A.polys > h->split_pairs_polys) return FHE_OK;
-    // partial accumulators: one pair per digit PAIR, or (N <= 2^13: the 16-per-thread form, one workgroup per digit) one pair per digit
-    int rc = ensure_ws(h, 2 * (size_t)A.polys * (fhe_dev::lds_small_multiply(4, (int)h->log_n) ? h->L * A.K : NP) * h->n * 4); if (rc) return rc;
-    A.pair_ws = h->d_ws;
-    return FHE_OK;
-}
+// ---- kernel forms of the LDS-resident ops ---------------------------------------------------------------------------------
+// Which form runs a multiply, tensor product, key switch or external product is decided here and nowhere else: every entry point plans,
+// ensures the plan's workspace, fills LdsArgs and launches; fhe_rns_ntt_reserve sizes the workspaces with the same planners.
+struct LdsPlan {
+    fhe_dev::LdsForm form;
+    int ws = 0;                          // the form's workspace: 0 none, 1 d_ws, 3 d_ws3
+    size_t bytes = 0;
+    bool compact = false;                // key switch: c2 is read compact (compacted first, or from the fused tensor product); external product: the
+                                         // blind-rotation loop keeps the accumulator pair compact
+    bool prerot = false;                 // external product: the loop applies the monomial factor once per step (rotated digit sources b0, b1)
+};
+static void *plan_ws(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? h->d_ws : p.ws == 3 ? h->d_ws3 : nullptr; }
+static int ensure_plan(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? ensure_ws(h, p.bytes) : p.ws == 3 ? ensure_ws3(h, p.bytes) : FHE_OK; }
 
+static int lds_eb(const fhe_rns_ntt *h) { return h->width == FHE_WIDTH_32 ? 4 : 8; }
+// r = a * b of `polys` limb polynomials; same_operands: b == a (not broadcast)
+static LdsPlan plan_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands) {
+    const int eb = lds_eb(h), ln = (int)h->log_n;
+    // a handful of polynomials: four workgroups each (in place is fine: every operand container is read by the first launch, the result containers
+    // are written by the third)
+    if (polys <= h->coop_polys && fhe_dev::lds_coop4_multiply(eb, ln)) return {fhe_dev::LDS_COOP4, 3, 3 * polys * h->n * 4};
+    if (polys <= h->small_batch_polys && fhe_dev::lds_small_multiply(eb, ln)) return {fhe_dev::LDS_SMALL16};   // few: one workgroup's latency is what counts
+    return {same_operands && !h->no_square ? fhe_dev::LDS_SQUARE : fhe_dev::LDS_ONE_LAUNCH};
+}
+// Tensor product of `polys` limb polynomials per component; compact_out: c0, c1, c2 as compact polynomials (the fused multiply + relinearise);
+// alone: no other chunk of the call runs beside it.
+// Two launches (ntt_forward_compact_kernel + ntt_ct_a_kernel, workspace for the transformed b-side) instead of the one-launch kernel: always
+// where that kernel does not exist (8-byte residues at N = 2^14, N = 2^15), and for the 8-byte residues where the interleaved A/B favoured it
+// (scripts/ab_ct_form.sh, one MI355X, batch 1024, N = 8192 / 4096 / 2048): the FP64 field (tensor product +32 / +35 / +26 %, full multiply
+// +11 / +10 / +2 %) and the stand-alone tensor product of the full-range 64-bit field (+13 / +11 / +12 %; inside the full multiply
+// 0 / -9 / -2 %); the lazy 64-bit field keeps its one-launch kernel (-1 / +6 / -4 %).  The squaring forms stay on the one-launch kernel
+// (5 transforms).  FHE_HIP_CT_FORM=one|two forces a form where both exist.
+static LdsPlan plan_ct_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands, bool compact_out, bool alone) {
+    const int eb = lds_eb(h), ln = (int)h->log_n;
+    const bool square = same_operands && !compact_out && !h->no_square;
+    bool two = !h->no_two_launch_ct && fhe_dev::lds_ct_two_launch(eb, ln);
+    if (two && fhe_dev::lds_ct_fused(eb, ln)) {
+        bool want = h->width == FHE_WIDTH_52 || (h->width == FHE_WIDTH_64X && !compact_out);
+        if (h->ct_form_force) want = h->ct_form_force == 2;       // FHE_HIP_CT_FORM=one|two (A/B, cross-check)
+        two = want && !square;
+    }
+    if (two) return {fhe_dev::LDS_TWO_LAUNCH, 1, 2 * polys * h->n * eb};
+    if (compact_out && alone && polys <= h->coop_polys && fhe_dev::lds_coop4_multiply(eb, ln))     // a handful of ciphertexts: four workgroups per limb polynomial
+        return {fhe_dev::LDS_COOP4, 3, 7 * polys * h->n * 4};
+    if (compact_out && polys <= h->split_pairs_polys && fhe_dev::lds_small_multiply(eb, ln))      // few ciphertexts: the 16-per-thread tensor product (and the split key switch)
+        return {fhe_dev::LDS_SMALL16};
+    if (fhe_dev::lds_ct_fused(eb, ln)) return {square ? fhe_dev::LDS_SQUARE : fhe_dev::LDS_ONE_LAUNCH};
+    return {fhe_dev::LDS_THREE_LAUNCH};
+}
 // Key switch / external product of the 8-byte residues (and of the 4-byte residues at N = 2^15): ONE workgroup per (ciphertext, limb)
 // with three live arrays (ntt_keyswitch3_kernel / ntt_extprod3_kernel) instead of the split form -- everywhere it was faster in the
 // interleaved A/B (scripts/ab_keyswitch3.sh, ab_extprod3.sh, ab_joint3_small.sh; with the descriptor loads of round 2): every size for
 // the lazy 64-bit field (+4...+60 %) and for the FP64 field's external product and compact-operand key switch (+10...+46 %); the FP64
 // field's stand-alone key switch (container operands) from N = 2^13 (3-6 % behind at N <= 4096); the full-range 64-bit field from
-// N = 2^12 (at N = 2048: key switch -3 %, external product -16 %).
+// N = 2^12 (at N = 2048: key switch -3 %, external product -16 %).  Never under FHE_HIP_SPLIT_KEYSWITCH=1 (a testing aid).
 static bool use_joint3(const fhe_rns_ntt *h, bool extprod, bool compact) {
-    const int eb = h->width == FHE_WIDTH_32 ? 4 : 8;
-    if (h->split_keyswitch || !fhe_dev::lds_keyswitch_joint3(eb, (int)h->log_n)) return false;
+    if (h->split_keyswitch || !fhe_dev::lds_keyswitch_joint3(lds_eb(h), (int)h->log_n)) return false;
     if (h->width == FHE_WIDTH_52) return extprod || compact || h->log_n >= 13;
     if (h->width == FHE_WIDTH_64X) return h->log_n >= 12;
     return true;
 }
-// Tensor product in two launches (ntt_forward_compact_kernel + ntt_ct_a_kernel, workspace for the transformed b-side) instead of the
-// one-launch kernel: always where that kernel does not exist (8-byte residues at N = 2^14, N = 2^15), and for the 8-byte residues
-// where the interleaved A/B favoured it (scripts/ab_ct_form.sh, one MI355X, batch 1024, N = 8192 / 4096 / 2048): the FP64 field
-// (tensor product +32 / +35 / +26 %, full multiply +11 / +10 / +2 %) and the stand-alone tensor product of the full-range 64-bit
-// field (+13 / +11 / +12 %; inside the full multiply 0 / -9 / -2 %); the lazy 64-bit field keeps its one-launch kernel (-1 / +6 / -4 %).
-// The squaring forms stay on the one-launch kernel (5 transforms).  FHE_HIP_CT_FORM=one|two forces a form where both exist.
-static int ct_workspace(fhe_rns_ntt *h, fhe_dev::LdsArgs &A) {
-    const int eb = h->width == FHE_WIDTH_32 ? 4 : 8;
-    if (h->no_two_launch_ct || !fhe_dev::lds_ct_two_launch(eb, (int)h->log_n)) return FHE_OK;
-    if (fhe_dev::lds_ct_fused(eb, (int)h->log_n)) {
-        bool want = h->width == FHE_WIDTH_52 || (h->width == FHE_WIDTH_64X && !A.compact_c2);
-        if (h->ct_form_force) want = h->ct_form_force == 2;       // FHE_HIP_CT_FORM=one|two (A/B, cross-check)
-        if (!want || A.square) return FHE_OK;
-    }
-    int rc = ensure_ws(h, 2 * (size_t)A.polys * h->n * eb); if (rc) return rc;
-    A.ws = h->d_ws;
-    return FHE_OK;
+// The fused FHEContext::multiply (tensor product with compact outputs straight into the key switch) on every LDS-resident size with packed keys
+static bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys) {
+    return packed_keys && h->width != FHE_WIDTH_256 && !h->sub_top && !h->single_transforms && !h->no_fused_ct_relin;
 }
-static int lds_run(fhe_rns_ntt *h, int op, void *r0, void *r1, void *r2, const void *a0, const void *a1, const void *b0,
-                   const void *b1, uint32_t polys, const char *what, uint32_t b_polys = 0) {
-    fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), (int)h->log_n);
-    if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
-    fhe_dev::LdsArgs A{op, r0, r1, r2, a0, a1, b0, b1, h->d_limbs, h->L, polys, h->stream};
-    A.single_transforms = h->single_transforms;
-    A.b_polys = b_polys;
-    A.small_batch = op == fhe_dev::LDS_MULTIPLY && polys <= h->small_batch_polys;
-    if (op == fhe_dev::LDS_MULTIPLY && polys <= h->coop_polys && fhe_dev::lds_coop4_multiply(h->width == FHE_WIDTH_32 ? 4 : 8, (int)h->log_n)) {
-        // (in place is fine: every operand container is read by the first launch, the result containers are written by the third)
-        int rc = ensure_ws3(h, 3 * (size_t)polys * h->n * 4); if (rc) return rc;
-        A.coop_ws = h->d_ws3;
+// Key switch of `polys` limb polynomials with K digits.  KS_C2: c2 in containers, compacted first where that pays; KS_C2_AS_IS: containers that
+// must stay where they are (c2 already in d_ws2: the composed multiply + relinearise under a testing switch); KS_FUSED: c2 and the addends
+// are compact polynomials from the fused tensor product.  alone: no other chunk of the call runs beside it (the few-ciphertext parts take d_ws).
+enum KsSource { KS_C2, KS_C2_AS_IS, KS_FUSED };
+static LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone) {
+    const int eb = lds_eb(h), ln = (int)h->log_n;
+    const bool joint3 = use_joint3(h, false, src == KS_FUSED);
+    const bool paired32 = h->width == FHE_WIDTH_32 && !h->single_transforms && fhe_dev::lds_paired_keyswitch(4, ln);
+    LdsPlan p{fhe_dev::LDS_ONE_LAUNCH};
+    // Every limb workgroup re-reads all of c2 (the three-array kernels once per DIGIT): compact it once (a streaming pass: S read, S/4 or S/8
+    // written) so that those re-reads move compact polynomials instead of 32-byte containers -- round 2 counters at N = 2^14, 6 x 40-bit:
+    // 2.6 x the algorithmic bytes; on the 4-byte residues the container loads kept the address FIFO full 12 % of the time (round 3 SQ counters).
+    p.compact = src == KS_FUSED || (src == KS_C2 && ((joint3 && h->width != FHE_WIDTH_32) || paired32) && !h->no_c2_compaction);
+    // Few ciphertexts on the paired key-switch kernel: one workgroup per digit pair and a combining launch (ntt_lds_small.hip.h); partial
+    // accumulators: one pair per digit PAIR, or (N <= 2^13: the 16-per-thread form, one workgroup per digit) one pair per digit
+    const uint32_t NP = (h->L * K + 1) / 2;
+    if (alone && paired32 && NP >= 2 && polys <= h->split_pairs_polys) {
+        const bool d16 = fhe_dev::lds_small_multiply(4, ln);
+        p.form = d16 ? fhe_dev::LDS_PARTS16 : fhe_dev::LDS_PART_PAIRS;
+        p.ws = 1; p.bytes = 2 * polys * (d16 ? h->L * K : NP) * h->n * 4;
+    } else if (fhe_dev::lds_keyswitch_split(eb, ln)) {
+        p.form = joint3 ? fhe_dev::LDS_JOINT3 : fhe_dev::LDS_SPLIT;
+    } else if (fhe_dev::lds_paired_keyswitch(eb, ln) && !h->single_transforms) {
+        p.form = fhe_dev::LDS_PAIRED;
+    } else {
+        p.form = fhe_dev::lds_twiddles_in_lds(eb, ln) && !h->global_twiddles ? fhe_dev::LDS_SINGLE_LDS_TW : fhe_dev::LDS_SINGLE_L2_TW;
     }
-    A.square = !b_polys && !h->no_square &&
-               ((op == fhe_dev::LDS_MULTIPLY && a0 == b0) || (op == fhe_dev::LDS_CT_MULTIPLY && a0 == b0 && a1 == b1));
-    if (op == fhe_dev::LDS_CT_MULTIPLY) { int rc = ct_workspace(h, A); if (rc) return rc; }
-    fn(A);
-    return post_launch(h->stream, what);
+    return p;
+}
+// External product of a blind-rotation loop over `polys` limb polynomials per accumulator component, K digits (the largest of the loop's rows).
+static LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K) {
+    const int eb = lds_eb(h), ln = (int)h->log_n;
+    const bool w32 = h->width == FHE_WIDTH_32 && !h->single_transforms && !h->no_compact_blind_rotate;
+    LdsPlan p{fhe_dev::LDS_ONE_LAUNCH};
+    // Few accumulators (4-byte residues, N <= 2^13; what a bootstrapping of one or a few ciphertexts looks like): with one workgroup per (accumulator, limb)
+    // a step lasts as long as that workgroup's 2 L K / 2 paired transforms back to back (103 us per external product at N = 8192, L = 4, w = 16, batch 1).
+    // Here a step is three launches: the monomial factor (X^a - 1) once per step (a streaming pass), one workgroup per (accumulator, limb, component, DIGIT) on the
+    // 16-per-thread forward transform with that digit's two key products, and one workgroup per (accumulator, limb, output component) that sums the 2 L K partials,
+    // runs one inverse transform and adds the accumulator (ntt_keyswitch16_{part,comb}_kernel); two partial accumulators per (limb polynomial, component, digit).
+    // (N = 2^14: the same three launches on the paired 32-per-thread transforms, one workgroup per digit PAIR of a component)
+    if (w32 && !h->no_prerotation && fhe_dev::lds_paired_keyswitch(4, ln) && polys <= h->split_pairs_polys) {
+        const bool d16 = fhe_dev::lds_small_multiply(4, ln);
+        p.form = d16 ? fhe_dev::LDS_PARTS16 : fhe_dev::LDS_PART_PAIRS;
+        p.ws = 1; p.bytes = 2 * polys * h->n * (d16 ? 2 * (size_t)h->L * K : 2 * (((size_t)h->L * K + 1) / 2)) * 4;
+        p.compact = p.prerot = true;
+    // Paired kernel (4-byte residues up to N = 2^14): the accumulator pair lives in COMPACT form for the whole loop: the L limb workgroups of an
+    // accumulator each read all of it, which in container form is 3x the algorithmic traffic (profiles/r02_blindrotate_*) and made the first step
+    // of a loop 40 % slower than the others (1114 vs 785 us at N = 16384 x 6, profiles/r03_blindrotate_n16384_summary.txt).
+    } else if (w32 && fhe_dev::lds_paired_extprod(4, ln)) {
+        p.form = fhe_dev::LDS_PAIRED; p.compact = true;
+    // Three-array kernel (8-byte residues; 4-byte residues at N = 2^15): every limb workgroup re-reads each limb of the accumulator pair once per
+    // DIGIT (rotated), L * K * 2 reads per workgroup -- as containers that was several times the algorithmic traffic: compact pair, and the
+    // monomial factor once per step (a streaming pass over two compact polynomials) instead of once per digit inside the kernel.
+    } else if (use_joint3(h, true, false) && !h->no_compact_blind_rotate) {
+        p.form = fhe_dev::LDS_JOINT3; p.compact = true; p.prerot = !h->no_prerotation;
+    // container accumulators
+    } else if (fhe_dev::lds_keyswitch_split(eb, ln)) {
+        p.form = use_joint3(h, true, false) ? fhe_dev::LDS_JOINT3 : fhe_dev::LDS_SPLIT;
+    } else if (fhe_dev::lds_paired_extprod(eb, ln) && !h->single_transforms) {
+        p.form = fhe_dev::LDS_PAIRED;
+    } else {
+        p.form = fhe_dev::lds_twiddles_in_lds(eb, ln) && !h->global_twiddles ? fhe_dev::LDS_SINGLE_LDS_TW : fhe_dev::LDS_SINGLE_L2_TW;
+    }
+    return p;
+}
+
+// r = a * b on the LDS-resident sizes; b_polys: polynomials behind b (0 = as many as the batch, L = one RNS polynomial broadcast over the batch)
+static int lds_multiply(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t polys, uint32_t b_polys) {
+    const LdsPlan P = plan_multiply(h, polys, a == b && !b_polys);
+    int rc = ensure_plan(h, P); if (rc) return rc;
+    fhe_dev::LdsArgs A{fhe_dev::LDS_MULTIPLY, P.form, r, nullptr, nullptr, a, nullptr, b, nullptr, h->d_limbs, h->L, polys, h->stream};
+    A.ws = plan_ws(h, P); A.b_polys = b_polys;
+    return lds_launch(h, A, "ntt_multiply_kernel");
 }
 template <class F, int OP>
 static int lds_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t polys, const char *what) {
@@ -842,14 +936,14 @@ static int do_forward(fhe_rns_ntt *h, void *d_data, uint32_t batch) {
     const uint32_t polys = batch * h->L;
     if (h->sub_top) return big_forward(h, d_data, d_data, polys);
     if (h->width != FHE_WIDTH_256)
-        return lds_run(h, fhe_dev::LDS_FORWARD, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, polys, "ntt_forward_kernel");
+        return lds_launch(h, {fhe_dev::LDS_FORWARD, 0, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->d_limbs, h->L, polys, h->stream}, "ntt_forward_kernel");
     return run256_transform(h, (fhe_dev::u256 *)d_data, polys, true);
 }
 static int do_inverse(fhe_rns_ntt *h, void *d_data, uint32_t batch) {
     const uint32_t polys = batch * h->L;
     if (h->sub_top) return big_inverse(h, d_data, polys);
     if (h->width != FHE_WIDTH_256)
-        return lds_run(h, fhe_dev::LDS_INVERSE, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, polys, "ntt_inverse_kernel");
+        return lds_launch(h, {fhe_dev::LDS_INVERSE, 0, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->d_limbs, h->L, polys, h->stream}, "ntt_inverse_kernel");
     return run256_transform(h, (fhe_dev::u256 *)d_data, polys, false);
 }
 template <int OP>
@@ -920,8 +1014,7 @@ static int do_multiply(fhe_rns_ntt *h, void *d_r, const void *d_a, const void *d
         if ((rc = lds_big(h, fhe_dev::LDS_SUB_MULTIPLY, wa, true, wa, true, wb, polys, false, "ntt_sub_kernel"))) return rc;
         return lds_big(h, fhe_dev::LDS_PASS_INV, d_r, false, wa, true, nullptr, polys, true, "word_pass_kernel");
     }
-    if (h->width != FHE_WIDTH_256)
-        return lds_run(h, fhe_dev::LDS_MULTIPLY, d_r, nullptr, nullptr, d_a, nullptr, d_b, nullptr, polys, "ntt_multiply_kernel");
+    if (h->width != FHE_WIDTH_256) return lds_multiply(h, d_r, d_a, d_b, polys, 0);
     return h->wide_nl == 2 ? wide_multiply_t<2>(h, d_r, d_a, d_b, polys) : wide_multiply_t<4>(h, d_r, d_a, d_b, polys);
 }
 static int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0,
@@ -941,8 +1034,13 @@ static int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const vo
         for (void *c : {c0, c1, c2}) if ((rc = big_inverse(h, c, polys))) return rc;
         return FHE_OK;
     }
-    if (h->width != FHE_WIDTH_256)
-        return lds_run(h, fhe_dev::LDS_CT_MULTIPLY, c0, c1, c2, a0, a1, b0, b1, polys, "ntt_ct_multiply_kernel");
+    if (h->width != FHE_WIDTH_256) {
+        const LdsPlan P = plan_ct_multiply(h, polys, a0 == b0 && a1 == b1, false, true);
+        int rc = ensure_plan(h, P); if (rc) return rc;
+        fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, P.form, c0, c1, c2, a0, a1, b0, b1, h->d_limbs, h->L, polys, h->stream};
+        A.ws = plan_ws(h, P);
+        return lds_launch(h, A, "ntt_ct_multiply_kernel");
+    }
     return h->wide_nl == 2 ? wide_ct_multiply_t<2>(h, c0, c1, c2, a0, a1, b0, b1, polys) : wide_ct_multiply_t<4>(h, c0, c1, c2, a0, a1, b0, b1, polys);
 }
 
@@ -977,30 +1075,31 @@ extern "C" int fhe_rns_ntt_set_stream(fhe_rns_ntt_t *h, void *stream) {
 // transform workspace of the general paths (full-width class, two-pass sizes).  Relinearisation on the general path sizes its digit
 // workspace by itself (bounded to 1 GiB, chunked).
 extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
-    // The union of what every entry point asks of ensure_ws / ws2 / ws3 for `batch` units (each site cited), so that none of them allocates
-    // afterwards.  The key-switch workspaces depend on the digit count: the largest K of the key sets imported so far (import keys first).
+    // The union of what every entry point asks of ensure_ws / ws2 / ws3 for `batch` units, so that none of them allocates afterwards.  The
+    // key-switch workspaces depend on the digit count: the largest K of the key sets imported so far (import keys first).
     int rc = check_call(h, batch, "reserve"); if (rc) return rc;
     const size_t polys = (size_t)batch * h->L, S = (size_t)h->L * h->n * 32, eb = residue_bytes(h), cbytes = polys * h->n * eb;
     const bool lds_class = h->width != FHE_WIDTH_256 && !h->sub_top;
-    const uint32_t LK = h->L * (h->max_digits ? h->max_digits : 1);
     size_t ws = 0, ws2 = (size_t)batch * S, ws3 = 0;                   // ws2: one container component (c2 of multiply + relinearise on the general path) ...
-    if (6 * cbytes > ws2) ws2 = 6 * cbytes;                            // ... or 4 compact accumulators + 2 rotated ones of a blind-rotation loop on the 8-byte fields
+    if (6 * cbytes > ws2) ws2 = 6 * cbytes;                            // ... or the 3 compact components of the fused multiply + relinearise, the 4 or 6 of a blind-rotation loop
     if (!lds_class) ws = 5 * (size_t)batch * S;                        // 4 transformed operands + one product (tensor product of the general / two-pass paths)
-    else ws = 2 * cbytes;                                              // transformed b-side of the two-launch tensor product (2 compact components)
     if (h->max_composed_digits) {                                      // digit polynomials + two accumulators of the composed key switch (key sets without packed tables)
         const size_t LK = (size_t)h->L * h->max_composed_digits;
         size_t chunk = ((size_t)1 << 30) / ((LK + 2) * S); if (chunk < 1) chunk = 1; if (chunk > batch) chunk = batch;
         if ((LK + 2) * chunk * S > ws) ws = (LK + 2) * chunk * S;
     }
-    // (the few-ciphertext forms are taken by every call of at most split_pairs_polys / coop_polys limb polynomials: a smaller batch than the reserved one included)
-    if (lds_class && h->width == FHE_WIDTH_32 && h->split_pairs_polys) {            // few ciphertexts: one workgroup per digit pair, partial sums in the workspace
-        // N <= 2^13: one pair per digit, and two digit sources in a blind-rotation step (2 L K partials per limb polynomial)
-        const size_t NP = fhe_dev::lds_small_multiply(4, (int)h->log_n) ? 2 * LK : 2 * ((LK + 1) / 2), few = polys < h->split_pairs_polys ? polys : h->split_pairs_polys;
-        if (2 * few * NP * h->n * 4 > ws) ws = 2 * few * NP * h->n * 4;
-    }
     if (h->sub_top) ws3 = 2 * cbytes;                                  // two compact operands of a two-pass multiply
-    if (lds_class && h->coop_polys && fhe_dev::lds_coop4_multiply((int)eb, (int)h->log_n))
-        ws3 = 7 * (polys < h->coop_polys ? polys : h->coop_polys) * h->n * 4;       // few polynomials over four workgroups each: 3 (multiply) / 7 (tensor product) block images per limb polynomial
+    if (lds_class) {
+        // the workspace of every form the planners pick for up to `batch` units: the few-polynomial forms are taken by every call of at most
+        // split_pairs_polys / coop_polys limb polynomials, a smaller batch than the reserved one included
+        const uint32_t K = h->max_digits ? h->max_digits : 1;
+        for (size_t p : {polys, std::min<size_t>(polys, h->split_pairs_polys), std::min<size_t>(polys, h->coop_polys)})
+            for (const LdsPlan &P : {plan_multiply(h, p, false), plan_ct_multiply(h, p, false, false, true), plan_ct_multiply(h, p, false, true, true),
+                                     plan_keyswitch(h, p, K, KS_C2, true), plan_keyswitch(h, p, K, KS_FUSED, true), plan_extprod(h, p, K)}) {
+                size_t &need = P.ws == 1 ? ws : ws3;
+                if (P.ws && P.bytes > need) need = P.bytes;
+            }
+    }
     if ((rc = ensure_ws(h, ws)) || (rc = ensure_ws2(h, ws2)) || (ws3 && (rc = ensure_ws3(h, ws3)))) return rc;
     return ensure_aux_stream(h);                                       // second stream + events of the chunked pipelines
 }
@@ -1038,7 +1137,7 @@ extern "C" int fhe_rns_ntt_multiply_bcast(fhe_rns_ntt_t *h, void *r, const void 
     if (!r || !a || !b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: null argument");
     if (r == b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: the result must not overwrite the shared operand");
     if (h->width != FHE_WIDTH_256 && !h->sub_top)   // every workgroup reads limb (p % L) of the one shared polynomial: L2 hits after the first use
-        return lds_run(h, fhe_dev::LDS_MULTIPLY, r, nullptr, nullptr, a, nullptr, b_one, nullptr, batch * h->L, "ntt_multiply_kernel", h->L);
+        return lds_multiply(h, r, a, b_one, batch * h->L, h->L);
     const size_t S = (size_t)h->L * h->n * 32;
     for (uint32_t i = 0; i < batch; i++)
         if ((rc = do_multiply(h, (char *)r + i * S, (const char *)a + i * S, b_one, 1))) return rc;
@@ -1242,53 +1341,48 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
     if (rk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: keys were imported for a different engine");
     if (d_c0 == d_c1 || d_c0 == d_c2 || d_c1 == d_c2) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: components must be distinct buffers");
     if ((rc = check_inputs(h, {d_c0, d_c1, d_c2}, batch))) return rc;
-    if (rk->d_pkb) {   // word-sized paths: one fused launch
-        fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), (int)h->log_n);
-        if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
-        fhe_dev::LdsArgs A{fhe_dev::LDS_KEYSWITCH, d_c0, d_c1, nullptr, d_c2, nullptr, nullptr, nullptr, h->d_limbs, h->L, batch * h->L, h->stream};
-        A.kb = rk->d_pkb; A.ka = rk->d_pka; A.K = rk->K; A.w = rk->decomp_bits;
-        A.global_twiddles = h->global_twiddles;
-        A.single_transforms = h->single_transforms;
-        A.joint3 = use_joint3(h, false, false);
+    if (rk->d_pkb) {   // word-sized paths: fused launches
+        // (c2 already in the workspace: the composed multiply + relinearise under a testing switch -- it stays where it is)
         const bool c2_in_ws2 = h->d_ws2 && (const char *)d_c2 >= (const char *)h->d_ws2 && (const char *)d_c2 < (const char *)h->d_ws2 + h->ws2_bytes;
-        const size_t eb = residue_bytes(h), S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * eb;
-        const bool paired32 = h->width == FHE_WIDTH_32 && !h->single_transforms && fhe_dev::lds_paired_keyswitch(4, (int)h->log_n);
-        if (((A.joint3 && h->width != FHE_WIDTH_32) || paired32) && !h->no_c2_compaction && !c2_in_ws2) {   // (c2 already in the workspace: the composed multiply + relinearise under a testing switch)
-            // Every limb workgroup re-reads all of c2 (the three-array kernels once per DIGIT): compact it once (a streaming pass: S read, S/4 or
-            // S/8 written) so that those re-reads move compact polynomials instead of 32-byte containers -- round 2 counters at N = 2^14, 6 x 40-bit:
-            // 2.6 x the algorithmic bytes; on the 4-byte residues the container loads kept the address FIFO full 12 % of the time (round 3 SQ counters).
-            // Chunks of whole ciphertexts on two streams: the compaction of chunk i+1 (HBM-bound) runs beside the key switch of chunk i.
+        const LdsPlan P = plan_keyswitch(h, batch * h->L, rk->K, c2_in_ws2 ? KS_C2_AS_IS : KS_C2, true);
+        const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * residue_bytes(h);
+        uint32_t chunks = 1;
+        if (P.compact) {
             if ((rc = ensure_ws2(h, (size_t)batch * Sc))) return rc;
+            // Chunks of whole ciphertexts on two streams: the compaction of chunk i+1 (HBM-bound) runs beside the key switch of chunk i.
             // (measured, N = 8192 x 4 x 30-bit, batch 1024: compaction alone 773 K -> 805 K relin/s at w = 16, 948 K -> 1007 K at w = 30; with the key switch of
             //  chunk i beside the compaction of chunk i+1 on a second stream 807 K / 953 K at two chunks, 772 K / 948 K at four: one stream unless asked)
-            uint32_t chunks = (paired32 && h->relin_chunks_forced) ? h->overlap_chunks : 1;
+            if (h->width == FHE_WIDTH_32 && h->relin_chunks_forced) chunks = h->overlap_chunks;
             while (chunks > 1 && ((size_t)batch * h->L / chunks < 1024 || batch < chunks)) chunks--;
             if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
-            for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
-                const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
-                char *c2c = (char *)h->d_ws2 + (size_t)b0 * Sc;
-                if ((rc = compact_poly(h, c2c, (const char *)d_c2 + (size_t)b0 * S, (size_t)nb * h->L * h->n))) return rc;
-                fhe_dev::LdsArgs B = A;
-                B.r0 = (char *)d_c0 + (size_t)b0 * S; B.r1 = (char *)d_c1 + (size_t)b0 * S; B.a0 = c2c; B.polys = nb * h->L; B.c2_only_compact = true;
-                if (chunks == 1 && (rc = split_pairs_workspace(h, B))) return rc;
-                if (chunks > 1) {
-                    HIP_TRY(hipEventRecord(h->ev_chunk[c], h->stream));
-                    HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_chunk[c], 0));
-                    B.stream = h->aux_stream;
-                }
-                fn(B);
-                if ((rc = post_launch(B.stream, "ntt_keyswitch_kernel"))) return rc;
-                b0 += nb;
-            }
-            if (chunks > 1) {
-                HIP_TRY(hipEventRecord(h->ev_join, h->aux_stream));
-                HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-            }
-            return FHE_OK;
         }
-        if ((rc = split_pairs_workspace(h, A))) return rc;
-        fn(A);
-        return post_launch(h->stream, "ntt_keyswitch_kernel");
+        for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
+            const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
+            const void *c2 = (const char *)d_c2 + (size_t)b0 * S;
+            if (P.compact) {
+                char *c2c = (char *)h->d_ws2 + (size_t)b0 * Sc;
+                if ((rc = compact_poly(h, c2c, c2, (size_t)nb * h->L * h->n))) return rc;
+                c2 = c2c;
+            }
+            const LdsPlan Q = chunks == 1 ? P : plan_keyswitch(h, nb * h->L, rk->K, KS_C2, false);
+            if ((rc = ensure_plan(h, Q))) return rc;
+            fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, Q.form, (char *)d_c0 + (size_t)b0 * S, (char *)d_c1 + (size_t)b0 * S, nullptr, c2, nullptr, nullptr, nullptr,
+                               h->d_limbs, h->L, nb * h->L, h->stream};
+            B.in_compact = Q.compact; B.ws = plan_ws(h, Q);
+            B.kb = rk->d_pkb; B.ka = rk->d_pka; B.K = rk->K; B.w = rk->decomp_bits;
+            if (chunks > 1) {
+                HIP_TRY(hipEventRecord(h->ev_chunk[c], h->stream));
+                HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_chunk[c], 0));
+                B.stream = h->aux_stream;
+            }
+            if ((rc = lds_launch(h, B, "ntt_keyswitch_kernel"))) return rc;
+            b0 += nb;
+        }
+        if (chunks > 1) {
+            HIP_TRY(hipEventRecord(h->ev_join, h->aux_stream));
+            HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+        }
+        return FHE_OK;
     }
     const uint32_t LK = h->L * rk->K;
     const size_t S = (size_t)h->L * h->n * 32;
@@ -1328,60 +1422,47 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
     for (const void *i : ins) if (d_c0 == i || d_c1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must not alias inputs");
     if (d_c0 == d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must be distinct");
     if ((rc = check_inputs(h, {d_a0, d_a1, d_b0, d_b1}, batch))) return rc;
-    const int eb = h->width == FHE_WIDTH_32 ? 4 : 8;
-    const bool fused = rk->d_pkb && h->width != FHE_WIDTH_256 && !h->sub_top && !h->single_transforms && !h->no_fused_ct_relin &&
-                       fhe_dev::lds_compact_c2(eb, (int)h->log_n);
     const uint32_t polys = batch * h->L;
-    if (fused) {
-        const size_t cbytes = (size_t)polys * h->n * eb;         // one compact component
+    if (plan_fused_ct_relin(h, rk->d_pkb != nullptr)) {
+        const size_t eb = residue_bytes(h), cbytes = (size_t)polys * h->n * eb;         // one compact component
         if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
         char *c0c = (char *)h->d_ws2, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
-        fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), (int)h->log_n);
-        if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
         // The two kernels of the call sit on different roofs: the tensor product streams 4 S in at the HBM rate, the key switch (compact
         // operands) is bound by instruction issue.  The call is therefore a two-stage pipeline over chunks of whole ciphertexts: every
         // tensor product runs on the engine's stream, back to back; the key switch of chunk i runs on a second stream as soon as
         // tensor product i is done (event), i.e. beside tensor product i+1 on the same CUs.  The engine's stream joins the second one
         // at the end, so the call stays ordered on the engine's stream (and can be captured into a graph: fork / join through events).
-        // Every chunk has its own slice of the compact workspace.
+        // Every chunk has its own slice of the compact workspace (and of the two-launch form's, sized here for the whole batch).
+        const LdsPlan T = plan_ct_multiply(h, polys, false, true, true);
+        if ((rc = ensure_plan(h, T))) return rc;
+        const bool two = T.form == fhe_dev::LDS_TWO_LAUNCH;
         uint32_t chunks = h->overlap_chunks;
-        char *bws = nullptr;                                     // two-launch tensor product: the transformed b-side, sized here for the whole batch, sliced per chunk
-        {
-            fhe_dev::LdsArgs probe{fhe_dev::LDS_CT_MULTIPLY, c0c, c1c, c2c, d_a0, d_a1, d_b0, d_b1, h->d_limbs, h->L, polys, h->stream};
-            probe.compact_c2 = true;
-            if ((rc = ct_workspace(h, probe))) return rc;
-            bws = (char *)probe.ws;
-            if (bws && h->log_n >= 14) chunks = 1;               // 128+ KiB of LDS per workgroup: the two stages cannot share a CU anyway
-        }
+        if (two && h->log_n >= 14) chunks = 1;                  // 128+ KiB of LDS per workgroup: the two stages cannot share a CU anyway
         while (chunks > 1 && (polys / chunks < 1024 || batch < chunks)) chunks--;   // every chunk must fill the chip: >= 256 CUs x 4 workgroups (one per limb polynomial)
         if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
         const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * eb;   // bytes of one ciphertext component: containers / compact
         for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
             const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
             const size_t o = (size_t)b0 * S, oc = (size_t)b0 * Sc;
-            fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, c0c + oc, c1c + oc, c2c + oc, (const char *)d_a0 + o, (const char *)d_a1 + o, (const char *)d_b0 + o,
+            const LdsPlan Tc = chunks == 1 ? T : plan_ct_multiply(h, nb * h->L, false, true, false);
+            fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, Tc.form, c0c + oc, c1c + oc, c2c + oc, (const char *)d_a0 + o, (const char *)d_a1 + o, (const char *)d_b0 + o,
                                (const char *)d_b1 + o, h->d_limbs, h->L, nb * h->L, h->stream};
-            A.compact_c2 = true;
-            if (bws) A.ws = bws + 2 * oc;                        // two compact polynomials per limb polynomial of the chunk
-            A.small_batch = A.polys <= h->split_pairs_polys;     // few ciphertexts: the 16-per-thread tensor product (and, below, the split key switch)
-            if (chunks == 1 && !bws && A.polys <= h->coop_polys && h->width == FHE_WIDTH_32 && fhe_dev::lds_coop4_multiply(4, (int)h->log_n)) {
-                if ((rc = ensure_ws3(h, 7 * (size_t)A.polys * h->n * 4))) return rc;      // a handful: four workgroups per limb polynomial, three launches
-                A.coop_ws = h->d_ws3;
-            }
-            fn(A);
-            if ((rc = post_launch(h->stream, "tensor product (compact outputs)"))) return rc;
+            A.out_compact = true;
+            if (Tc.ws) A.ws = (char *)plan_ws(h, Tc) + (two ? 2 * oc : 0);   // two-launch: two compact polynomials per limb polynomial of the chunk
+            if ((rc = lds_launch(h, A, "tensor product (compact outputs)"))) return rc;
             hipStream_t ks = h->stream;
             if (chunks > 1) {
                 HIP_TRY(hipEventRecord(h->ev_chunk[c], h->stream));
                 HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_chunk[c], 0));
                 ks = h->aux_stream;
             }
-            fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, (char *)d_c0 + o, (char *)d_c1 + o, nullptr, c2c + oc, c0c + oc, c1c + oc, nullptr, h->d_limbs, h->L, nb * h->L, ks};
-            B.kb = rk->d_pkb; B.ka = rk->d_pka; B.K = rk->K; B.w = rk->decomp_bits; B.compact_c2 = true;
-            B.joint3 = use_joint3(h, false, true);
-            if (chunks == 1 && !bws && (rc = split_pairs_workspace(h, B))) return rc;     // (d_ws is free: no two-launch tensor product on the 4-byte field up to 2^14)
-            fn(B);
-            if ((rc = post_launch(ks, "key switch (compact operands)"))) return rc;
+            // (the few-ciphertext parts take d_ws: never beside the two-launch tensor product, which the 4-byte field up to 2^14 does not use anyway)
+            const LdsPlan Kc = plan_keyswitch(h, nb * h->L, rk->K, KS_FUSED, chunks == 1 && !two);
+            if ((rc = ensure_plan(h, Kc))) return rc;
+            fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, Kc.form, (char *)d_c0 + o, (char *)d_c1 + o, nullptr, c2c + oc, c0c + oc, c1c + oc, nullptr, h->d_limbs, h->L, nb * h->L, ks};
+            B.in_compact = true; B.ws = plan_ws(h, Kc);
+            B.kb = rk->d_pkb; B.ka = rk->d_pka; B.K = rk->K; B.w = rk->decomp_bits;
+            if ((rc = lds_launch(h, B, "key switch (compact operands)"))) return rc;
             b0 += nb;
         }
         if (chunks > 1) {
@@ -1672,20 +1753,14 @@ static int blind_rotate_step_general(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
     return fhe_ct_relinearize(h, rows_c1, d_acc0, d_acc1, d_tmp1, batch);                     // acc += sum D(d1) * rows_c1
 }
 // One step as ONE launch (word-sized classes with packed rows): (out0, out1) = (in0, in1) + ExtProd((X^a - 1) * in, RGSW).
-static int blind_rotate_step_fused(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1, void *out0, void *out1, const void *in0,
-                                   const void *in1, const uint32_t *d_shifts, uint32_t batch, bool in_compact = false, bool out_compact = false,
-                                   const void *rot0 = nullptr, const void *rot1 = nullptr, void *pair_ws = nullptr) {
-    fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), (int)h->log_n);
-    if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
-    fhe_dev::LdsArgs A{fhe_dev::LDS_EXTPROD, out0, out1, nullptr, in0, in1, rot0, rot1, h->d_limbs, h->L, batch * h->L, h->stream};   // b0, b1: pre-rotated digit sources (three-array kernel)
+// rot0, rot1: (X^a - 1) * (in0, in1), pre-rotated by the loop (compact), or nullptr
+static int blind_rotate_step_fused(fhe_rns_ntt_t *h, const LdsPlan &P, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1, void *out0, void *out1,
+                                   const void *in0, const void *in1, const uint32_t *d_shifts, uint32_t batch, bool in_compact, bool out_compact,
+                                   const void *rot0, const void *rot1) {
+    fhe_dev::LdsArgs A{fhe_dev::LDS_EXTPROD, P.form, out0, out1, nullptr, in0, in1, rot0, rot1, h->d_limbs, h->L, batch * h->L, h->stream};
     A.kb = r0->d_pkb; A.ka = r0->d_pka; A.kb1 = r1->d_pkb; A.ka1 = r1->d_pka; A.K = r0->K; A.w = r0->decomp_bits; A.shifts = d_shifts;
-    A.in_compact = in_compact; A.out_compact = out_compact;
-    A.pair_ws = pair_ws;                 // few accumulators: partial accumulators of the one-workgroup-per-digit form
-    A.joint3 = use_joint3(h, true, false);
-    A.global_twiddles = h->global_twiddles;
-    A.single_transforms = h->single_transforms;
-    fn(A);
-    return post_launch(h->stream, "ntt_extprod_kernel");
+    A.in_compact = in_compact; A.out_compact = out_compact; A.ws = plan_ws(h, P);
+    return lds_launch(h, A, "ntt_extprod_kernel");
 }
 static int check_rows(const fhe_rns_ntt_t *h, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1) {
     if (!r0 || !r1) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: null RGSW rows");
@@ -1704,32 +1779,29 @@ extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const 
     }
     if ((rc = check_inputs(h, {d_acc0, d_acc1}, batch))) return rc;
     bool fused = h->width != FHE_WIDTH_256 && !h->no_fused_blind_rotate;
+    uint32_t kmax = 0;
     for (uint32_t s = 0; s < steps; s++) {
         if ((rc = check_rows(h, rows_c0[s], rows_c1[s]))) return rc;
         fused = fused && rows_c0[s]->d_pkb && rows_c1[s]->d_pkb;
+        kmax = rows_c0[s]->K > kmax ? rows_c0[s]->K : kmax;
     }
     if (!fused) {
         for (uint32_t s = 0; s < steps; s++)
             if ((rc = blind_rotate_step_general(h, rows_c0[s], rows_c1[s], d_acc0, d_acc1, d_shifts + (size_t)s * batch, d_tmp0, d_tmp1, batch))) return rc;
         return FHE_OK;
     }
-    // Few accumulators (4-byte residues, N <= 2^13; what a bootstrapping of one or a few ciphertexts looks like): with one workgroup per (accumulator, limb)
-    // a step lasts as long as that workgroup's 2 L K / 2 paired transforms back to back (103 us per external product at N = 8192, L = 4, w = 16, batch 1).
-    // Here a step is three launches: the monomial factor (X^a - 1) once per step (a streaming pass), one workgroup per (accumulator, limb, component, DIGIT) on the
-    // 16-per-thread forward transform with that digit's two key products, and one workgroup per (accumulator, limb, output component) that sums the 2 L K partials,
-    // runs one inverse transform and adds the accumulator (ntt_keyswitch16_{part,comb}_kernel).  The pair stays compact between the steps.
-    // (N = 2^14: the same three launches on the paired 32-per-thread transforms, one workgroup per digit PAIR of a component)
-    if (steps >= 1 && h->width == FHE_WIDTH_32 && !h->single_transforms && !h->no_compact_blind_rotate && !h->no_prerotation && fhe_dev::lds_paired_keyswitch(4, (int)h->log_n) &&
-        h->split_pairs_polys && batch * h->L <= h->split_pairs_polys) {
-        const size_t cbytes = (size_t)batch * h->L * h->n * 4, count = (size_t)batch * h->L * h->n;
-        if ((rc = ensure_ws2(h, 6 * cbytes))) return rc;
+    if (!steps) return FHE_OK;
+    const LdsPlan P = plan_extprod(h, batch * h->L, kmax);
+    if (P.compact) {
+        // The accumulator pair is compacted first (one streaming pass), every step reads compact input from a workspace ping-pong (4 compact
+        // polynomials; 2 more hold the pre-rotated pair of the current step), all but the last write compact output, the last one writes the
+        // caller's containers.  The caller's scratch pair is not touched.
+        const size_t cbytes = (size_t)batch * h->L * h->n * residue_bytes(h), count = (size_t)batch * h->L * h->n;
+        if ((rc = ensure_ws2(h, (P.form == fhe_dev::LDS_PAIRED ? 4 : 6) * cbytes))) return rc;
         char *w0 = (char *)h->d_ws2;
         char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
         char *rot0 = w0 + 4 * cbytes, *rot1 = w0 + 5 * cbytes;       // (X^a - 1) * acc of the current step
-        uint32_t kmax = 0;
-        for (uint32_t s = 0; s < steps; s++) kmax = rows_c0[s]->K > kmax ? rows_c0[s]->K : kmax;
-        const size_t parts = fhe_dev::lds_small_multiply(4, (int)h->log_n) ? 2 * (size_t)h->L * kmax : 2 * (((size_t)h->L * kmax + 1) / 2);
-        if ((rc = ensure_ws(h, 2 * count * parts * 4))) return rc;      // two partial accumulators per (limb polynomial, component, digit or digit pair)
+        if ((rc = ensure_plan(h, P))) return rc;
         if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;
         if ((rc = compact_poly(h, pp[1][1], d_acc1, count))) return rc;
         for (uint32_t s = 0; s < steps; s++) {
@@ -1737,58 +1809,16 @@ extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const 
             const void *i0 = pp[(s + 1) & 1][0], *i1 = pp[(s + 1) & 1][1];
             void *o0 = last ? d_acc0 : pp[s & 1][0], *o1 = last ? d_acc1 : pp[s & 1][1];
             const uint32_t *sh = d_shifts + (size_t)s * batch;
-            if ((rc = monomial_compact(h, rot0, i0, sh, count)) || (rc = monomial_compact(h, rot1, i1, sh, count))) return rc;
-            if ((rc = blind_rotate_step_fused(h, rows_c0[s], rows_c1[s], o0, o1, i0, i1, sh, batch, true, !last, rot0, rot1, h->d_ws))) return rc;
-        }
-        return FHE_OK;
-    }
-    // Paired kernel (4-byte residues up to N = 2^14): the accumulator pair lives in COMPACT form for the whole call (workspace ping-pong, 4
-    // bytes per coefficient): the L limb workgroups of an accumulator each read all of it, which in container form is 3x the algorithmic
-    // traffic (profiles/r02_blindrotate_*) and made the first step of a loop 40 % slower than the others (1114 vs 785 us at N = 16384 x 6,
-    // profiles/r03_blindrotate_n16384_summary.txt).  Since round 3 the pair is compacted first (one streaming pass), every step reads compact
-    // input, the last one writes the caller's containers.  The caller's scratch pair is not touched.
-    if (steps >= 1 && h->width == FHE_WIDTH_32 && !h->single_transforms && !h->no_compact_blind_rotate && fhe_dev::lds_paired_extprod(4, (int)h->log_n)) {
-        const size_t cbytes = (size_t)batch * h->L * h->n * 4, count = (size_t)batch * h->L * h->n;
-        if ((rc = ensure_ws2(h, 4 * cbytes))) return rc;
-        char *w0 = (char *)h->d_ws2;
-        char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
-        if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;
-        if ((rc = compact_poly(h, pp[1][1], d_acc1, count))) return rc;
-        for (uint32_t s = 0; s < steps; s++) {
-            const bool last = s + 1 == steps;
-            const void *i0 = pp[(s + 1) & 1][0], *i1 = pp[(s + 1) & 1][1];
-            void *o0 = last ? d_acc0 : pp[s & 1][0], *o1 = last ? d_acc1 : pp[s & 1][1];
-            if ((rc = blind_rotate_step_fused(h, rows_c0[s], rows_c1[s], o0, o1, i0, i1, d_shifts + (size_t)s * batch, batch, true, !last))) return rc;
-        }
-        return FHE_OK;
-    }
-    // Three-array kernel (8-byte residues; 4-byte residues at N = 2^15): every limb workgroup re-reads each limb of the accumulator pair once
-    // per DIGIT (rotated), L * K * 2 reads per workgroup -- as containers that was several times the algorithmic traffic.  The pair is
-    // compacted once (compact_kernel), every step reads compact input, all but the last write compact output (workspace ping-pong).
-    if (steps >= 1 && use_joint3(h, true, false) && !h->no_compact_blind_rotate) {
-        const size_t eb = residue_bytes(h), cbytes = (size_t)batch * h->L * h->n * eb, count = (size_t)batch * h->L * h->n;
-        if ((rc = ensure_ws2(h, 6 * cbytes))) return rc;
-        char *w0 = (char *)h->d_ws2;
-        char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
-        char *rot0 = w0 + 4 * cbytes, *rot1 = w0 + 5 * cbytes;       // (X^a - 1) * acc of the current step
-        if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;
-        if ((rc = compact_poly(h, pp[1][1], d_acc1, count))) return rc;
-        for (uint32_t s = 0; s < steps; s++) {
-            const bool last = s + 1 == steps;
-            const void *i0 = pp[(s + 1) & 1][0], *i1 = pp[(s + 1) & 1][1];
-            void *o0 = last ? d_acc0 : pp[s & 1][0], *o1 = last ? d_acc1 : pp[s & 1][1];
-            const uint32_t *sh = d_shifts + (size_t)s * batch;
-            // the monomial factor once per step (a streaming pass over two compact polynomials) instead of once per digit inside the kernel
-            const bool prerot = !h->no_prerotation;
-            if (prerot && ((rc = monomial_compact(h, rot0, i0, sh, count)) || (rc = monomial_compact(h, rot1, i1, sh, count)))) return rc;
-            if ((rc = blind_rotate_step_fused(h, rows_c0[s], rows_c1[s], o0, o1, i0, i1, sh, batch, true, !last, prerot ? rot0 : nullptr, prerot ? rot1 : nullptr))) return rc;
+            if (P.prerot && ((rc = monomial_compact(h, rot0, i0, sh, count)) || (rc = monomial_compact(h, rot1, i1, sh, count)))) return rc;
+            if ((rc = blind_rotate_step_fused(h, P, rows_c0[s], rows_c1[s], o0, o1, i0, i1, sh, batch, true, !last, P.prerot ? rot0 : nullptr,
+                                              P.prerot ? rot1 : nullptr))) return rc;
         }
         return FHE_OK;
     }
     // ping-pong between (acc0, acc1) and (tmp0, tmp1): one launch per step, 4*S bytes of HBM traffic per accumulator and step
     void *cur0 = d_acc0, *cur1 = d_acc1, *nxt0 = d_tmp0, *nxt1 = d_tmp1;
     for (uint32_t s = 0; s < steps; s++) {
-        if ((rc = blind_rotate_step_fused(h, rows_c0[s], rows_c1[s], nxt0, nxt1, cur0, cur1, d_shifts + (size_t)s * batch, batch))) return rc;
+        if ((rc = blind_rotate_step_fused(h, P, rows_c0[s], rows_c1[s], nxt0, nxt1, cur0, cur1, d_shifts + (size_t)s * batch, batch, false, false, nullptr, nullptr))) return rc;
         std::swap(cur0, nxt0); std::swap(cur1, nxt1);
     }
     if (cur0 != d_acc0) {   // odd number of steps: the result sits in the scratch pair

@@ -3,7 +3,7 @@
 
 namespace fhe_dev {
 
-#define DECL(F, N) void lds_launch_##F##_##N(const LdsArgs &);
+#define DECL(F, N) bool lds_launch_##F##_##N(const LdsArgs &);
 DECL(F32, 11) DECL(F32, 12) DECL(F32, 13) DECL(F32, 14) DECL(F32, 15)
 DECL(F64, 11) DECL(F64, 12) DECL(F64, 13) DECL(F64, 14)
 DECL(F64X, 11) DECL(F64X, 12) DECL(F64X, 13) DECL(F64X, 14)

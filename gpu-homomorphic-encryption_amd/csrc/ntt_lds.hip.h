@@ -107,28 +107,20 @@ __device__ __forceinline__ void lds_get(const E *lds, uint32_t tid, E (&x)[32]) 
 // Two arrays through ONE exchange image of element PAIRS (x0[r], x1[r]) side by side: the paired transforms of the 4-byte residues then
 // exchange with ds_write_b64 / ds_read_b64 -- half the LDS instructions of two 4-byte images (a 4-byte LDS read needs ~4 waves per
 // SIMD to reach its rate, these kernels run two: MI355X guide, LDS table), same padding rule in units of pairs, same footprint.
-// FHE_PAIR_EXCHANGE_B32 (compile-time A/B switch) keeps the round-2 form: two 4-byte images at lds and lds + LDS_ELEMS.
+// (The round-2 form, two 4-byte images at lds and lds + LDS_ELEMS, measured the same: scratch/experiments/README.md.)
 template <class Pat, class E>
 __device__ __forceinline__ void lds_put2(E *lds, uint32_t tid, const E (&x0)[32], const E (&x1)[32]) {
-#ifdef FHE_PAIR_EXCHANGE_B32
-    lds_put<Pat>(lds, tid, x0); lds_put<Pat>(lds + NttCfg<Pat::LOGN_>::LDS_ELEMS, tid, x1);
-#else
     typedef E E2 __attribute__((ext_vector_type(2)));
     E2 *p = reinterpret_cast<E2 *>(lds) + Pat::pbase(tid);
 #pragma unroll
     for (int r = 0; r < 32; r++) { E2 v = {x0[r], x1[r]}; p[Pat::poff(r)] = v; }
-#endif
 }
 template <class Pat, class E>
 __device__ __forceinline__ void lds_get2(const E *lds, uint32_t tid, E (&x0)[32], E (&x1)[32]) {
-#ifdef FHE_PAIR_EXCHANGE_B32
-    lds_get<Pat>(lds, tid, x0); lds_get<Pat>(lds + NttCfg<Pat::LOGN_>::LDS_ELEMS, tid, x1);
-#else
     typedef E E2 __attribute__((ext_vector_type(2)));
     const E2 *p = reinterpret_cast<const E2 *>(lds) + Pat::pbase(tid);
 #pragma unroll
     for (int r = 0; r < 32; r++) { const E2 v = p[Pat::poff(r)]; x0[r] = v.x; x1[r] = v.y; }
-#endif
 }
 
 // ---- twiddle tables ----------------------------------------------------------------------------------------
@@ -172,9 +164,6 @@ __device__ __forceinline__ void stage_twiddles(typename F::TW *twl, const typena
 // a 64-bit VGPR address per load and goes through the aperture check.  They are global memory: say so (global_load, SGPR base).
 template <class TW>
 __device__ __forceinline__ TW load_global(const TW *p) {
-#ifdef FHE_FLAT_TWIDDLES      // compile-time A/B switch: generic-pointer loads as in rounds 1-2
-    return *p;
-#endif
     if constexpr (sizeof(TW) == 16) {
         typedef uint64_t V __attribute__((ext_vector_type(2)));
         const V v = *(const __attribute__((address_space(1))) V *)p;
@@ -475,18 +464,6 @@ template <class F, int LOGN, bool PRESYNC = false>
 __device__ __forceinline__ void fwd_core2(typename F::E (&x0)[32], typename F::E (&x1)[32], typename F::E *lds, uint32_t tid,
                                           const Limb<F> &P) {
     using C = NttCfg<LOGN>;
-#ifdef FHE_NO_TWIDDLE_PRELOAD     // compile-time A/B switch: the round-2 form (twiddles loaded where they are used)
-    fwd_stages2<F, LOGN, PatA<LOGN>, 4, 0>(x0, x1, tid, P.tw, P);
-    if constexpr (PRESYNC) __syncthreads();
-    lds_put2<PatA<LOGN>>(lds, tid, x0, x1);
-    __syncthreads();
-    lds_get2<PatM<LOGN>>(lds, tid, x0, x1);
-    fwd_stages2<F, LOGN, PatM<LOGN>, 4, 0>(x0, x1, tid, P.tw, P);
-    lds_put2<PatM<LOGN>>(lds, tid, x0, x1);       // same slots this thread just read: no barrier needed before
-    __syncthreads();
-    lds_get2<PatZ<LOGN>>(lds, tid, x0, x1);
-    fwd_stages2<F, LOGN, PatZ<LOGN>, C::REM - 1, 0>(x0, x1, tid, P.tw, P);
-#else
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatM<LOGN>, 4, 0>(w, tid, P.tw);          // in flight under the first register group and the first exchange
     fwd_stages2<F, LOGN, PatA<LOGN>, 4, 0>(x0, x1, tid, P.tw, P);
@@ -500,7 +477,6 @@ __device__ __forceinline__ void fwd_core2(typename F::E (&x0)[32], typename F::E
     __syncthreads();
     lds_get2<PatZ<LOGN>>(lds, tid, x0, x1);
     fwd_stages2_pre<F, C::REM - 1, 0>(x0, x1, w, P);
-#endif
 }
 
 // NTT values in pattern Z, in [0, 2q)  ->  coefficients in pattern A, in [0, 2q), scaled by the (ninv..) constants
@@ -553,15 +529,6 @@ template <class F, int LOGN, bool PRESYNC = false>
 __device__ __forceinline__ void inv_core2(typename F::E (&x0)[32], typename F::E (&x1)[32], typename F::E *lds, uint32_t tid,
                                           const Limb<F> &P, typename F::E ninv, typename F::E ninv_s, typename F::E ninvw, typename F::E ninvw_s) {
     using C = NttCfg<LOGN>;
-#ifdef FHE_NO_TWIDDLE_PRELOAD
-    inv_stages2<F, LOGN, PatZ<LOGN>, 0, 4>(x0, x1, tid, P.itw, P);
-    F::regroup(x0, P.q, P.qinv); F::regroup(x1, P.q, P.qinv);
-    if constexpr (PRESYNC) __syncthreads();
-    lds_put2<PatZ<LOGN>>(lds, tid, x0, x1);
-    __syncthreads();
-    lds_get2<PatY<LOGN>>(lds, tid, x0, x1);
-    inv_stages2<F, LOGN, PatY<LOGN>, 0, 4>(x0, x1, tid, P.itw, P);
-#else
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatZ<LOGN>, 4, 0>(w, tid, P.itw);          // needed at once (issued together: one latency, not five)
     inv_stages2_pre<F, 0, 4>(x0, x1, w, P);
@@ -572,7 +539,6 @@ __device__ __forceinline__ void inv_core2(typename F::E (&x0)[32], typename F::E
     __syncthreads();
     lds_get2<PatY<LOGN>>(lds, tid, x0, x1);
     inv_stages2_pre<F, 0, 4>(x0, x1, w, P);
-#endif
     F::regroup(x0, P.q, P.qinv); F::regroup(x1, P.q, P.qinv);
     lds_put2<PatY<LOGN>>(lds, tid, x0, x1);
     __syncthreads();

@@ -11,7 +11,7 @@
 //   * EVERY twiddle the three transforms need (15 per non-uniform register group) is loaded into registers at the top of the kernel
 //     together with both operands: one memory round trip in all (the workgroup has 256 VGPRs per lane to itself).
 // Same tables, same HBM access shapes, same lazy butterflies and bit-identical results as ntt_multiply_kernel; the host uses it while
-// batch x limbs stays below the number of CUs (lds_small_batch in lds_launch.h).  16-per-thread forms of the throughput kernels were
+// batch x limbs stays below the number of CUs (LDS_SMALL16: plan_multiply in fhe_hip.hip).  16-per-thread forms of the throughput kernels were
 // measured in round 1 (scratch/experiments/ntt_lds16.hip.h: the extra exchange costs what the occupancy buys) -- this is the latency case.
 #pragma once
 #include "ntt_lds.hip.h"
@@ -75,7 +75,7 @@ __device__ __forceinline__ void preload16(typename F::TW (&w)[15], uint32_t tid,
 }
 // the wave-uniform twiddles of the pattern-A group (stage k, twiddle j = r >> (k+1), same slots): scalar loads, but issued at the top of the
 // kernel like the others -- left where they are used, the first transform waited for four dependent scalar-cache misses (~9 K cycles,
-// scripts/small_batch_timeline.py)
+// round-3 s_memtime timeline)
 template <class F, int LOGN, int KHI, int KLO>
 __device__ __forceinline__ void preload16_uniform(typename F::TW (&w)[15], const typename F::TW *__restrict__ tw, uint32_t pre = 1) {
     using Pat = P16A<LOGN>;
@@ -256,13 +256,6 @@ __device__ __forceinline__ void store16(char *__restrict__ poly, const typename 
     }
 }
 
-#ifdef FHE_STAMPS      // diagnostic build only (scripts/small_batch_timeline.py): s_memtime at the phase boundaries of workgroup 0, wave 0
-__device__ unsigned long long g_stamps16[16];
-#define STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps16[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 // r = INTT(NTT(a) .* NTT(b)) for few polynomials: grid.x = batch * L, workgroup p handles polynomial p (limb p % L).
 // res may alias a and / or b (both operands are in registers before the first store); bcast != 0: b holds ONE RNS polynomial.
 template <class F, int LOGN>
@@ -275,43 +268,30 @@ ntt16_multiply_kernel(char *res, const char *a, const char *b, const Limb<F> *__
     const Limb<F> P = limbs[limb];
     const size_t off = (size_t)p * (C::N * 32);
     E x[16], y[16];
-    STAMP(0);
     // Twiddles first: the operand loads (512 KiB of container lines through ONE CU's 64 B/clk vector-memory path: ~9 K cycles, during
-    // which the issuing waves are blocked on the full address FIFO) would otherwise delay them by the same ~9 K cycles (timeline of
-    // scripts/small_batch_timeline.py: first forward transform 18.5 K cycles against 9.1 K for the second)
+    // which the issuing waves are blocked on the full address FIFO) would otherwise delay them by the same ~9 K cycles (round-3
+    // s_memtime timeline, DESIGN.md: first forward transform 18.5 K cycles against 9.1 K for the second)
     Twiddles16<F, LOGN> W;
     W.template load<false>(tid, P);
     load16<F, LOGN>(a + off, tid, x);
     load16<F, LOGN>(b + (size_t)(bcast ? limb : p) * (C::N * 32), tid, y);
-    STAMP(1);
-#ifdef FHE_STAMPS
-    { E t = 0;
-#pragma unroll
-      for (int r = 0; r < 16; r++) t ^= x[r] ^ y[r];
-      asm volatile("" :: "v"(t) : "memory"); }          // force the operands to have arrived
-    STAMP(2);
-#endif
     fwd_core16<F, LOGN>(x, lds, tid, P, W);
-    STAMP(3);
 #pragma unroll
     for (int r = 0; r < 16; r++) x[r] = F::canon_fwd(x[r], P.q, P.q2, P.qinv);
     __syncthreads();                                  // all pattern-Z reads of a are done before b's first exchange
     fwd_core16<F, LOGN>(y, lds, tid, P, W);
-    STAMP(4);
 #pragma unroll
     for (int r = 0; r < 16; r++) x[r] = F::pw_mul(x[r], y[r], P.q, P.qinv);
     inv_core16<F, LOGN>(x, lds, tid, P, W, P.ninv_r, P.ninv_r_s, P.ninvw_r, P.ninvw_r_s);
 #pragma unroll
     for (int r = 0; r < 16; r++) x[r] = F::canon_inv(x[r], P.q);
-    STAMP(5);
     put16<P16A<LOGN>>(lds, tid, x);                   // the slots this thread read last
     __syncthreads();
     store16<F, LOGN>(res + off, lds, tid);
-    STAMP(6);
 }
 
 // ---- ONE polynomial over FOUR workgroups: the fused product for the smallest batches -----------------------------------------------------
-// The timeline of ntt16_multiply_kernel (scripts/small_batch_timeline.py) shows what bounds a lone workgroup: one CU needs ~19 K cycles to ingest
+// The timeline of ntt16_multiply_kernel (round 3) shows what bounds a lone workgroup: one CU needs ~19 K cycles to ingest
 // the 512 KiB of container lines of an operand pair and ~4.5 K to emit the result -- 10 of its 22 us are the container format moving through a
 // single CU.  Here every (polynomial, limb) is shared by Q = 4 workgroups (4 CUs) in three phases, each its own launch (the stream order is the
 // barrier between them; what crosses is a compact polynomial in a library workspace):
@@ -331,12 +311,9 @@ struct Coop4 {
     using S = Cfg16<LOGS>;
     static constexpr int T = S::T;                        // threads per workgroup (128 / 256)
     static constexpr int NS = 1 << LOGS;                  // coefficients per block = columns of the top stages
-#ifndef FHE_COOP_COLUMNS_PER_THREAD
-#define FHE_COOP_COLUMNS_PER_THREAD 1
-#endif
     // phases 1 and 3 work on COLUMNS (coefficients c, c + N/4, c + N/2, c + 3N/4) and can be cut anywhere: one column per thread = 16 workgroups per limb
-    // polynomial, so that a CU ingests 32 KiB of operand containers instead of 128 KiB (-DFHE_COOP_COLUMNS_PER_THREAD=4: the first form, four workgroups)
-    static constexpr int CPT = FHE_COOP_COLUMNS_PER_THREAD;
+    // polynomial, so that a CU ingests 32 KiB of operand containers instead of 128 KiB (four columns per thread, four workgroups, was the first form)
+    static constexpr int CPT = 1;
     static constexpr int CWG = NS / (T * CPT);            // column workgroups per limb polynomial (16 or 4)
     static_assert(CWG * T * CPT == NS, "columns per thread must divide the columns of a workgroup");
 };
@@ -376,8 +353,7 @@ ntt_multiply4_top_kernel(const char *a, const char *b, typename F::E *ws, const 
 // Phase 2 with the two forward transforms SIDE BY SIDE: the workgroup is two groups of T threads (group 0: the a block, group 1: the b block, each with
 // its own LDS image); NTT(b) crosses to group 0 through group 1's image in register order, group 0 multiplies and runs the inverse.  The critical path is
 // two transforms instead of three.  Group 1 walks through the inverse's barriers on its stale registers (its waves sit on other SIMDs) and stores nothing.
-// Same arithmetic per coefficient as the one-group form (-DFHE_COOP_ONE_GROUP): a-side canonical, b-side lazy, pw_mul.
-#ifndef FHE_COOP_ONE_GROUP
+// Same arithmetic per coefficient as the earlier one-group form: a-side canonical, b-side lazy, pw_mul.
 template <class F, int LOGN>
 __global__ void __launch_bounds__(2 << (LOGN - 6))
 ntt_multiply4_block_kernel(typename F::E *ws, const Limb<F> *__restrict__ limbs, uint32_t L) {
@@ -408,34 +384,6 @@ ntt_multiply4_block_kernel(typename F::E *ws, const Limb<F> *__restrict__ limbs,
         for (int r = 0; r < 16; r++) wr[k * NS + tid + r * T] = F::canon_inv(x[r], P.q);
     }
 }
-#else
-template <class F, int LOGN>
-__global__ void __launch_bounds__(1 << (LOGN - 6))
-ntt_multiply4_block_kernel(typename F::E *ws, const Limb<F> *__restrict__ limbs, uint32_t L) {
-    using K = Coop4<F, LOGN>;
-    using E = typename F::E;
-    constexpr int LOGS = K::LOGS, NS = K::NS, T = K::T, N = 1 << LOGN;
-    __shared__ E lds[NS];
-    const uint32_t tid = threadIdx.x, p = blockIdx.x >> 2, k = blockIdx.x & 3;
-    const Limb<F> P = limbs[p % L];
-    E *wa = ws + (size_t)p * (3 * N), *wb = wa + N, *wr = wb + N;
-    Twiddles16<F, LOGS> W;
-    W.template load<true>(tid, P, 4 + k);
-    E x[16], y[16];
-#pragma unroll
-    for (int r = 0; r < 16; r++) { x[r] = wa[k * NS + tid + r * T]; y[r] = wb[k * NS + tid + r * T]; }
-    fwd_core16<F, LOGS>(x, lds, tid, P, W);
-#pragma unroll
-    for (int r = 0; r < 16; r++) x[r] = F::canon_fwd(x[r], P.q, P.q2, P.qinv);
-    __syncthreads();
-    fwd_core16<F, LOGS>(y, lds, tid, P, W);
-#pragma unroll
-    for (int r = 0; r < 16; r++) x[r] = F::pw_mul(x[r], y[r], P.q, P.qinv);               // carries 2^-W until the last stage (ninv_r constants)
-    inv_core16<F, LOGS, true>(x, lds, tid, P, W, P.ninv, P.ninv_s, P.ninvw, P.ninvw_s);
-#pragma unroll
-    for (int r = 0; r < 16; r++) wr[k * NS + tid + r * T] = F::canon_inv(x[r], P.q);
-}
-#endif
 template <class F, int LOGN>
 __global__ void __launch_bounds__(1 << (LOGN - 6))
 ntt_multiply4_last_kernel(char *res, const typename F::E *ws, const Limb<F> *__restrict__ limbs, uint32_t L) {

@@ -158,9 +158,10 @@ int fhe_rns_base_create(fhe_rns_ntt_t **out, const uint64_t (*primes)[4], uint32
 int fhe_rns_ntt_destroy(fhe_rns_ntt_t *h);                                    /* src/ntt.cu:147-156 */
 int fhe_rns_ntt_set_stream(fhe_rns_ntt_t *h, void *stream);
 int fhe_rns_ntt_width_class(const fhe_rns_ntt_t *h);
-/* Pre-sizes the library-owned workspaces for calls of up to `batch` units (fhe_ct_multiply_relin, fhe_blind_rotate, the general
- * paths), so that later calls never allocate: required before capturing such calls into a hipGraph, optional otherwise (the
- * workspaces grow on first use).  No counterpart in the reference, which mallocs and frees inside every multiply (src/ntt.cu:51-74).
+/* Pre-sizes the library-owned workspaces for calls of up to `batch` units of every entry point that uses one -- fhe_rns_ntt_forward /
+ * inverse (two-pass sizes), fhe_rns_ntt_multiply, fhe_rns_ntt_multiply_bcast, fhe_ct_multiply, fhe_ct_relinearize, fhe_ct_multiply_relin,
+ * fhe_blind_rotate and fhe_blind_rotate_step -- so that later calls never allocate: required before capturing such calls into a hipGraph,
+ * optional otherwise (the workspaces grow on first use).  No counterpart in the reference, which mallocs and frees inside every multiply (src/ntt.cu:51-74).
  * The key-switch workspaces depend on the digit count: import the key sets BEFORE reserving.  fhe_rns_ntt_workspace_bytes reports what
  * the engine holds at the moment (device bytes in its three workspaces; tables and key sets are not counted). */
 int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch);
