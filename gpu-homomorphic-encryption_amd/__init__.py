@@ -11,7 +11,7 @@ The directory name carries a hyphen, so import it by string:
 """
 from .build import build_library, library_path  # noqa: F401
 from .capi import (  # noqa: F401
-    FheError, NttEngine, RnsNttEngine, DeviceBuffer, Timer, lib, device_count, find_ntt_primes, find_psi,
+    FheError, NttEngine, RnsNttEngine, DeviceBuffer, Timer, lib, device_count, find_ntt_primes, find_psi, galois_element,
     montgomery_inverse, montgomery_params, u256_add_mod, u256_sub_mod, u256_mont_mul, u256_mont_mul_scalar,
     ref_forward_kernel_literal, ref_inverse_kernel_literal, ref_stockham_stage_literal, bit_reverse, sample_uniform_lcg, sample_gaussian_placeholder, gaussian_cdt, poly_mod_switch, negacyclic_reduce,
     WIDTH_32, WIDTH_52, WIDTH_64, WIDTH_256, WIDTH_64X,
@@ -19,7 +19,7 @@ from .capi import (  # noqa: F401
 
 __all__ = [
     "build_library", "library_path", "FheError", "NttEngine", "RnsNttEngine", "DeviceBuffer", "Timer", "lib",
-    "device_count", "find_ntt_primes", "find_psi", "montgomery_inverse", "montgomery_params", "u256_add_mod",
+    "device_count", "find_ntt_primes", "find_psi", "galois_element", "montgomery_inverse", "montgomery_params", "u256_add_mod",
     "u256_sub_mod", "u256_mont_mul", "u256_mont_mul_scalar", "ref_forward_kernel_literal", "ref_inverse_kernel_literal", "ref_stockham_stage_literal", "bit_reverse", "sample_uniform_lcg", "sample_gaussian_placeholder",
     "gaussian_cdt", "poly_mod_switch", "negacyclic_reduce", "WIDTH_32", "WIDTH_52", "WIDTH_64", "WIDTH_256", "WIDTH_64X",
 ]

@@ -103,6 +103,9 @@ def lib():
         "fhe_relin_keys_destroy": ([vp], ci),
         "fhe_ct_relinearize": ([vp, vp, vp, vp, vp, u32], ci),
         "fhe_ct_multiply_relin": ([vp, vp, vp, vp, vp, vp, vp, vp, u32], ci),
+        "fhe_galois_element": ([u32, ctypes.c_int32, P(u32)], ci),
+        "fhe_rns_automorphism": ([vp, vp, vp, u32, u32], ci),
+        "fhe_ct_apply_galois": ([vp, vp, u32, vp, vp, vp, vp, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -148,6 +151,11 @@ def find_ntt_primes(bits, n, count):
 
 def find_psi(n, q):
     out = U64x4(); _check(lib().fhe_find_psi(n, _q4(q), out)); return _int(out)
+
+
+def galois_element(n, steps):
+    """3^(steps mod n/2) mod 2n: the Galois element of a row rotation by `steps` slots (host only)."""
+    e = ctypes.c_uint32(0); _check(lib().fhe_galois_element(n, steps, ctypes.byref(e))); return e.value
 
 
 def device_count():
@@ -418,6 +426,15 @@ class RnsNttEngine:
     def ct_multiply_relin(self, rk, d_c0, d_c1, d_a0, d_a1, d_b0, d_b1, batch=1):
         """FHEContext::multiply: tensor product + relinearisation in one call (two components out)."""
         _check(lib().fhe_ct_multiply_relin(self.h, rk.h, _ptr(d_c0), _ptr(d_c1), _ptr(d_a0), _ptr(d_a1), _ptr(d_b0), _ptr(d_b1), batch))
+
+    def automorphism(self, d_out, d_in, galois_elt, batch=1):
+        """d_out = sigma_g(d_in): a(x) -> a(x^g) per limb polynomial, g odd and below 2n (out of place)."""
+        _check(lib().fhe_rns_automorphism(self.h, _ptr(d_out), _ptr(d_in), galois_elt, batch))
+
+    def apply_galois(self, gk, galois_elt, d_out0, d_out1, d_c0, d_c1, batch=1):
+        """(d_out0, d_out1) = sigma_g applied to the ciphertext (d_c0, d_c1) and key-switched back with the Galois keys gk of g
+        (imported with import_relin_keys: rows (b, a) with b = -a*s + e + g_jk * sigma_g(s))."""
+        _check(lib().fhe_ct_apply_galois(self.h, gk.h, galois_elt, _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), _ptr(d_c1), batch))
 
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))

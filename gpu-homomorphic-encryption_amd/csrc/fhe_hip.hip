@@ -20,6 +20,7 @@
 #include "sampling.hip.h"
 #include "lds_launch.h"
 #include "ntt_word.hip.h"
+#include "galois.hip.h"
 
 using fhe_host::U256;
 
@@ -260,7 +261,8 @@ struct fhe_rns_ntt {
     bool wide_lazy = false;             // FHE_WIDTH_256: every modulus below 2^(64 wide_nl - 6): the lazy tile kernels (FHE_HIP_NO_WIDE_LAZY=1: the canonical ones; cross-check / A-B)
     bool wide_tiles = true;             // FHE_HIP_NO_WIDE_TILES=1: every stage as a global-memory pass (cross-check / A-B)
     bool no_square = false, single_transforms = false, global_twiddles = false, check_inputs = false, no_fused_keyswitch = false,
-         no_word_conversions = false, no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, split_keyswitch = false, no_c2_compaction = false, no_prerotation = false;
+         no_word_conversions = false, no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, split_keyswitch = false, no_c2_compaction = false, no_prerotation = false,
+         no_fused_galois = false;
     int ct_form_force = 0;                         // FHE_HIP_CT_FORM: 0 = by field and size, 1 = one-launch tensor product where it exists, 2 = two-launch where it exists   // environment switches, read once at creation
     std::vector<void *> d_tables;
     void *d_ws = nullptr; size_t ws_bytes = 0;
@@ -548,6 +550,7 @@ static int create_impl(fhe_rns_ntt **out, uint32_t n, const uint64_t (*moduli)[4
     h->no_fused_ct_relin = getenv("FHE_HIP_NO_FUSED_CT_RELIN") != nullptr;
     h->no_compact_blind_rotate = getenv("FHE_HIP_NO_COMPACT_BLIND_ROTATE") != nullptr;
     h->no_two_launch_ct = getenv("FHE_HIP_NO_TWO_LAUNCH_CT") != nullptr;
+    h->no_fused_galois = getenv("FHE_HIP_NO_FUSED_GALOIS") != nullptr;        // fhe_ct_apply_galois on the composed path everywhere (cross-check)
     h->split_keyswitch = getenv("FHE_HIP_SPLIT_KEYSWITCH") != nullptr;
     if (const char *m = getenv("FHE_HIP_SMALL_BATCH_POLYS")) { const long v = atol(m); h->small_batch_polys = v < 0 ? 0u : (uint32_t)v; }
     if (const char *m = getenv("FHE_HIP_COOP_POLYS")) { const long v = atol(m); h->coop_polys = v < 0 ? 0u : v > 64 ? 64u : (uint32_t)v; }
@@ -1071,7 +1074,7 @@ extern "C" int fhe_rns_ntt_set_stream(fhe_rns_ntt_t *h, void *stream) {
     return FHE_OK;
 }
 // Pre-sizes the library-owned workspaces for calls of up to `batch` units, so that no later call allocates (hipMalloc synchronises
-// and cannot be captured into a hipGraph): the compact / container workspace of fhe_ct_multiply_relin and fhe_blind_rotate, and the
+// and cannot be captured into a hipGraph): the compact / container workspace of fhe_ct_multiply_relin, fhe_ct_apply_galois and fhe_blind_rotate, and the
 // transform workspace of the general paths (full-width class, two-pass sizes).  Relinearisation on the general path sizes its digit
 // workspace by itself (bounded to 1 GiB, chunked).
 extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
@@ -1474,6 +1477,106 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
     if ((rc = ensure_ws2(h, (size_t)polys * h->n * 32))) return rc;
     if ((rc = do_ct_multiply(h, d_c0, d_c1, h->d_ws2, d_a0, d_a1, d_b0, d_b1, batch))) return rc;
     return fhe_ct_relinearize(h, rk, d_c0, d_c1, h->d_ws2, batch);
+}
+
+
+// ------------------------------------------------------------------------------------------------------
+// Galois automorphisms and slot rotations (FHEContext::rotate_rows / rotate_columns, include/fhe.cuh:112-116)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int fhe_galois_element(uint32_t n, int32_t steps, uint32_t *elt) {
+    if (!elt) return fail(FHE_ERR_INVALID_ARG, "galois_element: elt is null");
+    if (n < 8 || n > (1u << 30) || (n & (n - 1))) return fail(FHE_ERR_INVALID_ARG, "galois_element: n must be a power of two in [8, 2^30]");
+    const uint32_t half = n / 2, m = 2 * n;                          // 3 generates a cyclic subgroup of order n/2 of (Z/2n)^*
+    const uint32_t e = (uint32_t)(((int64_t)steps % half + half) % half);
+    uint64_t r = 1, b = 3;
+    for (uint32_t k = e; k; k >>= 1) { if (k & 1) r = r * b % m; b = b * b % m; }
+    *elt = (uint32_t)r;
+    return FHE_OK;
+}
+static int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what) {
+    if (!(g & 1) || g >= 2 * h->n)
+        return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the Galois element must be odd and below 2n");
+    return FHE_OK;
+}
+static uint32_t galois_inverse(const fhe_rns_ntt *h, uint32_t g) {    // g^-1 mod 2n (g odd): Newton iteration modulo 2^32, then reduced
+    uint32_t x = g;
+    for (int i = 0; i < 5; i++) x *= 2 - g * x;
+    return x & (2 * h->n - 1);
+}
+// sigma_g of one or two components (in1 == nullptr: one) into out0 / out1, zero_out (optional) cleared beside them; compact: E per coefficient out.
+// The staged form up to 32 KiB per limb polynomial (4-byte residues up to N = 8192, 8-byte ones up to 4096), the L2 gather above: the interleaved
+// A/B of scratch/galois_ab.hip had the staged form 13 % faster at 32 KiB and 8-14 % slower at 64 KiB (two workgroups per CU).
+template <class F>
+static int galois_word(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g_inv, size_t polys, bool compact) {
+    using V = typename F::V16; using E = typename F::E;
+    const uint32_t comps = in1 ? 2 : 1;
+    const size_t lds = (size_t)h->n * sizeof(E);
+    const bool staged = lds <= fhe_dev::GALOIS_STAGE_BYTES;
+    const dim3 block(fhe_dev::GALOIS_T), grid(staged ? (unsigned)std::min<size_t>(polys, 1u << 20) : ew_grid(polys * h->n), comps);
+    const fhe_dev::Limb<F> *limbs = (const fhe_dev::Limb<F> *)h->d_limbs;
+    if (compact) {
+        if (staged) hipLaunchKernelGGL((fhe_dev::galois_compact_kernel<F, true>), grid, block, lds, h->stream, (E *)out0, (E *)out1, (E *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+        else hipLaunchKernelGGL((fhe_dev::galois_compact_kernel<F, false>), grid, block, 0, h->stream, (E *)out0, (E *)out1, (E *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+        return post_launch(h->stream, "galois_compact_kernel");
+    }
+    if (staged) hipLaunchKernelGGL((fhe_dev::galois_kernel<F, true>), grid, block, lds, h->stream, (V *)out0, (V *)out1, (V *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+    else hipLaunchKernelGGL((fhe_dev::galois_kernel<F, false>), grid, block, 0, h->stream, (V *)out0, (V *)out1, (V *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+    return post_launch(h->stream, "galois_kernel");
+}
+static int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact) {
+    const uint32_t g_inv = galois_inverse(h, g);
+    switch (h->width) {
+        case FHE_WIDTH_32: return galois_word<fhe_dev::F32>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact);
+        case FHE_WIDTH_52: return galois_word<fhe_dev::F52>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact);
+        case FHE_WIDTH_64: return galois_word<fhe_dev::F64>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact);
+        case FHE_WIDTH_64X: return galois_word<fhe_dev::F64X>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact);
+        default: break;
+    }
+    if (compact) return fail(FHE_ERR_UNSUPPORTED, "compact polynomials exist on the word-sized classes only");
+    const size_t count = polys * h->n;
+    hipLaunchKernelGGL(fhe_dev::galois256_kernel, dim3(ew_grid(count), in1 ? 2 : 1), dim3(fhe_dev::GALOIS_T), 0, h->stream, (fhe_dev::u256 *)out0,
+                       (fhe_dev::u256 *)out1, (fhe_dev::u256 *)zero_out, (const fhe_dev::u256 *)in0, (const fhe_dev::u256 *)in1,
+                       (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, g_inv, count);
+    return post_launch(h->stream, "galois256_kernel");
+}
+extern "C" int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t galois_elt, uint32_t batch) {
+    int rc = check_call(h, batch, "automorphism"); if (rc) return rc;
+    if (!d_out || !d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: null argument");
+    if (d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: the permutation is out of place (out must differ from in)");
+    if ((rc = check_galois_element(h, galois_elt, "automorphism"))) return rc;
+    if ((rc = check_inputs(h, {d_in}, batch))) return rc;
+    return do_galois(h, d_out, nullptr, nullptr, d_in, nullptr, galois_elt, (size_t)batch * h->L, false);
+}
+// (c0, c1) -> (sigma(c0) + sum D(sigma(c1)) b, sum D(sigma(c1)) a): bit for bit fhe_ct_relinearize applied to (sigma(c0), 0, sigma(c1)).
+// Fused path (the LDS-resident word-sized sizes with packed keys, as plan_fused_ct_relin): the prologue writes sigma(c0), sigma(c1) and a zero
+// polynomial as compact polynomials into the three slices of d_ws2 that fhe_ct_multiply_relin uses, then ONE compact-operand key switch
+// (KS_FUSED) reads them -- HBM traffic 2 S in + 2 S out plus the compact round trip.  Elsewhere: sigma(c0) -> out0, zero -> out1 and
+// sigma(c1) -> d_ws2 as containers in one launch, then fhe_ct_relinearize.
+extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1, const void *d_c0,
+                                   const void *d_c1, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_apply_galois"); if (rc) return rc;
+    if (!gk || !d_out0 || !d_out1 || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: null argument");
+    if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: keys were imported for a different engine");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must be distinct");
+    for (const void *i : {d_c0, d_c1}) if (d_out0 == i || d_out1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must not alias inputs");
+    if ((rc = check_galois_element(h, galois_elt, "ct_apply_galois"))) return rc;
+    if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
+    const size_t polys = (size_t)batch * h->L;
+    if (plan_fused_ct_relin(h, gk->d_pkb != nullptr) && !h->no_fused_galois) {
+        const size_t cbytes = polys * h->n * residue_bytes(h);
+        if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
+        char *s0 = (char *)h->d_ws2, *s1 = s0 + cbytes, *zero = s1 + cbytes;      // sigma(c0): addend of c0'; sigma(c1): digit source; 0: addend of c1'
+        const LdsPlan P = plan_keyswitch(h, polys, gk->K, KS_FUSED, true);
+        if ((rc = ensure_plan(h, P))) return rc;
+        if ((rc = do_galois(h, s0, s1, zero, d_c0, d_c1, galois_elt, polys, true))) return rc;
+        fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, P.form, d_out0, d_out1, nullptr, s1, s0, zero, nullptr, h->d_limbs, h->L, (uint32_t)polys, h->stream};
+        B.in_compact = true; B.ws = plan_ws(h, P);
+        B.kb = gk->d_pkb; B.ka = gk->d_pka; B.K = gk->K; B.w = gk->decomp_bits;
+        return lds_launch(h, B, "key switch (rotation)");
+    }
+    if ((rc = ensure_ws2(h, polys * h->n * 32))) return rc;
+    if ((rc = do_galois(h, d_out0, h->d_ws2, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
+    return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->d_ws2, batch);
 }
 
 

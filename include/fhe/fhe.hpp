@@ -1,9 +1,10 @@
 // fhe/fhe.hpp -- mirror of the parts of fhe::FHEContext on the multiply path (include/fhe.cuh:15-148,
-// src/fhe.cu:7-52,187-235): SecurityParams, SchemeParams, Ciphertext, RelinKeys, FHEContext::add /
-// multiply / relinearize.  Key generation, encoding, encryption, rotations and bootstrapping are out
-// of scope of this engine.
+// src/fhe.cu:7-52,187-235): SecurityParams, SchemeParams, Ciphertext, RelinKeys, GaloisKeys, FHEContext::add /
+// multiply / relinearize / rotate_rows / rotate_columns, and the scheme plumbing around them (key generation, slot encoding,
+// encryption).  Bootstrapping is out of scope of this engine.
 #pragma once
 #include <algorithm>
+#include <stdexcept>
 #include <memory>
 #include <random>
 #include <vector>
@@ -32,6 +33,23 @@ struct RelinKeys {                                            // include/fhe.cuh
     RelinKeys(const RelinKeys &) = delete;
     RelinKeys &operator=(const RelinKeys &) = delete;
     ~RelinKeys() { fhe_relin_keys_destroy(imported); for (PublicKey *k : rlk_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } } }
+};
+
+struct GaloisKeys {                                           // include/fhe.cuh:58-61
+    std::vector<PublicKey *> gal_keys;     // one block of L*K key rows per Galois element, in the order of `elements`: row j*K + k of the block for g
+                                           // is (b, a) with b = -a*s + e + g_{j,k} * sigma_g(s) (the relinearisation-key layout with sigma_g(s) for s^2)
+    std::vector<uint32_t> elements;        // the Galois elements the blocks were made for (odd, below 2n)
+    uint32_t decomp_bits = 16;
+    // engine-side copies (one imported key set per element, NTT domain, packed for the fused key switch); built on first use
+    mutable std::vector<fhe_relin_keys_t *> imported;
+    mutable const void *imported_for = nullptr;
+    GaloisKeys() = default;
+    GaloisKeys(const GaloisKeys &) = delete;
+    GaloisKeys &operator=(const GaloisKeys &) = delete;
+    ~GaloisKeys() {
+        for (fhe_relin_keys_t *k : imported) fhe_relin_keys_destroy(k);
+        for (PublicKey *k : gal_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } }
+    }
 };
 
 struct Plaintext {                                            // include/fhe.cuh:72-75
@@ -172,13 +190,21 @@ public:
     template <class Rng>
     void relinkey_gen(RelinKeys &rlk, const SecretKey &sk, uint32_t decomp_bits, Rng &rng, uint64_t noise_scale = 1, int noise_bound = 3) {
         rlk.decomp_bits = decomp_bits;
+        std::unique_ptr<Polynomial> s2(new_polynomial());
+        params_.rns_ntt->multiply_rns(s2->coeffs, sk.sk->coeffs, sk.sk->coeffs);             // s^2 (src/fhe.cu:80-81)
+        keyswitch_rows(rlk.rlk_keys, *s2, sk, decomp_bits, rng, noise_scale, noise_bound);
+    }
+
+    // The L*K key rows that switch `target` (s^2, sigma_g(s)) to s: row j*K + k = (-a*s + e + g_{j,k} * target, a), g_{j,k} = 2^(k*w) in limb j.
+    template <class Rng>
+    void keyswitch_rows(std::vector<PublicKey *> &rows, const Polynomial &target, const SecretKey &sk, uint32_t decomp_bits, Rng &rng,
+                        uint64_t noise_scale = 1, int noise_bound = 3) {
         const uint32_t L = (uint32_t)params_.rns_moduli.size(), n = params_.n, levels = relin_levels(decomp_bits), K = levels / L;
         RNS_NTTEngine &E = *params_.rns_ntt;
-        std::unique_ptr<Polynomial> s2(new_polynomial()), tmp(new_polynomial());
-        E.multiply_rns(s2->coeffs, sk.sk->coeffs, sk.sk->coeffs);                              // s^2 (src/fhe.cu:80-81)
+        std::unique_ptr<Polynomial> tmp(new_polynomial());
         std::vector<uint256_t> h_s2((size_t)L * n), h_a((size_t)L * n), h_e((size_t)L * n), h_g((size_t)L * n);
         device_synchronize();
-        copy_to_host(h_s2.data(), s2->coeffs, h_s2.size());
+        copy_to_host(h_s2.data(), target.coeffs, h_s2.size());
         for (uint32_t j = 0; j < L; j++)
             for (uint32_t k = 0; k < K; k++) {
                 PublicKey *key = new PublicKey{new_polynomial(), new_polynomial()};
@@ -203,9 +229,9 @@ public:
                 copy_to_device(key->pk0->coeffs, h_e.data(), h_e.size());
                 E.sub_rns(key->pk0->coeffs, key->pk0->coeffs, tmp->coeffs);                   // e - a*s (:105)
                 copy_to_device(tmp->coeffs, h_g.data(), h_g.size());
-                E.add_rns(key->pk0->coeffs, key->pk0->coeffs, tmp->coeffs);                   // + g*s^2 (:106)
+                E.add_rns(key->pk0->coeffs, key->pk0->coeffs, tmp->coeffs);                   // + g*s^2 (:106) / + g*sigma_g(s)
                 device_synchronize();
-                rlk.rlk_keys.push_back(key);
+                rows.push_back(key);
             }
     }
 
@@ -240,6 +266,107 @@ public:
 
     void relinkey_gen(RelinKeys &rlk, const SecretKey &sk, uint32_t decomp_bits = 16) {    // src/fhe.cu:76 signature
         relinkey_gen(rlk, sk, decomp_bits, rng_, params_.t);
+    }
+
+    // ---- Galois keys and slot rotations (include/fhe.cuh:58-61, 86, 112-116; declared, never defined in the reference) ------------------
+    // Slot i of the encoding holds m(zeta_i), zeta_i = psi^(2i+1); sigma_g moves slot pi_g(i) to slot i, 2 pi_g(i) + 1 = g (2i + 1) (mod 2n).
+    // Ordered as row 0: 2i+1 = 3^k, row 1: 2i+1 = -3^k (mod 2n), k = 0 .. n/2 - 1, rotate_rows(r) is a cyclic left shift by r of both rows
+    // (g = 3^r) and rotate_columns swaps them (g = 2n - 1), as in SEAL; the natural slot order of encode() is a permutation of that order.
+
+    // the Galois element of a row rotation by `steps` (mod n/2; negative steps: the inverse power)
+    uint32_t galois_element(int steps) const {
+        uint32_t g = 0;
+        check(fhe_galois_element(params_.n, (int32_t)steps, &g), "FHEContext::galois_element");
+        return g;
+    }
+    uint32_t column_element() const { return 2 * params_.n - 1; }
+
+    // FHEContext::galoiskey_gen (include/fhe.cuh:86): the SEAL-style default set, row steps +-2^i for i = 0 .. log2(n/2) - 1 and the column element.
+    void galoiskey_gen(GaloisKeys &gal_keys, const SecretKey &sk) {
+        std::vector<int> steps;
+        for (uint32_t s = 1; s < params_.n / 2; s <<= 1) { steps.push_back((int)s); steps.push_back(-(int)s); }
+        galoiskey_gen(gal_keys, sk, steps, true, 16);
+    }
+    // Keys for the given row steps (and the column element when `columns`), digit width decomp_bits.  sigma_g(s) is computed on the engine
+    // (fhe_rns_automorphism); noise as in relinkey_gen (times t).
+    void galoiskey_gen(GaloisKeys &gal_keys, const SecretKey &sk, const std::vector<int> &steps, bool columns, uint32_t decomp_bits) {
+        if (!gal_keys.gal_keys.empty() && gal_keys.decomp_bits != decomp_bits)
+            throw std::runtime_error("FHEContext::galoiskey_gen: the key set already holds keys of another digit width");
+        gal_keys.decomp_bits = decomp_bits;
+        std::vector<uint32_t> elts;
+        for (int st : steps) elts.push_back(galois_element(st));
+        if (columns) elts.push_back(column_element());
+        std::unique_ptr<Polynomial> sg(new_polynomial());
+        for (uint32_t g : elts) {
+            if (std::find(gal_keys.elements.begin(), gal_keys.elements.end(), g) != gal_keys.elements.end()) continue;
+            check(fhe_rns_automorphism(params_.rns_ntt->handle(), sg->coeffs, sk.sk->coeffs, g, 1), "galoiskey_gen: sigma_g(s)");
+            keyswitch_rows(gal_keys.gal_keys, *sg, sk, decomp_bits, rng_, params_.t);
+            gal_keys.elements.push_back(g);
+        }
+    }
+
+    // result = sigma_g(ct), key-switched back to s (one fhe_ct_apply_galois call); `result` may be `ct`.
+    void apply_galois(Ciphertext &result, const Ciphertext &ct, uint32_t galois_elt, const GaloisKeys &gal_keys) {
+        if (ct.components.size() != 2) throw std::runtime_error("FHEContext::apply_galois: 2-component ciphertext expected (relinearize first)");
+        const size_t idx = galois_key_index(gal_keys, galois_elt);
+        if (idx == (size_t)-1) throw std::runtime_error("FHEContext::apply_galois: no Galois key for this element");
+        import_galois_keys(gal_keys);
+        std::unique_ptr<Polynomial> o0(new_polynomial()), o1(new_polynomial());     // the ABI call is out of place
+        check(fhe_ct_apply_galois(params_.rns_ntt->handle(), gal_keys.imported[idx], galois_elt, o0->coeffs, o1->coeffs, ct.components[0]->coeffs,
+                                  ct.components[1]->coeffs, 1), "FHEContext::apply_galois");
+        const float nb = ct.noise_budget; const uint32_t lv = ct.level;
+        ensure_components(result, 2);
+        while (result.components.size() > 2) { delete result.components.back(); result.components.pop_back(); }
+        const size_t bytes = o0->count() * sizeof(uint256_t);
+        check(fhe_hip_memcpy_d2d(result.components[0]->coeffs, o0->coeffs, bytes), "apply_galois copy");
+        check(fhe_hip_memcpy_d2d(result.components[1]->coeffs, o1->coeffs, bytes), "apply_galois copy");
+        device_synchronize();
+        result.noise_budget = nb; result.level = lv; result.is_ntt_form = false;
+    }
+    // FHEContext::rotate_rows (include/fhe.cuh:112-113): cyclic left shift by `steps` of both rows.  One call when the key set holds 3^steps,
+    // else a composition of the power-of-two steps it holds (either direction); throws when the step cannot be reached.
+    void rotate_rows(Ciphertext &result, const Ciphertext &ct, int steps, const GaloisKeys &gal_keys) {
+        const uint32_t half = params_.n / 2, r = (uint32_t)(((long long)steps % half + half) % half);
+        const uint32_t g = galois_element((int)r);
+        if (galois_key_index(gal_keys, g) != (size_t)-1) { apply_galois(result, ct, g, gal_keys); return; }
+        auto compose = [&](int dir, std::vector<uint32_t> &out) {  // r as a sum of +2^i, or n/2 - r as a sum of -2^i
+            const uint32_t m = dir > 0 ? r : half - r;
+            out.clear();
+            for (uint32_t b = 0; (1u << b) < half; b++) {
+                if (!((m >> b) & 1)) continue;
+                const uint32_t e = galois_element(dir * (int)(1u << b));
+                if (galois_key_index(gal_keys, e) == (size_t)-1) return false;
+                out.push_back(e);
+            }
+            return true;
+        };
+        std::vector<uint32_t> path;
+        if (!compose(1, path) && !compose(-1, path)) throw std::runtime_error("FHEContext::rotate_rows: no composition of the Galois keys reaches this step");
+        if (path.empty()) {                                         // r = 0: the identity
+            if (&result != &ct) { ensure_components(result, ct.components.size()); copy_ciphertext(result, ct); }
+            return;
+        }
+        apply_galois(result, ct, path[0], gal_keys);
+        for (size_t i = 1; i < path.size(); i++) apply_galois(result, result, path[i], gal_keys);
+    }
+    // FHEContext::rotate_columns (include/fhe.cuh:114-115): swaps the two rows (g = 2n - 1).
+    void rotate_columns(Ciphertext &result, const Ciphertext &ct, const GaloisKeys &gal_keys) { apply_galois(result, ct, column_element(), gal_keys); }
+
+    // hands every element's key rows to the engine once, cached in the GaloisKeys object
+    void import_galois_keys(const GaloisKeys &gk) {
+        if (gk.imported_for == params_.rns_ntt && gk.imported.size() == gk.elements.size()) return;
+        for (fhe_relin_keys_t *k : gk.imported) fhe_relin_keys_destroy(k);
+        gk.imported.clear();
+        const uint32_t levels = relin_levels(gk.decomp_bits);
+        if (gk.gal_keys.size() != (size_t)levels * gk.elements.size()) throw std::runtime_error("FHEContext: Galois key set of the wrong size");
+        for (size_t e = 0; e < gk.elements.size(); e++) {
+            std::vector<const void *> kb, ka;
+            for (uint32_t r = 0; r < levels; r++) { const PublicKey *k = gk.gal_keys[e * levels + r]; kb.push_back(k->pk0->coeffs); ka.push_back(k->pk1->coeffs); }
+            fhe_relin_keys_t *h = nullptr;
+            check(fhe_relin_keys_create(params_.rns_ntt->handle(), &h, gk.decomp_bits, kb.data(), ka.data(), levels), "FHEContext: Galois key import");
+            gk.imported.push_back(h);
+        }
+        gk.imported_for = params_.rns_ntt;
     }
 
     // SIMD-slot encoding (the reference's encode scales by delta, src/fhe.cu:113-136, and its BatchEncoder is a passthrough,
@@ -424,6 +551,15 @@ private:
         params_.n = params.poly_degree;
         params_.rns_moduli = moduli;
         params_.rns_ntt = new RNS_NTTEngine(params_.n, params_.rns_moduli.data(), (uint32_t)moduli.size());
+    }
+    static size_t galois_key_index(const GaloisKeys &gk, uint32_t g) {
+        for (size_t i = 0; i < gk.elements.size(); i++) if (gk.elements[i] == g) return i;
+        return (size_t)-1;
+    }
+    void copy_ciphertext(Ciphertext &dst, const Ciphertext &src) {
+        for (size_t i = 0; i < src.components.size(); i++)
+            check(fhe_hip_memcpy_d2d(dst.components[i]->coeffs, src.components[i]->coeffs, src.components[i]->count() * sizeof(uint256_t)), "ciphertext copy");
+        dst.noise_budget = src.noise_budget; dst.level = src.level;
     }
     void ensure_components(Ciphertext &ct, size_t num) {
         while (ct.components.size() < num) ct.components.push_back(new_polynomial());   // the reference `new`s and never frees (src/fhe.cu:202-205)

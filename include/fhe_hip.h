@@ -160,7 +160,7 @@ int fhe_rns_ntt_set_stream(fhe_rns_ntt_t *h, void *stream);
 int fhe_rns_ntt_width_class(const fhe_rns_ntt_t *h);
 /* Pre-sizes the library-owned workspaces for calls of up to `batch` units of every entry point that uses one -- fhe_rns_ntt_forward /
  * inverse (two-pass sizes), fhe_rns_ntt_multiply, fhe_rns_ntt_multiply_bcast, fhe_ct_multiply, fhe_ct_relinearize, fhe_ct_multiply_relin,
- * fhe_blind_rotate and fhe_blind_rotate_step -- so that later calls never allocate: required before capturing such calls into a hipGraph,
+ * fhe_rns_automorphism, fhe_ct_apply_galois, fhe_blind_rotate and fhe_blind_rotate_step -- so that later calls never allocate: required before capturing such calls into a hipGraph,
  * optional otherwise (the workspaces grow on first use).  No counterpart in the reference, which mallocs and frees inside every multiply (src/ntt.cu:51-74).
  * The key-switch workspaces depend on the digit count: import the key sets BEFORE reserving.  fhe_rns_ntt_workspace_bytes reports what
  * the engine holds at the moment (device bytes in its three workspaces; tables and key sets are not counted). */
@@ -231,6 +231,33 @@ int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_c0,
  * Outputs must be distinct and must not alias the inputs. */
 int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_c0, void *d_c1, const void *d_a0, const void *d_a1,
                           const void *d_b0, const void *d_b1, uint32_t batch);
+
+/* ---- Galois automorphisms / slot rotations ------------------------------------------------------------------------ */
+/* The reference declares GaloisKeys (include/fhe.cuh:58-61), FHEContext::galoiskey_gen (:86) and rotate_rows / rotate_columns (:112-116;
+ * docs/API_REFERENCE.md:143-144, 220-236) and defines none of them.
+ *   Automorphism.  For an odd Galois element g, 1 <= g < 2n, sigma_g maps a(x) to a(x^g) in Z_q[x]/(x^n + 1), coefficient by coefficient
+ *     and limb by limb.  Gather form, output index j: i = j * g^-1 mod 2n; out[j] = in[i] if i < n, else (q - in[i - n]) mod q.
+ *     sigma_g o sigma_h = sigma_{gh mod 2n}; sigma_1 is the identity.
+ *   Galois key for g.  The layout of a relinearisation key with sigma_g(s) in place of s^2: L*K rows, row j*K + k is (b, a) with
+ *     b = -a*s + e + g_{j,k} * sigma_g(s).  Imported with fhe_relin_keys_create (no key type of its own); the engine cannot tell which
+ *     element a key set was made for, so the caller passes g with the keys.
+ *   Applying g to a ciphertext.  (c0, c1) -> (sigma(c0) + sum_{j,k} D_{j,k}(sigma(c1)) b_{j,k}, sum_{j,k} D_{j,k}(sigma(c1)) a_{j,k}): bit for
+ *     bit fhe_ct_relinearize applied to (sigma(c0), 0, sigma(c1)).  The result decrypts under s to sigma_g(m).
+ *   Slots (slot i holds m(zeta_i), zeta_i = psi^(2i+1), t = 1 mod 2n).  Decrypting sigma_g(ct) gives slot i = v[pi_g(i)] with
+ *     2 pi_g(i) + 1 = g (2i + 1) (mod 2n).  rotate_rows(steps) uses g = 3^steps mod 2n (steps taken mod n/2, negative steps the inverse
+ *     power); rotate_columns uses g = 2n - 1.  With the slots of row 0 ordered by 2i+1 = 3^k and those of row 1 by 2i+1 = -3^k (mod 2n),
+ *     rotate_rows(r) is a cyclic left shift by r of both rows, as in SEAL, and rotate_columns swaps the rows.  The natural slot order of
+ *     the encoding is a permutation of this one. */
+/* Host only: *elt = 3^(steps mod n/2) mod 2n, the row-rotation element.  n a power of two, 8 <= n <= 2^30. */
+int fhe_galois_element(uint32_t n, int32_t steps, uint32_t *elt);
+/* d_out[b][l] = sigma_g(d_in[b][l]) on [batch][L][n]; out of place (d_out != d_in).  FHE_ERR_INVALID_ARG for an even g or g >= 2n. */
+int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t galois_elt, uint32_t batch);
+/* (d_out0, d_out1) = the ciphertext (d_c0, d_c1) under sigma_g, key-switched back to s with the Galois keys gk of g (see above).  Inputs are
+ * read only; outputs distinct from each other and from the inputs; keys imported for another engine are rejected.  On the LDS-resident
+ * word-sized sizes with packed keys: two launches (the automorphism of both components into the compact workspace, then the compact-operand
+ * key switch of fhe_ct_multiply_relin); elsewhere the automorphism followed by fhe_ct_relinearize. */
+int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1, const void *d_c0,
+                        const void *d_c1, uint32_t batch);
 
 /* ---- blind-rotation inner loop ------------------------------------------------------ */
 /* FHEContext::blind_rotate is only declared in the reference (include/fhe.cuh:139; pipeline prose README.md:146-159).  Its
