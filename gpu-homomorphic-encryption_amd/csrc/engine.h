@@ -1,0 +1,183 @@
+// engine.h -- what the host sources of the C ABI (include/fhe_hip.h) share: the engine and key-set structs, error plumbing, the
+// width-class -> field-type dispatch, workspaces, and the few entry points one subsystem offers the others.  Internal: nothing
+// declared here is exported from the library.  Which source owns what:
+//   core.hip        last error, device / memory entry points, host number theory, timers
+//   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
+//   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
+//   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve
+//   transforms.hip  wide and LDS launchers, the planners, forward / inverse / element-wise / multiply / tensor product (ntt_wide.hip.h,
+//                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
+//   keyswitch.hip   key import, relinearisation, multiply + relinearise, Galois, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
+//                   key / digit / monomial kernels of ntt_word.hip.h)
+//   rns.hip         CRT tables, to / from RNS, rescale, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
+// Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
+#pragma once
+#include "../../include/fhe_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "host_math.hpp"
+#include "lds_launch.h"
+#include "ntt256.hip.h"
+#include "ntt_field.hip.h"
+
+#pragma GCC visibility push(hidden)
+
+using fhe_host::U256;
+
+// ---- error plumbing (core.hip) ------------------------------------------------------------------------------------------------
+int fail(int code, const std::string &msg);              // records the thread's last error, returns code
+int ensure_device();
+int post_launch(hipStream_t s, const char *what);        // launch error of the call (FHE_HIP_SYNC=1: and of the kernel, after a stream sync)
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(FHE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
+    } while (0)
+
+inline fhe_dev::u256 to_dev(const uint64_t q[4]) { fhe_dev::u256 r; std::memcpy(r.l, q, 32); return r; }
+
+inline unsigned ew_grid(size_t items) {
+    size_t blocks = (items + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));   // grid-stride above 8192 blocks
+}
+
+// ---- engine handle ------------------------------------------------------------------------------------------------------------
+// Environment switches, read once at engine creation (read_env, engine.hip)
+struct EngineEnv {
+    int force_width = 0;
+    bool no_wide_lazy = false, no_wide_tiles = false;
+    bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
+         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false,
+         split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
+    uint32_t small_batch_polys = 256, coop_polys = 64, split_pairs_polys = 128, overlap_chunks = 4;
+    int ct_form_force = 0;
+};
+
+struct fhe_rns_ntt {
+    int device = 0;
+    uint32_t n = 0, log_n = 0, L = 0;
+    int width = 0;
+    size_t residue_bytes = 8; int lds_id = 65;   // of the word-sized class's field (set at creation through with_word_field): bytes of a compact residue, id of its instances in lds_table.cpp
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipStream_t aux_stream = nullptr;   // second stream of the overlapped one-call multiply (fork / join with events around it)
+    hipEvent_t ev_chunk[16] = {}, ev_join = nullptr;   // tensor product of chunk i done (engine stream) -> key switch of chunk i may start (second stream)
+    EngineEnv env;
+    uint32_t max_digits = 0, max_composed_digits = 0;   // largest digit count K of the key sets imported on this engine / of those without packed tables (fhe_rns_ntt_reserve)
+    void *d_limbs = nullptr;            // owned by d_tables
+    void *d_wlimbs = nullptr;           // FHE_WIDTH_256: WLimb<wide_nl>[L] for the NTT kernels of ntt_wide.hip.h (owned by d_tables)
+    uint32_t sub_top = 0;               // word-sized classes beyond the LDS range: log2 n = 13 + sub_top (two-pass transforms), else 0
+    int wide_nl = 0;                    // FHE_WIDTH_256: 64-bit limbs per residue in those kernels (2: q < 2^127, 4: q < 2^255)
+    bool wide_lazy = false;             // FHE_WIDTH_256: every modulus below 2^(64 wide_nl - 6): the lazy tile kernels (unless FHE_HIP_NO_WIDE_LAZY)
+    std::vector<void *> d_tables;
+    void *d_ws = nullptr; size_t ws_bytes = 0;
+    void *d_ws2 = nullptr; size_t ws2_bytes = 0;   // c2 of the fused multiply + relinearise (compact or containers); separate from d_ws, which the general paths use
+    void *d_ws3 = nullptr; size_t ws3_bytes = 0;   // compact polynomials between the two launches of a two-pass transform (sub_top != 0)
+    uint32_t *d_flag = nullptr;
+    std::vector<U256> moduli;
+    void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
+    void *d_rescale = nullptr;           // RescaleLimb[L-1], built on first use of rescale_drop_last (owned by d_tables)
+    void *d_bconv = nullptr;             // ((Q/q_i) mod p_j) * R_j for the most recent base-conversion target (owned by d_tables)
+    const void *bconv_target = nullptr;
+    void *d_rescale_w = nullptr;         // word-sized classes: (q_last^-1 mod q_l) as pw operands, E[L-1] (owned by d_tables)
+    void *d_bconv_w_minv = nullptr, *d_bconv_w_mat = nullptr;   // word-sized classes: base-conversion operands for bconv_w_target
+    const void *bconv_w_target = nullptr;
+    std::vector<U256> bconv_moduli, bconv_w_moduli;   // the target bases the cached matrices were built for (a handle address can be re-used)
+    void *d_from_rns_w_minv = nullptr, *d_from_rns_w_M = nullptr;   // integer word classes: CRT operands and Q / q_l (owned by d_tables)
+    void *d_to_rns_w = nullptr;          // integer word classes: 2^(W k) mod q_l as pw operands, E[L][256 / W] (owned by d_tables)
+    fhe_dev::CrtBig crt_big;
+    int crt_state = 0;                   // 0 = not built, 1 = ready, -1 = Q too large for from_rns (to_rns still fine)
+    double cdt_sigma = 0; uint64_t *d_cdt = nullptr; uint32_t cdt_len = 0;   // cumulative table of the last Gaussian sampler call
+};
+struct fhe_ntt { fhe_rns_ntt *impl; };
+
+struct fhe_relin_keys {
+    fhe_rns_ntt *owner = nullptr;
+    uint32_t decomp_bits = 0, K = 0, num_keys = 0;
+    void *d_kb = nullptr, *d_ka = nullptr;      // [num_keys][L][n] containers, NTT domain, canonical
+    void *d_pkb = nullptr, *d_pka = nullptr;    // packed tables for the fused key-switch kernel (word-sized paths)
+};
+
+// The one place that maps a word-sized width class to its field type: fn(F32{}) / fn(F52{}) / fn(F64{}) / fn(F64X{}), in the body
+// `using F = decltype(f);`.  The FHE_WIDTH_256 branch stays with the caller.
+template <class Fn>
+int with_word_field(const fhe_rns_ntt *h, Fn &&fn) {
+    switch (h->width) {
+        case FHE_WIDTH_32: return fn(fhe_dev::F32{});
+        case FHE_WIDTH_52: return fn(fhe_dev::F52{});
+        case FHE_WIDTH_64: return fn(fhe_dev::F64{});
+        case FHE_WIDTH_64X: return fn(fhe_dev::F64X{});
+        default: return fail(FHE_ERR_UNSUPPORTED, "width class " + std::to_string(h->width) + " has no word-sized field (compact polynomials and the field kernels exist on the word-sized classes only)");
+    }
+}
+inline size_t residue_bytes(const fhe_rns_ntt *h) { return h->residue_bytes; }   // of a compact polynomial's coefficient
+inline int lds_width_id(const fhe_rns_ntt *h) { return h->lds_id; }
+
+// ---- engine.hip -----------------------------------------------------------------------------------------------------------------
+int create_impl(fhe_rns_ntt **out, uint32_t n, const uint64_t (*moduli)[4], uint32_t L, bool base_only = false);
+void destroy_impl(fhe_rns_ntt *h);
+int check_call(const fhe_rns_ntt *h, uint32_t batch, const char *what);
+int check_inputs(fhe_rns_ntt *h, std::initializer_list<const void *> operands, uint32_t batch);   // FHE_HIP_CHECK_INPUTS=1
+// Library-owned workspaces, per engine, grown on demand (never while the engine's stream is capturing):
+// d_ws : general paths (the reference mallocs/frees per multiply, src/ntt.cu:51-74) and the transformed b-side of the two-launch tensor product
+// d_ws2: c0, c1, c2 of the fused multiply + relinearise and the compact accumulators of a blind-rotation loop
+// d_ws3: the compact polynomials between the two launches of a two-pass transform (N beyond the LDS range)
+int grow_ws(fhe_rns_ntt *h, void **ws, size_t *have, size_t bytes);
+inline int ensure_ws(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws, &h->ws_bytes, bytes); }
+inline int ensure_ws2(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws2, &h->ws2_bytes, bytes); }
+inline int ensure_ws3(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws3, &h->ws3_bytes, bytes); }
+int ensure_aux_stream(fhe_rns_ntt *h);   // second stream + events of the chunked two-stage pipelines, created on first use
+
+template <class T>
+int upload(fhe_rns_ntt *h, const std::vector<T> &v, void **out) {    // a table owned by the engine (d_tables)
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, v.size() * sizeof(T)));
+    h->d_tables.push_back(d);
+    HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = d;
+    return FHE_OK;
+}
+
+// ---- transforms.hip -------------------------------------------------------------------------------------------------------------
+// Which form runs a multiply, tensor product, key switch or external product is decided by the planners and nowhere else: every entry point
+// plans, ensures the plan's workspace, fills LdsArgs and launches; fhe_rns_ntt_reserve sizes the workspaces with the same planners.
+struct LdsPlan {
+    fhe_dev::LdsForm form;
+    int ws = 0;                          // the form's workspace: 0 none, 1 d_ws, 3 d_ws3
+    size_t bytes = 0;
+    bool compact = false;                // key switch: c2 is read compact (compacted first, or from the fused tensor product); external product: the
+                                         // blind-rotation loop keeps the accumulator pair compact
+    bool prerot = false;                 // external product: the loop applies the monomial factor once per step (rotated digit sources b0, b1)
+};
+inline void *plan_ws(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? h->d_ws : p.ws == 3 ? h->d_ws3 : nullptr; }
+inline int ensure_plan(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? ensure_ws(h, p.bytes) : p.ws == 3 ? ensure_ws3(h, p.bytes) : FHE_OK; }
+// Key switch source.  KS_C2: c2 in containers, compacted first where that pays; KS_C2_AS_IS: containers that must stay where they are (c2 already
+// in d_ws2: the composed multiply + relinearise under a testing switch); KS_FUSED: c2 and the addends are compact polynomials
+enum KsSource { KS_C2, KS_C2_AS_IS, KS_FUSED };
+LdsPlan plan_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands);
+LdsPlan plan_ct_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands, bool compact_out, bool alone);
+bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys);
+LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone);
+LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
+// one call of the (field, log_n) instance: the instance launches exactly the form A asks for, or nothing and says so
+int lds_launch(fhe_rns_ntt *h, const fhe_dev::LdsArgs &A, const char *what, int log_n = 0);
+int do_forward(fhe_rns_ntt *h, void *d_data, uint32_t batch);
+int do_inverse(fhe_rns_ntt *h, void *d_data, uint32_t batch);
+template <int OP> int do_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t batch, const char *what);   // OP 0: product, 1: add, 2: sub
+int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0, const void *b1, uint32_t batch);
+int compact_poly(fhe_rns_ntt *h, void *out, const void *in, size_t containers);   // containers -> compact polynomials (word-sized classes)
+
+// ---- rns.hip --------------------------------------------------------------------------------------------------------------------
+int ensure_crt(fhe_rns_ntt *h);          // CrtLimb[L] (and Q, where it fits 255 bits) on first use
+
+#pragma GCC visibility pop

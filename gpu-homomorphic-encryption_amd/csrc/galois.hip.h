@@ -1,5 +1,5 @@
 // galois.hip.h -- Galois automorphisms sigma_g: a(x) -> a(x^g) over Z_q[x]/(x^n + 1), g odd, 1 <= g < 2n (slot rotations,
-// FHEContext::rotate_rows / rotate_columns, include/fhe.cuh:112-116).  Streaming kernels, compiled into fhe_hip.o.
+// FHEContext::rotate_rows / rotate_columns, include/fhe.cuh:112-116).  Streaming kernels, compiled into keyswitch.o.
 //
 // Gather form: output coefficient j reads input coefficient i = j * g^-1 mod 2n and negates it when i >= n (x^n = -1).  Consecutive
 // outputs read at stride g^-1 across a limb polynomial.  The STAGED form loads a limb polynomial coalesced into LDS, takes the permuted

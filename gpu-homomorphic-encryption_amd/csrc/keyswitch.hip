@@ -1,0 +1,486 @@
+// keyswitch.hip -- key import and packing, relinearisation, multiply + relinearise, Galois automorphisms, blind rotation.
+#include "engine.h"
+
+#include <algorithm>
+#include <utility>
+
+#include "galois.hip.h"
+#include "ntt256_keyswitch.hip.h"
+#include "ntt_word.hip.h"
+
+// ------------------------------------------------------------------------------------------------------
+// relinearisation / key switching (general path: digit embedding -> batched forward NTT -> MAC -> inverse)
+// ------------------------------------------------------------------------------------------------------
+static uint32_t relin_digits(const fhe_rns_ntt *h, uint32_t w) {
+    int mx = 0;
+    for (const U256 &q : h->moduli) mx = q.bit_length() > mx ? q.bit_length() : mx;
+    return ((uint32_t)mx + w - 1) / w;
+}
+extern "C" int fhe_relin_num_digits(const fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t *digits) {
+    if (!h || !digits) return fail(FHE_ERR_INVALID_ARG, "null argument");
+    if (decomp_bits < 1 || decomp_bits > 64) return fail(FHE_ERR_INVALID_ARG, "decomp_bits must be in [1, 64]");
+    *digits = relin_digits(h, decomp_bits);
+    return FHE_OK;
+}
+extern "C" int fhe_relin_keys_destroy(fhe_relin_keys_t *rk) {
+    if (rk) {
+        for (void *p : {rk->d_kb, rk->d_ka, rk->d_pkb, rk->d_pka}) if (p) (void)hipFree(p);
+        delete rk;
+    }
+    return FHE_OK;
+}
+
+// packed key tables for the fused key-switch kernels (word-sized paths)
+template <class F>
+static int pack_relin_keys_t(fhe_rns_ntt *h, fhe_relin_keys *rk) {
+    const size_t elems = (size_t)rk->num_keys * h->L * h->n;
+    HIP_TRY(hipMalloc(&rk->d_pkb, elems * sizeof(typename F::E)));
+    HIP_TRY(hipMalloc(&rk->d_pka, elems * sizeof(typename F::E)));
+    hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid(elems)), dim3(256), 0, h->stream, (typename F::E *)rk->d_pkb,
+                       (const typename F::V16 *)rk->d_kb, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->num_keys);
+    hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid(elems)), dim3(256), 0, h->stream, (typename F::E *)rk->d_pka,
+                       (const typename F::V16 *)rk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->num_keys);
+    return post_launch(h->stream, "pack_keys_kernel");
+}
+
+extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, uint32_t decomp_bits,
+                                     const void *const *d_keys_b, const void *const *d_keys_a, uint32_t num_keys) {
+    if (!h || !out || !d_keys_b || !d_keys_a) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null argument");
+    *out = nullptr;
+    if (decomp_bits < 1 || decomp_bits > 64) return fail(FHE_ERR_INVALID_ARG, "decomp_bits must be in [1, 64]");
+    const uint32_t K = relin_digits(h, decomp_bits);
+    if (num_keys != h->L * K) {
+        char buf[128]; snprintf(buf, sizeof buf, "relin_keys_create: expected %u keys (L = %u limbs x K = %u digits), got %u", h->L * K, h->L, K, num_keys);
+        return fail(FHE_ERR_INVALID_ARG, buf);
+    }
+    for (uint32_t i = 0; i < num_keys; i++) if (!d_keys_b[i] || !d_keys_a[i]) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null key pointer");
+    (void)hipGetLastError();
+    fhe_relin_keys *rk = new (std::nothrow) fhe_relin_keys();
+    if (!rk) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
+    rk->owner = h; rk->decomp_bits = decomp_bits; rk->K = K; rk->num_keys = num_keys;
+    if (K > h->max_digits) h->max_digits = K;                          // fhe_rns_ntt_reserve sizes the key-switch workspaces for it
+    const size_t S = (size_t)h->L * h->n * 32;
+    hipError_t e;
+    if ((e = hipMalloc(&rk->d_kb, S * num_keys)) != hipSuccess || (e = hipMalloc(&rk->d_ka, S * num_keys)) != hipSuccess) {
+        fhe_relin_keys_destroy(rk); return fail(FHE_ERR_HIP, std::string("relin_keys_create: ") + hipGetErrorString(e));
+    }
+    for (uint32_t i = 0; i < num_keys; i++) {
+        if ((e = hipMemcpyAsync((char *)rk->d_kb + i * S, d_keys_b[i], S, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync((char *)rk->d_ka + i * S, d_keys_a[i], S, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess) {
+            fhe_relin_keys_destroy(rk); return fail(FHE_ERR_HIP, std::string("relin_keys_create copy: ") + hipGetErrorString(e));
+        }
+    }
+    int rc = do_forward(h, rk->d_kb, num_keys);
+    if (!rc) rc = do_forward(h, rk->d_ka, num_keys);
+    // The fused kernels feed a digit of limb j (< min(2^w, q_j)) straight into limb i's lazy forward transform, whose
+    // integer butterflies accept inputs below 4*q_i; bases mixing very different prime sizes go through the general
+    // composition, which reduces every digit modulo q_i first.
+    bool digits_fit = true;
+    if (h->width == FHE_WIDTH_32 || h->width == FHE_WIDTH_64) {
+        fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
+        for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
+        fhe_host::u128 digit_bound = decomp_bits >= 64 ? q_max : (((fhe_host::u128)1 << decomp_bits) < q_max ? ((fhe_host::u128)1 << decomp_bits) : q_max);
+        digits_fit = digit_bound <= 4 * q_min;
+    } else if (h->width == FHE_WIDTH_64X) {   // canonical butterflies: a digit must be a residue of q_i as it stands
+        fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
+        for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
+        digits_fit = (decomp_bits >= 64 ? q_max : (((fhe_host::u128)1 << decomp_bits) < q_max ? ((fhe_host::u128)1 << decomp_bits) : q_max)) <= q_min;
+    }
+    // the fused kernels address a packed table through a buffer descriptor with 32-bit offsets (fhe_dev::TableBuf): a table of 4 GiB or
+    // more (L*K*L*n residues: not reached by any parameter set of the reference) stays on the general composition
+    const bool table_fits = (size_t)rk->num_keys * h->L * h->n * (h->width == FHE_WIDTH_32 ? 4 : 8) < ((size_t)1 << 32);
+    if (!rc && h->width != FHE_WIDTH_256 && !h->sub_top && digits_fit && table_fits && !h->env.no_fused_keyswitch) {
+        rc = with_word_field(h, [&](auto f) { return pack_relin_keys_t<decltype(f)>(h, rk); });
+        if (!rc) {   // the fused kernels read only the packed tables (n * sizeof(E) bytes per key polynomial instead of n * 32): drop the
+                     // container copy, so that a bootstrapping key of several hundred RGSW ciphertexts fits (hipFree waits for the packing)
+            (void)hipFree(rk->d_kb); (void)hipFree(rk->d_ka);
+            rk->d_kb = rk->d_ka = nullptr;
+        }
+    }
+    if (rc) { fhe_relin_keys_destroy(rk); return rc; }
+    if (!rk->d_pkb && K > h->max_composed_digits) h->max_composed_digits = K;   // this key set runs the composed key switch (digit polynomials in the workspace)
+    *out = rk;
+    return FHE_OK;
+}
+
+template <class F>
+static int relin_embed_mac_lds(fhe_rns_ntt *h, const fhe_relin_keys *rk, char *D, char *acc0, char *acc1, const void *c2, uint32_t chunk, int phase) {
+    using V = typename F::V16;
+    const uint32_t LK = h->L * rk->K;
+    if (phase == 0) {
+        size_t total = (size_t)LK * chunk * h->L * h->n * 2;
+        hipLaunchKernelGGL((fhe_dev::digit_embed_kernel<F>), dim3(ew_grid(total)), dim3(256), 0, h->stream, (V *)D, (const V *)c2,
+                           (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->K, rk->decomp_bits, chunk);
+        return post_launch(h->stream, "digit_embed_kernel");
+    }
+    size_t halves = (size_t)chunk * h->L * h->n * 2;
+    hipLaunchKernelGGL((fhe_dev::relin_mac_kernel<F>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)D,
+                       (const V *)rk->d_kb, (const V *)rk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, chunk);
+    return post_launch(h->stream, "relin_mac_kernel");
+}
+static int relin_embed_mac(fhe_rns_ntt *h, const fhe_relin_keys *rk, char *D, char *acc0, char *acc1, const void *c2, uint32_t chunk, int phase) {
+    if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return relin_embed_mac_lds<decltype(f)>(h, rk, D, acc0, acc1, c2, chunk, phase); });
+    const uint32_t LK = h->L * rk->K;
+    if (phase == 0) {
+        size_t total = (size_t)LK * chunk * h->L * h->n;
+        hipLaunchKernelGGL(fhe_dev::digit_embed256_kernel, dim3(ew_grid(total)), dim3(256), 0, h->stream, (fhe_dev::u256 *)D, (const fhe_dev::u256 *)c2,
+                           (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, rk->K, rk->decomp_bits, chunk);
+        return post_launch(h->stream, "digit_embed256_kernel");
+    }
+    size_t count = (size_t)chunk * h->L * h->n;
+    hipLaunchKernelGGL(fhe_dev::relin_mac256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)acc0, (fhe_dev::u256 *)acc1,
+                       (const fhe_dev::u256 *)D, (const fhe_dev::u256 *)rk->d_kb, (const fhe_dev::u256 *)rk->d_ka,
+                       (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, LK, chunk);
+    return post_launch(h->stream, "relin_mac256_kernel");
+}
+
+// The key-switch call of a plan: digit source c2 (compact where the plan says so), results r0 / r1, addends add0 / add1 (nullptr: r0 / r1 are
+// accumulated in place), `polys` limb polynomials on stream s
+static fhe_dev::LdsArgs keyswitch_args(fhe_rns_ntt *h, const fhe_relin_keys *rk, const LdsPlan &P, void *r0, void *r1, const void *c2, const void *add0,
+                                       const void *add1, uint32_t polys, hipStream_t s) {
+    fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, P.form, r0, r1, nullptr, c2, add0, add1, nullptr, h->d_limbs, h->L, polys, s};
+    B.in_compact = P.compact; B.ws = plan_ws(h, P);
+    B.kb = rk->d_pkb; B.ka = rk->d_pka; B.K = rk->K; B.w = rk->decomp_bits;
+    return B;
+}
+// Two-stream chunk pipeline: what the engine's stream has queued for chunk c is done -> the second stream may start on it; at the end the
+// engine's stream joins the second one, so the call stays ordered on the engine's stream (and can be captured: fork / join through events).
+static int fork_chunk(fhe_rns_ntt *h, uint32_t c) {
+    HIP_TRY(hipEventRecord(h->ev_chunk[c], h->stream));
+    HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_chunk[c], 0));
+    return FHE_OK;
+}
+static int join_chunks(fhe_rns_ntt *h) {
+    HIP_TRY(hipEventRecord(h->ev_join, h->aux_stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    return FHE_OK;
+}
+
+extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_c0, void *d_c1, const void *d_c2, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_relinearize"); if (rc) return rc;
+    if (!rk || !d_c0 || !d_c1 || !d_c2) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: null argument");
+    if (rk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: keys were imported for a different engine");
+    if (d_c0 == d_c1 || d_c0 == d_c2 || d_c1 == d_c2) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: components must be distinct buffers");
+    if ((rc = check_inputs(h, {d_c0, d_c1, d_c2}, batch))) return rc;
+    if (rk->d_pkb) {   // word-sized paths: fused launches
+        // (c2 already in the workspace: the composed multiply + relinearise under a testing switch -- it stays where it is)
+        const bool c2_in_ws2 = h->d_ws2 && (const char *)d_c2 >= (const char *)h->d_ws2 && (const char *)d_c2 < (const char *)h->d_ws2 + h->ws2_bytes;
+        const LdsPlan P = plan_keyswitch(h, batch * h->L, rk->K, c2_in_ws2 ? KS_C2_AS_IS : KS_C2, true);
+        const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * residue_bytes(h);
+        uint32_t chunks = 1;
+        if (P.compact) {
+            if ((rc = ensure_ws2(h, (size_t)batch * Sc))) return rc;
+            // Chunks of whole ciphertexts on two streams: the compaction of chunk i+1 (HBM-bound) runs beside the key switch of chunk i.
+            // (measured, N = 8192 x 4 x 30-bit, batch 1024: compaction alone 773 K -> 805 K relin/s at w = 16, 948 K -> 1007 K at w = 30; with the key switch of
+            //  chunk i beside the compaction of chunk i+1 on a second stream 807 K / 953 K at two chunks, 772 K / 948 K at four: one stream unless asked)
+            if (h->width == FHE_WIDTH_32 && h->env.relin_chunks_forced) chunks = h->env.overlap_chunks;
+            while (chunks > 1 && ((size_t)batch * h->L / chunks < 1024 || batch < chunks)) chunks--;
+            if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
+        }
+        for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
+            const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
+            const void *c2 = (const char *)d_c2 + (size_t)b0 * S;
+            if (P.compact) {
+                char *c2c = (char *)h->d_ws2 + (size_t)b0 * Sc;
+                if ((rc = compact_poly(h, c2c, c2, (size_t)nb * h->L * h->n))) return rc;
+                c2 = c2c;
+            }
+            const LdsPlan Q = chunks == 1 ? P : plan_keyswitch(h, nb * h->L, rk->K, KS_C2, false);
+            if ((rc = ensure_plan(h, Q))) return rc;
+            if (chunks > 1 && (rc = fork_chunk(h, c))) return rc;
+            if ((rc = lds_launch(h, keyswitch_args(h, rk, Q, (char *)d_c0 + (size_t)b0 * S, (char *)d_c1 + (size_t)b0 * S, c2, nullptr, nullptr, nb * h->L,
+                                                   chunks > 1 ? h->aux_stream : h->stream), "ntt_keyswitch_kernel"))) return rc;
+            b0 += nb;
+        }
+        return chunks > 1 ? join_chunks(h) : FHE_OK;
+    }
+    const uint32_t LK = h->L * rk->K;
+    const size_t S = (size_t)h->L * h->n * 32;
+    // workspace: digit polynomials D[LK][chunk] + two accumulators; bounded to ~1 GiB, the batch is processed in chunks
+    uint32_t chunk = (uint32_t)(((size_t)1 << 30) / ((LK + 2) * S));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    if ((rc = ensure_ws(h, (size_t)(LK + 2) * chunk * S))) return rc;
+    char *D = (char *)h->d_ws, *acc0 = D + (size_t)LK * chunk * S, *acc1 = acc0 + (size_t)chunk * S;
+    for (uint32_t done = 0; done < batch; done += chunk) {
+        const uint32_t nb = batch - done < chunk ? batch - done : chunk;
+        const char *c2 = (const char *)d_c2 + (size_t)done * S;
+        char *c0 = (char *)d_c0 + (size_t)done * S, *c1 = (char *)d_c1 + (size_t)done * S;
+        if ((rc = relin_embed_mac(h, rk, D, acc0, acc1, c2, nb, 0))) return rc;
+        if ((rc = do_forward(h, D, LK * nb))) return rc;
+        if ((rc = relin_embed_mac(h, rk, D, acc0, acc1, c2, nb, 1))) return rc;
+        if ((rc = do_inverse(h, acc0, nb))) return rc;
+        if ((rc = do_inverse(h, acc1, nb))) return rc;
+        if ((rc = do_ew<1>(h, c0, c0, acc0, nb, "relin add"))) return rc;
+        if ((rc = do_ew<1>(h, c1, c1, acc1, nb, "relin add"))) return rc;
+    }
+    return FHE_OK;
+}
+
+// FHEContext::multiply as the reference declares it (src/fhe.cu:199-224: tensor product, then relinearize): (c0, c1) = relin(a (x) b).
+// On the LDS-resident sizes of the word-sized classes the three components of the tensor product never take the 32-byte container
+// form: the tensor-product kernel(s) write c0, c1, c2 to a compact workspace (sizeof(residue) bytes per coefficient) and the
+// key-switch kernel reads its digit source (c2) and its addends (c0, c1) from there -- HBM traffic 4 S in + 2 S out + 3 compact
+// components written once and read back (c2 by every limb workgroup) instead of 12 S.  Elsewhere: fhe_ct_multiply into a container
+// workspace followed by fhe_ct_relinearize.  Same bits either way (tests compare both with the oracle).
+extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_c0, void *d_c1, const void *d_a0, const void *d_a1,
+                                     const void *d_b0, const void *d_b1, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_multiply_relin"); if (rc) return rc;
+    if (!rk || !d_c0 || !d_c1 || !d_a0 || !d_a1 || !d_b0 || !d_b1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: null argument");
+    if (rk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: keys were imported for a different engine");
+    const void *ins[4] = {d_a0, d_a1, d_b0, d_b1};
+    for (const void *i : ins) if (d_c0 == i || d_c1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must not alias inputs");
+    if (d_c0 == d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must be distinct");
+    if ((rc = check_inputs(h, {d_a0, d_a1, d_b0, d_b1}, batch))) return rc;
+    const uint32_t polys = batch * h->L;
+    if (plan_fused_ct_relin(h, rk->d_pkb != nullptr)) {
+        const size_t eb = residue_bytes(h), cbytes = (size_t)polys * h->n * eb;         // one compact component
+        if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
+        char *c0c = (char *)h->d_ws2, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
+        // The two kernels of the call sit on different roofs: the tensor product streams 4 S in at the HBM rate, the key switch (compact
+        // operands) is bound by instruction issue.  The call is therefore a two-stage pipeline over chunks of whole ciphertexts: every
+        // tensor product runs on the engine's stream, back to back; the key switch of chunk i runs on a second stream as soon as
+        // tensor product i is done (event), i.e. beside tensor product i+1 on the same CUs.  The engine's stream joins the second one
+        // at the end, so the call stays ordered on the engine's stream (and can be captured into a graph: fork / join through events).
+        // Every chunk has its own slice of the compact workspace (and of the two-launch form's, sized here for the whole batch).
+        const LdsPlan T = plan_ct_multiply(h, polys, false, true, true);
+        if ((rc = ensure_plan(h, T))) return rc;
+        const bool two = T.form == fhe_dev::LDS_TWO_LAUNCH;
+        uint32_t chunks = h->env.overlap_chunks;
+        if (two && h->log_n >= 14) chunks = 1;                  // 128+ KiB of LDS per workgroup: the two stages cannot share a CU anyway
+        while (chunks > 1 && (polys / chunks < 1024 || batch < chunks)) chunks--;   // every chunk must fill the chip: >= 256 CUs x 4 workgroups (one per limb polynomial)
+        if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
+        const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * eb;   // bytes of one ciphertext component: containers / compact
+        for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
+            const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
+            const size_t o = (size_t)b0 * S, oc = (size_t)b0 * Sc;
+            const LdsPlan Tc = chunks == 1 ? T : plan_ct_multiply(h, nb * h->L, false, true, false);
+            fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, Tc.form, c0c + oc, c1c + oc, c2c + oc, (const char *)d_a0 + o, (const char *)d_a1 + o, (const char *)d_b0 + o,
+                               (const char *)d_b1 + o, h->d_limbs, h->L, nb * h->L, h->stream};
+            A.out_compact = true;
+            if (Tc.ws) A.ws = (char *)plan_ws(h, Tc) + (two ? 2 * oc : 0);   // two-launch: two compact polynomials per limb polynomial of the chunk
+            if ((rc = lds_launch(h, A, "tensor product (compact outputs)"))) return rc;
+            if (chunks > 1 && (rc = fork_chunk(h, c))) return rc;
+            // (the few-ciphertext parts take d_ws: never beside the two-launch tensor product, which the 4-byte field up to 2^14 does not use anyway)
+            const LdsPlan Kc = plan_keyswitch(h, nb * h->L, rk->K, KS_FUSED, chunks == 1 && !two);
+            if ((rc = ensure_plan(h, Kc))) return rc;
+            if ((rc = lds_launch(h, keyswitch_args(h, rk, Kc, (char *)d_c0 + o, (char *)d_c1 + o, c2c + oc, c0c + oc, c1c + oc, nb * h->L,
+                                                   chunks > 1 ? h->aux_stream : h->stream), "key switch (compact operands)"))) return rc;
+            b0 += nb;
+        }
+        return chunks > 1 ? join_chunks(h) : FHE_OK;
+    }
+    if ((rc = ensure_ws2(h, (size_t)polys * h->n * 32))) return rc;
+    if ((rc = do_ct_multiply(h, d_c0, d_c1, h->d_ws2, d_a0, d_a1, d_b0, d_b1, batch))) return rc;
+    return fhe_ct_relinearize(h, rk, d_c0, d_c1, h->d_ws2, batch);
+}
+
+
+// ------------------------------------------------------------------------------------------------------
+// Galois automorphisms and slot rotations (FHEContext::rotate_rows / rotate_columns, include/fhe.cuh:112-116)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int fhe_galois_element(uint32_t n, int32_t steps, uint32_t *elt) {
+    if (!elt) return fail(FHE_ERR_INVALID_ARG, "galois_element: elt is null");
+    if (n < 8 || n > (1u << 30) || (n & (n - 1))) return fail(FHE_ERR_INVALID_ARG, "galois_element: n must be a power of two in [8, 2^30]");
+    const uint32_t half = n / 2, m = 2 * n;                          // 3 generates a cyclic subgroup of order n/2 of (Z/2n)^*
+    const uint32_t e = (uint32_t)(((int64_t)steps % half + half) % half);
+    uint64_t r = 1, b = 3;
+    for (uint32_t k = e; k; k >>= 1) { if (k & 1) r = r * b % m; b = b * b % m; }
+    *elt = (uint32_t)r;
+    return FHE_OK;
+}
+static int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what) {
+    if (!(g & 1) || g >= 2 * h->n)
+        return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the Galois element must be odd and below 2n");
+    return FHE_OK;
+}
+static uint32_t galois_inverse(const fhe_rns_ntt *h, uint32_t g) {    // g^-1 mod 2n (g odd): Newton iteration modulo 2^32, then reduced
+    uint32_t x = g;
+    for (int i = 0; i < 5; i++) x *= 2 - g * x;
+    return x & (2 * h->n - 1);
+}
+// sigma_g of one or two components (in1 == nullptr: one) into out0 / out1, zero_out (optional) cleared beside them; compact: E per coefficient out.
+// The staged form up to 32 KiB per limb polynomial (4-byte residues up to N = 8192, 8-byte ones up to 4096), the L2 gather above: the interleaved
+// A/B of scratch/galois_ab.hip had the staged form 13 % faster at 32 KiB and 8-14 % slower at 64 KiB (two workgroups per CU).
+template <class F>
+static int galois_word(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g_inv, size_t polys, bool compact) {
+    using V = typename F::V16; using E = typename F::E;
+    const uint32_t comps = in1 ? 2 : 1;
+    const size_t lds = (size_t)h->n * sizeof(E);
+    const bool staged = lds <= fhe_dev::GALOIS_STAGE_BYTES;
+    const dim3 block(fhe_dev::GALOIS_T), grid(staged ? (unsigned)std::min<size_t>(polys, 1u << 20) : ew_grid(polys * h->n), comps);
+    const fhe_dev::Limb<F> *limbs = (const fhe_dev::Limb<F> *)h->d_limbs;
+    if (compact) {
+        if (staged) hipLaunchKernelGGL((fhe_dev::galois_compact_kernel<F, true>), grid, block, lds, h->stream, (E *)out0, (E *)out1, (E *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+        else hipLaunchKernelGGL((fhe_dev::galois_compact_kernel<F, false>), grid, block, 0, h->stream, (E *)out0, (E *)out1, (E *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+        return post_launch(h->stream, "galois_compact_kernel");
+    }
+    if (staged) hipLaunchKernelGGL((fhe_dev::galois_kernel<F, true>), grid, block, lds, h->stream, (V *)out0, (V *)out1, (V *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+    else hipLaunchKernelGGL((fhe_dev::galois_kernel<F, false>), grid, block, 0, h->stream, (V *)out0, (V *)out1, (V *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
+    return post_launch(h->stream, "galois_kernel");
+}
+static int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact) {
+    const uint32_t g_inv = galois_inverse(h, g);
+    if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return galois_word<decltype(f)>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact); });
+    if (compact) return fail(FHE_ERR_UNSUPPORTED, "compact polynomials exist on the word-sized classes only");
+    const size_t count = polys * h->n;
+    hipLaunchKernelGGL(fhe_dev::galois256_kernel, dim3(ew_grid(count), in1 ? 2 : 1), dim3(fhe_dev::GALOIS_T), 0, h->stream, (fhe_dev::u256 *)out0,
+                       (fhe_dev::u256 *)out1, (fhe_dev::u256 *)zero_out, (const fhe_dev::u256 *)in0, (const fhe_dev::u256 *)in1,
+                       (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, g_inv, count);
+    return post_launch(h->stream, "galois256_kernel");
+}
+extern "C" int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t galois_elt, uint32_t batch) {
+    int rc = check_call(h, batch, "automorphism"); if (rc) return rc;
+    if (!d_out || !d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: null argument");
+    if (d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: the permutation is out of place (out must differ from in)");
+    if ((rc = check_galois_element(h, galois_elt, "automorphism"))) return rc;
+    if ((rc = check_inputs(h, {d_in}, batch))) return rc;
+    return do_galois(h, d_out, nullptr, nullptr, d_in, nullptr, galois_elt, (size_t)batch * h->L, false);
+}
+// (c0, c1) -> (sigma(c0) + sum D(sigma(c1)) b, sum D(sigma(c1)) a): bit for bit fhe_ct_relinearize applied to (sigma(c0), 0, sigma(c1)).
+// Fused path (the LDS-resident word-sized sizes with packed keys, as plan_fused_ct_relin): the prologue writes sigma(c0), sigma(c1) and a zero
+// polynomial as compact polynomials into the three slices of d_ws2 that fhe_ct_multiply_relin uses, then ONE compact-operand key switch
+// (KS_FUSED) reads them -- HBM traffic 2 S in + 2 S out plus the compact round trip.  Elsewhere: sigma(c0) -> out0, zero -> out1 and
+// sigma(c1) -> d_ws2 as containers in one launch, then fhe_ct_relinearize.
+extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1, const void *d_c0,
+                                   const void *d_c1, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_apply_galois"); if (rc) return rc;
+    if (!gk || !d_out0 || !d_out1 || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: null argument");
+    if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: keys were imported for a different engine");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must be distinct");
+    for (const void *i : {d_c0, d_c1}) if (d_out0 == i || d_out1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must not alias inputs");
+    if ((rc = check_galois_element(h, galois_elt, "ct_apply_galois"))) return rc;
+    if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
+    const size_t polys = (size_t)batch * h->L;
+    if (plan_fused_ct_relin(h, gk->d_pkb != nullptr) && !h->env.no_fused_galois) {
+        const size_t cbytes = polys * h->n * residue_bytes(h);
+        if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
+        char *s0 = (char *)h->d_ws2, *s1 = s0 + cbytes, *zero = s1 + cbytes;      // sigma(c0): addend of c0'; sigma(c1): digit source; 0: addend of c1'
+        const LdsPlan P = plan_keyswitch(h, polys, gk->K, KS_FUSED, true);
+        if ((rc = ensure_plan(h, P))) return rc;
+        if ((rc = do_galois(h, s0, s1, zero, d_c0, d_c1, galois_elt, polys, true))) return rc;
+        return lds_launch(h, keyswitch_args(h, gk, P, d_out0, d_out1, s1, s0, zero, (uint32_t)polys, h->stream), "key switch (rotation)");
+    }
+    if ((rc = ensure_ws2(h, polys * h->n * 32))) return rc;
+    if ((rc = do_galois(h, d_out0, h->d_ws2, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
+    return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->d_ws2, batch);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// blind-rotation inner loop
+// ------------------------------------------------------------------------------------------------------
+static int monomial_compact(fhe_rns_ntt *h, void *out, const void *in, const uint32_t *shifts, size_t count) {   // (X^shift - 1) * p on compact polynomials
+    return with_word_field(h, [&](auto f) {
+        using F = decltype(f);
+        hipLaunchKernelGGL((fhe_dev::monomial_compact_kernel<F>), dim3(ew_grid(count)), dim3(256), 0, h->stream, (typename F::E *)out, (const typename F::E *)in, shifts,
+                           (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, count);
+        return post_launch(h->stream, "monomial_compact_kernel");
+    });
+}
+
+template <class F>
+static int monomial_lds(fhe_rns_ntt *h, void *out, const void *in, const uint32_t *shifts, uint32_t batch) {
+    using V = typename F::V16;
+    size_t halves = (size_t)batch * h->L * h->n * 2;
+    hipLaunchKernelGGL((fhe_dev::monomial_mul_sub_kernel<F>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)out, (const V *)in, shifts,
+                       (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, halves);
+    return post_launch(h->stream, "monomial_mul_sub_kernel");
+}
+extern "C" int fhe_rns_monomial_mul_sub(fhe_rns_ntt_t *h, void *d_out, const void *d_in, const uint32_t *d_shifts, uint32_t batch) {
+    int rc = check_call(h, batch, "monomial_mul_sub"); if (rc) return rc;
+    if (!d_out || !d_in || !d_shifts || d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "monomial_mul_sub: null or aliased argument");
+    if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return monomial_lds<decltype(f)>(h, d_out, d_in, d_shifts, batch); });
+    size_t count = (size_t)batch * h->L * h->n;
+    hipLaunchKernelGGL(fhe_dev::monomial_mul_sub256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out,
+                       (const fhe_dev::u256 *)d_in, d_shifts, (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, count);
+    return post_launch(h->stream, "monomial_mul_sub256_kernel");
+}
+// One step on the general composition (any width class): d = (X^a - 1) * acc, then two key switches accumulate into acc in place.
+static int blind_rotate_step_general(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rows_c0, const fhe_relin_keys_t *rows_c1, void *d_acc0, void *d_acc1,
+                                     const uint32_t *d_shifts, void *d_tmp0, void *d_tmp1, uint32_t batch) {
+    int rc;
+    if ((rc = fhe_rns_monomial_mul_sub(h, d_tmp0, d_acc0, d_shifts, batch))) return rc;       // d0 = (X^a - 1) * acc0
+    if ((rc = fhe_rns_monomial_mul_sub(h, d_tmp1, d_acc1, d_shifts, batch))) return rc;       // d1 = (X^a - 1) * acc1
+    if ((rc = fhe_ct_relinearize(h, rows_c0, d_acc0, d_acc1, d_tmp0, batch))) return rc;      // acc += sum D(d0) * rows_c0
+    return fhe_ct_relinearize(h, rows_c1, d_acc0, d_acc1, d_tmp1, batch);                     // acc += sum D(d1) * rows_c1
+}
+// One step as ONE launch (word-sized classes with packed rows): (out0, out1) = (in0, in1) + ExtProd((X^a - 1) * in, RGSW).
+// rot0, rot1: (X^a - 1) * (in0, in1), pre-rotated by the loop (compact), or nullptr
+static int blind_rotate_step_fused(fhe_rns_ntt_t *h, const LdsPlan &P, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1, void *out0, void *out1,
+                                   const void *in0, const void *in1, const uint32_t *d_shifts, uint32_t batch, bool in_compact, bool out_compact,
+                                   const void *rot0, const void *rot1) {
+    fhe_dev::LdsArgs A{fhe_dev::LDS_EXTPROD, P.form, out0, out1, nullptr, in0, in1, rot0, rot1, h->d_limbs, h->L, batch * h->L, h->stream};
+    A.kb = r0->d_pkb; A.ka = r0->d_pka; A.kb1 = r1->d_pkb; A.ka1 = r1->d_pka; A.K = r0->K; A.w = r0->decomp_bits; A.shifts = d_shifts;
+    A.in_compact = in_compact; A.out_compact = out_compact; A.ws = plan_ws(h, P);
+    return lds_launch(h, A, "ntt_extprod_kernel");
+}
+static int check_rows(const fhe_rns_ntt_t *h, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1) {
+    if (!r0 || !r1) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: null RGSW rows");
+    if (r0->owner != h || r1->owner != h) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: rows were imported for a different engine");
+    if (r0->decomp_bits != r1->decomp_bits || r0->K != r1->K) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: the two row sets use different digit widths");
+    return FHE_OK;
+}
+extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *rows_c0, const fhe_relin_keys_t *const *rows_c1, uint32_t steps,
+                                void *d_acc0, void *d_acc1, const uint32_t *d_shifts, void *d_tmp0, void *d_tmp1, uint32_t batch) {
+    int rc = check_call(h, batch, "blind_rotate"); if (rc) return rc;
+    if (!d_acc0 || !d_acc1 || !d_tmp0 || !d_tmp1 || !d_shifts || (steps && (!rows_c0 || !rows_c1))) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: null argument");
+    {   // the four buffers must be pairwise distinct
+        const void *bufs[4] = {d_acc0, d_acc1, d_tmp0, d_tmp1};
+        for (int x = 0; x < 4; x++) for (int y = x + 1; y < 4; y++)
+            if (bufs[x] == bufs[y]) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: accumulators and scratch must be distinct buffers");
+    }
+    if ((rc = check_inputs(h, {d_acc0, d_acc1}, batch))) return rc;
+    bool fused = h->width != FHE_WIDTH_256 && !h->env.no_fused_blind_rotate;
+    uint32_t kmax = 0;
+    for (uint32_t s = 0; s < steps; s++) {
+        if ((rc = check_rows(h, rows_c0[s], rows_c1[s]))) return rc;
+        fused = fused && rows_c0[s]->d_pkb && rows_c1[s]->d_pkb;
+        kmax = rows_c0[s]->K > kmax ? rows_c0[s]->K : kmax;
+    }
+    if (!fused) {
+        for (uint32_t s = 0; s < steps; s++)
+            if ((rc = blind_rotate_step_general(h, rows_c0[s], rows_c1[s], d_acc0, d_acc1, d_shifts + (size_t)s * batch, d_tmp0, d_tmp1, batch))) return rc;
+        return FHE_OK;
+    }
+    if (!steps) return FHE_OK;
+    const LdsPlan P = plan_extprod(h, batch * h->L, kmax);
+    if (P.compact) {
+        // The accumulator pair is compacted first (one streaming pass), every step reads compact input from a workspace ping-pong (4 compact
+        // polynomials; 2 more hold the pre-rotated pair of the current step), all but the last write compact output, the last one writes the
+        // caller's containers.  The caller's scratch pair is not touched.
+        const size_t cbytes = (size_t)batch * h->L * h->n * residue_bytes(h), count = (size_t)batch * h->L * h->n;
+        if ((rc = ensure_ws2(h, (P.form == fhe_dev::LDS_PAIRED ? 4 : 6) * cbytes))) return rc;
+        char *w0 = (char *)h->d_ws2;
+        char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
+        char *rot0 = w0 + 4 * cbytes, *rot1 = w0 + 5 * cbytes;       // (X^a - 1) * acc of the current step
+        if ((rc = ensure_plan(h, P))) return rc;
+        if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;
+        if ((rc = compact_poly(h, pp[1][1], d_acc1, count))) return rc;
+        for (uint32_t s = 0; s < steps; s++) {
+            const bool last = s + 1 == steps;
+            const void *i0 = pp[(s + 1) & 1][0], *i1 = pp[(s + 1) & 1][1];
+            void *o0 = last ? d_acc0 : pp[s & 1][0], *o1 = last ? d_acc1 : pp[s & 1][1];
+            const uint32_t *sh = d_shifts + (size_t)s * batch;
+            if (P.prerot && ((rc = monomial_compact(h, rot0, i0, sh, count)) || (rc = monomial_compact(h, rot1, i1, sh, count)))) return rc;
+            if ((rc = blind_rotate_step_fused(h, P, rows_c0[s], rows_c1[s], o0, o1, i0, i1, sh, batch, true, !last, P.prerot ? rot0 : nullptr,
+                                              P.prerot ? rot1 : nullptr))) return rc;
+        }
+        return FHE_OK;
+    }
+    // ping-pong between (acc0, acc1) and (tmp0, tmp1): one launch per step, 4*S bytes of HBM traffic per accumulator and step
+    void *cur0 = d_acc0, *cur1 = d_acc1, *nxt0 = d_tmp0, *nxt1 = d_tmp1;
+    for (uint32_t s = 0; s < steps; s++) {
+        if ((rc = blind_rotate_step_fused(h, P, rows_c0[s], rows_c1[s], nxt0, nxt1, cur0, cur1, d_shifts + (size_t)s * batch, batch, false, false, nullptr, nullptr))) return rc;
+        std::swap(cur0, nxt0); std::swap(cur1, nxt1);
+    }
+    if (cur0 != d_acc0) {   // odd number of steps: the result sits in the scratch pair
+        const size_t bytes = (size_t)batch * h->L * h->n * 32;
+        HIP_TRY(hipMemcpyAsync(d_acc0, cur0, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_acc1, cur1, bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return FHE_OK;
+}
+extern "C" int fhe_blind_rotate_step(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rows_c0, const fhe_relin_keys_t *rows_c1, void *d_acc0, void *d_acc1,
+                                     const uint32_t *d_shifts, void *d_tmp0, void *d_tmp1, uint32_t batch) {
+    return fhe_blind_rotate(h, &rows_c0, &rows_c1, 1, d_acc0, d_acc1, d_shifts, d_tmp0, d_tmp1, batch);
+}

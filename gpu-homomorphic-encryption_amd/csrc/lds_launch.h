@@ -11,7 +11,7 @@ enum LdsOp { LDS_FORWARD = 0, LDS_INVERSE = 1, LDS_MULTIPLY = 2, LDS_CT_MULTIPLY
              // the top stages (r0 = dst, a0 = src) and the sub-transforms of the 2^top blocks (r0 = dst, a0 = src, b0 = second operand)
              LDS_PASS_FWD = 6, LDS_PASS_INV = 7, LDS_SUB_FORWARD = 8, LDS_SUB_INVERSE = 9, LDS_SUB_MULTIPLY = 10 };
 
-// Which kernel form runs an op is decided on the host, once, by the planner of fhe_hip.hip (plan_*), which also says which library workspace
+// Which kernel form runs an op is decided on the host, once, by the planner of transforms.hip (plan_*), which also says which library workspace
 // the form needs; the instance launches exactly that form or returns false.  The predicates below say where a form exists.
 
 // the tensor product as one fused launch (LDS_ONE_LAUNCH / LDS_SQUARE); elsewhere the two-launch form (NTT(b0), NTT(b1) into the compact

@@ -1,7 +1,7 @@
 // ntt_field.hip.h -- field traits of the word-sized RNS primes on gfx950 (residue type, butterflies, products, range bookkeeping),
 // the per-limb constant record and the two memory helpers every kernel family shares (buffer-descriptor loads, lane-pair container
 // stores).  Included by ntt_lds.hip.h (LDS-resident transforms: one object per (field, log2 n)) and ntt_word.hip.h (streaming kernels,
-// compiled into fhe_hip.o), so that an edit to the transform kernels does not rebuild the host translation unit.
+// compiled into the host objects that launch them), so that an edit to the transform kernels does not rebuild the host objects.
 //   F32 : q < 2^30, 32-bit residues, Harvey lazy butterflies on Montgomery-form twiddles   (FHE_WIDTH_32)
 //   F52 : q < 2^43, residues held as exact integers in doubles, FMA butterflies            (FHE_WIDTH_52)
 //   F64 : q < 2^62, 64-bit residues, Harvey/Shoup integer butterflies                      (FHE_WIDTH_64)

@@ -11,7 +11,7 @@
 //   * EVERY twiddle the three transforms need (15 per non-uniform register group) is loaded into registers at the top of the kernel
 //     together with both operands: one memory round trip in all (the workgroup has 256 VGPRs per lane to itself).
 // Same tables, same HBM access shapes, same lazy butterflies and bit-identical results as ntt_multiply_kernel; the host uses it while
-// batch x limbs stays below the number of CUs (LDS_SMALL16: plan_multiply in fhe_hip.hip).  16-per-thread forms of the throughput kernels were
+// batch x limbs stays below the number of CUs (LDS_SMALL16: plan_multiply in transforms.hip).  16-per-thread forms of the throughput kernels were
 // measured in round 1 (scratch/experiments/ntt_lds16.hip.h: the extra exchange costs what the occupancy buys) -- this is the latency case.
 #pragma once
 #include "ntt_lds.hip.h"

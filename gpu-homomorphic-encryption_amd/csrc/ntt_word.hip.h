@@ -1,6 +1,6 @@
 // ntt_word.hip.h -- streaming (one pass over HBM, no transform) kernels on word-sized residues: element-wise ring operations, the
 // canonical-input scan, key-table packing, the general-path relinearisation pieces, RNS conversions (row N2) and the monomial
-// multiply of the blind-rotation general path.  Compiled into fhe_hip.o; the LDS-resident transform kernels are in ntt_lds.hip.h.
+// multiply of the blind-rotation general path.  Each kernel is instantiated by the one host source that launches it (engine.h); the LDS-resident transform kernels are in ntt_lds.hip.h.
 #pragma once
 #include "ntt_field.hip.h"
 

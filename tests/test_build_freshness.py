@@ -1,12 +1,14 @@
 """Build robustness (CPU): what makes the library stale, and what must not.
 
 * make's view: every header an object includes is a prerequisite of it -- editing ntt_wide.hip.h or the generated wide_asm.inc
-  re-compiles fhe_hip.o (the round-2 Makefile left a stale library behind), editing the LDS transform kernels re-compiles the
-  lds_inst objects and leaves fhe_hip.o alone.
+  re-compiles every host object that includes it (the round-2 Makefile left a stale library behind), editing the LDS transform
+  kernels re-compiles the lds_inst objects and leaves the host objects alone, editing a header one subsystem owns re-compiles
+  that subsystem's object only.
 * build.py's view: freshness is a content hash in lib/.build_stamp, so a copy of the tree with every mtime reset (the GPU box's
   snapshot) does not rebuild, and a one-byte edit does."""
 import importlib
 import os
+import re
 import shutil
 import subprocess
 
@@ -30,17 +32,42 @@ def built(pkg):
     return importlib.import_module(pkg.__name__ + ".build")
 
 
+HOST_OBJECTS = {"core.o", "literal.o", "sampling.o", "engine.o", "transforms.o", "keyswitch.o", "rns.o"}
+
+
+def _includers(header):
+    """Host objects whose source includes `header`, directly or through another header: read from the sources, not from make."""
+    def closure(path, seen):
+        with open(os.path.join(CSRC, path)) as f:
+            for inc in re.findall(r'^#include "([^"/]+)"', f.read(), re.M):
+                if inc not in seen:
+                    seen.add(inc)
+                    closure(inc, seen)
+        return seen
+    return {o for o in HOST_OBJECTS if header in closure(o[:-2] + ".hip", set())}
+
+
 @pytest.mark.parametrize("header", ["wide_asm.inc", "ntt_wide.hip.h", "ntt_word.hip.h", "ntt256.hip.h", "ntt_field.hip.h"])
 def test_editing_a_header_of_the_host_unit_rebuilds_it(built, header):
     plan = _make_plan(header)
-    assert "fhe_hip.o" in plan and "libfhe_hip.so" in plan, plan
+    users = _includers(header)
+    assert users and users <= set(plan) and "libfhe_hip.so" in plan, plan
+    assert HOST_OBJECTS & set(plan) == users, plan
 
 
 def test_editing_the_lds_kernels_rebuilds_every_instance_but_not_the_host_unit(built):
     plan = _make_plan("ntt_lds.hip.h")
-    assert "fhe_hip.o" not in plan and "libfhe_hip.so" in plan
+    assert not HOST_OBJECTS & set(plan) and "libfhe_hip.so" in plan
     assert sum(1 for o in plan if o.startswith("lds_F")) == 17, plan
-    assert "fhe_hip.o" in _make_plan("ntt_field.hip.h") and "lds_F32_13.o" in _make_plan("ntt_field.hip.h")
+    assert HOST_OBJECTS <= set(_make_plan("ntt_field.hip.h")) and "lds_F32_13.o" in _make_plan("ntt_field.hip.h")
+
+
+def test_editing_a_header_one_subsystem_owns_rebuilds_that_object_only(built):
+    for header, owner in [("galois.hip.h", "keyswitch.o"), ("sampling.hip.h", "sampling.o"), ("ntt256_rns.hip.h", "rns.o"),
+                          ("ntt256_literal.hip.h", "literal.o"), ("ntt256_keyswitch.hip.h", "keyswitch.o"), ("ntt256_transforms.hip.h", "transforms.o")]:
+        plan = _make_plan(header)
+        assert HOST_OBJECTS & set(plan) == {owner} and "libfhe_hip.so" in plan, (header, plan)
+        assert not any(o.startswith("lds_") for o in plan), (header, plan)
 
 
 def test_up_to_date_tree_has_nothing_to_do(built):
