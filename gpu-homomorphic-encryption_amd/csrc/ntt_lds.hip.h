@@ -176,12 +176,14 @@ __device__ __forceinline__ TW load_global(const TW *p) {
 // ---- register-resident butterfly stages -------------------------------------------------------------
 // Forward (Cooley-Tukey, merged psi twiddles): stage on index bit b uses twiddle tw[m + (i >> (b+1))], m = N >> (b+1).
 // Processes r-bits KHI down to KLO of pattern Pat.  Values stay in [0, 4q).
+// x...: one array, or several that are transformed under ONE modulus in lock step: each twiddle is loaded once and feeds one butterfly per array.
 // TWL: `tw` is an LDS copy in the permuted order (non-uniform patterns only).
 // SUB: the 2^LOGN coefficients are block number (pre - 2^k) of a larger transform of 2^(LOGN + k) coefficients whose top k stages
 // ran elsewhere (word_pass_kernel); the stage on local bit b then uses the big table at (pre << (LOGN-1-b)) + (i >> (b+1)), which for
 // pre = 1 is the whole-transform formula.
-template <class F, int LOGN, class Pat, int KHI, int KLO, bool TWL = false, bool SUB = false, bool GTW = true>
-__device__ __forceinline__ void fwd_stages(typename F::E (&x)[32], uint32_t tid, const typename F::TW *__restrict__ tw, const Limb<F> &P, uint32_t pre = 1) {
+// The arrays are a parameter pack and so come last; `pre` therefore has no default, and a whole transform passes 1u.
+template <class F, int LOGN, class Pat, int KHI, int KLO, bool TWL = false, bool SUB = false, bool GTW = true, class... E>
+__device__ __forceinline__ void fwd_stages(uint32_t tid, const typename F::TW *__restrict__ tw, const Limb<F> &P, uint32_t pre, E (&...x)[32]) {
     static_assert(!(TWL && Pat::TW_UNIFORM), "uniform stages read device memory");
     static_assert(!(TWL && SUB), "sub-transforms read their twiddles from device memory");
     const uint32_t base = TWL ? Pat::tw_thread(tid) : Pat::TW_UNIFORM ? 0u : Pat::base(tid);   // uniform -> scalar twiddle loads
@@ -196,14 +198,14 @@ __device__ __forceinline__ void fwd_stages(typename F::E (&x)[32], uint32_t tid,
             if constexpr (TWL) w = p[tw_slot_off<Pat>(r, k)];
             else if constexpr (GTW) w = load_global(p + (Pat::off(r) >> (b + 1)));
             else w = p[Pat::off(r) >> (b + 1)];
-            F::fwd_bfly(x[r], x[r | (1 << k)], w, P);
+            (F::fwd_bfly(x[r], x[r | (1 << k)], w, P), ...);
         }
     }
 }
 // Inverse (Gentleman-Sande): stage on index bit b uses itw[m + (i >> (b+1))].  Processes r-bits KLO up to KHI.
 // Values stay in [0, 2q).
-template <class F, int LOGN, class Pat, int KLO, int KHI, bool TWL = false, bool SUB = false, bool GTW = true>
-__device__ __forceinline__ void inv_stages(typename F::E (&x)[32], uint32_t tid, const typename F::TW *__restrict__ itw, const Limb<F> &P, uint32_t pre = 1) {
+template <class F, int LOGN, class Pat, int KLO, int KHI, bool TWL = false, bool SUB = false, bool GTW = true, class... E>
+__device__ __forceinline__ void inv_stages(uint32_t tid, const typename F::TW *__restrict__ itw, const Limb<F> &P, uint32_t pre, E (&...x)[32]) {
     static_assert(!(TWL && Pat::TW_UNIFORM), "uniform stages read device memory");
     static_assert(!(TWL && SUB), "sub-transforms read their twiddles from device memory");
     const uint32_t base = TWL ? Pat::tw_thread(tid) : Pat::TW_UNIFORM ? 0u : Pat::base(tid);
@@ -218,7 +220,7 @@ __device__ __forceinline__ void inv_stages(typename F::E (&x)[32], uint32_t tid,
             if constexpr (TWL) w = p[tw_slot_off<Pat>(r, k)];
             else if constexpr (GTW) w = load_global(p + (Pat::off(r) >> (b + 1)));
             else w = p[Pat::off(r) >> (b + 1)];
-            F::inv_bfly(x[r], x[r | (1 << k)], w, P);
+            (F::inv_bfly(x[r], x[r | (1 << k)], w, P), ...);
         }
     }
 }
@@ -321,39 +323,22 @@ __device__ __forceinline__ void fwd_core(typename F::E (&x)[32], typename F::E *
                                          const typename F::TW *twl = nullptr, uint32_t pre = 1) {
     using C = NttCfg<LOGN>;
     const typename F::TW *t2 = TWL ? twl : P.tw;
-    fwd_stages<F, LOGN, PatA<LOGN>, 4, 0, false, SUB, GTW>(x, tid, P.tw, P, pre);
+    fwd_stages<F, LOGN, PatA<LOGN>, 4, 0, false, SUB, GTW>(tid, P.tw, P, pre, x);
     if constexpr (PRESYNC) __syncthreads();
     lds_put<PatA<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatM<LOGN>>(lds, tid, x);
-    fwd_stages<F, LOGN, PatM<LOGN>, 4, 0, TWL, SUB, GTW>(x, tid, t2, P, pre);
+    fwd_stages<F, LOGN, PatM<LOGN>, 4, 0, TWL, SUB, GTW>(tid, t2, P, pre, x);
     lds_put<PatM<LOGN>>(lds, tid, x);          // same slots this thread just read: no barrier needed before
     __syncthreads();
     lds_get<PatZ<LOGN>>(lds, tid, x);
-    fwd_stages<F, LOGN, PatZ<LOGN>, C::REM - 1, 0, TWL, SUB, GTW>(x, tid, t2, P, pre);
+    fwd_stages<F, LOGN, PatZ<LOGN>, C::REM - 1, 0, TWL, SUB, GTW>(tid, t2, P, pre, x);
 }
-// ---- two forward transforms under ONE modulus at once ------------------------------------------------------------------
+// ---- two transforms under ONE modulus at once (fwd_core2 / inv_core2 below) ----------------------------------------------
 // The key-switch and external-product kernels transform many digit polynomials under the same modulus.  Doing two of them
-// in lock step shares every twiddle load (one load feeds two butterflies), every barrier and every LDS wait between the two,
-// and doubles the independent work in flight per wave -- for the same register budget as holding the undecomposed limb
-// beside one digit polynomial.  x0 / x1 travel through ONE exchange image of element pairs (lds_put2 / lds_get2).
-template <class F, int LOGN, class Pat, int KHI, int KLO>
-__device__ __forceinline__ void fwd_stages2(typename F::E (&x0)[32], typename F::E (&x1)[32], uint32_t tid, const typename F::TW *__restrict__ tw,
-                                            const Limb<F> &P) {
-    const uint32_t base = Pat::TW_UNIFORM ? 0u : Pat::base(tid);
-#pragma unroll
-    for (int k = KHI; k >= KLO; k--) {
-        const int b = Pat::BIT0 + k;
-        const typename F::TW *p = tw + ((1u << (LOGN - 1 - b)) + (base >> (b + 1)));
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
-            if (r & (1 << k)) continue;
-            const typename F::TW w = load_global(p + (Pat::off(r) >> (b + 1)));
-            F::fwd_bfly(x0[r], x0[r | (1 << k)], w, P);
-            F::fwd_bfly(x1[r], x1[r | (1 << k)], w, P);
-        }
-    }
-}
+// in lock step shares every twiddle load (one load feeds two butterflies: fwd_stages / inv_stages / stages_w with two arrays), every
+// barrier and every LDS wait between the two, and doubles the independent work in flight per wave -- for the same register budget as
+// holding the undecomposed limb beside one digit polynomial.  x0 / x1 travel through ONE exchange image of element pairs (lds_put2 / lds_get2).
 // ---- twiddles issued one exchange ahead (paired transforms) --------------------------------------------------------------------
 // A wave of these kernels waits on vector-memory loads 0.44 of its lifetime (rocprofv3 SQ_WAIT_INST_ANY, round 3) although it issues only
 // ~440 of them: at two waves per SIMD every load that is consumed right after it is issued exposes its whole L2 latency, and the
@@ -373,51 +358,20 @@ __device__ __forceinline__ void preload_twiddles(typename F::TW (&w)[31], uint32
         for (int j = 0; j < (16 >> k); j++) w[(16 >> k) - 1 + j] = load_global(p + j);
     }
 }
-template <class F, int KHI, int KLO>
-__device__ __forceinline__ void fwd_stages2_pre(typename F::E (&x0)[32], typename F::E (&x1)[32], const typename F::TW (&w)[31], const Limb<F> &P) {
+// The stages on r-bits K0, .., K1 in the order they run (FWD: descending, inverse: ascending) with preloaded twiddles, on one array or on
+// several in lock step.  NW = 31 twiddles for arrays of R = 32 (preload_twiddles), 15 for 16 (preload16, ntt_lds_small.hip.h): slot of
+// stage k, twiddle j = r >> (k+1): (R / 2 >> k) - 1 + j.
+template <class F, bool FWD, int K0, int K1, int NW, int R, class... E>
+__device__ __forceinline__ void stages_w(const typename F::TW (&w)[NW], const Limb<F> &P, E (&...x)[R]) {
+    static_assert(NW == R - 1, "one twiddle per butterfly position of the group");
 #pragma unroll
-    for (int k = KHI; k >= KLO; k--) {
+    for (int k = K0; FWD ? k >= K1 : k <= K1; k += FWD ? -1 : 1) {
 #pragma unroll
-        for (int r = 0; r < 32; r++) {
+        for (int r = 0; r < R; r++) {
             if (r & (1 << k)) continue;
-            const typename F::TW t = w[(16 >> k) - 1 + (r >> (k + 1))];
-            F::fwd_bfly(x0[r], x0[r | (1 << k)], t, P);
-            F::fwd_bfly(x1[r], x1[r | (1 << k)], t, P);
-        }
-    }
-}
-template <class F, int KLO, int KHI>
-__device__ __forceinline__ void inv_stages2_pre(typename F::E (&x0)[32], typename F::E (&x1)[32], const typename F::TW (&w)[31], const Limb<F> &P) {
-#pragma unroll
-    for (int k = KLO; k <= KHI; k++) {
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
-            if (r & (1 << k)) continue;
-            const typename F::TW t = w[(16 >> k) - 1 + (r >> (k + 1))];
-            F::inv_bfly(x0[r], x0[r | (1 << k)], t, P);
-            F::inv_bfly(x1[r], x1[r | (1 << k)], t, P);
-        }
-    }
-}
-template <class F, int KHI, int KLO>
-__device__ __forceinline__ void fwd_stages_pre(typename F::E (&x)[32], const typename F::TW (&w)[31], const Limb<F> &P) {
-#pragma unroll
-    for (int k = KHI; k >= KLO; k--) {
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
-            if (r & (1 << k)) continue;
-            F::fwd_bfly(x[r], x[r | (1 << k)], w[(16 >> k) - 1 + (r >> (k + 1))], P);
-        }
-    }
-}
-template <class F, int KLO, int KHI>
-__device__ __forceinline__ void inv_stages_pre(typename F::E (&x)[32], const typename F::TW (&w)[31], const Limb<F> &P) {
-#pragma unroll
-    for (int k = KLO; k <= KHI; k++) {
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
-            if (r & (1 << k)) continue;
-            F::inv_bfly(x[r], x[r | (1 << k)], w[(16 >> k) - 1 + (r >> (k + 1))], P);
+            const typename F::TW t = w[(R / 2 >> k) - 1 + (r >> (k + 1))];
+            if constexpr (FWD) (F::fwd_bfly(x[r], x[r | (1 << k)], t, P), ...);
+            else (F::inv_bfly(x[r], x[r | (1 << k)], t, P), ...);
         }
     }
 }
@@ -428,16 +382,16 @@ __device__ __forceinline__ void fwd_core_pre(typename F::E (&x)[32], typename F:
     using C = NttCfg<LOGN>;
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatM<LOGN>, 4, 0>(w, tid, P.tw);
-    fwd_stages<F, LOGN, PatA<LOGN>, 4, 0>(x, tid, P.tw, P);
+    fwd_stages<F, LOGN, PatA<LOGN>, 4, 0>(tid, P.tw, P, /*pre=*/1u, x);
     lds_put<PatA<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatM<LOGN>>(lds, tid, x);
-    fwd_stages_pre<F, 4, 0>(x, w, P);
+    stages_w<F, true, 4, 0>(w, P, x);
     preload_twiddles<F, LOGN, PatZ<LOGN>, C::REM - 1, 0>(w, tid, P.tw);
     lds_put<PatM<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatZ<LOGN>>(lds, tid, x);
-    fwd_stages_pre<F, C::REM - 1, 0>(x, w, P);
+    stages_w<F, true, C::REM - 1, 0>(w, P, x);
 }
 template <class F, int LOGN>
 __device__ __forceinline__ void inv_core_pre(typename F::E (&x)[32], typename F::E *lds, uint32_t tid, const Limb<F> &P,
@@ -445,18 +399,18 @@ __device__ __forceinline__ void inv_core_pre(typename F::E (&x)[32], typename F:
     using C = NttCfg<LOGN>;
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatZ<LOGN>, 4, 0>(w, tid, P.itw);
-    inv_stages_pre<F, 0, 4>(x, w, P);
+    stages_w<F, false, 0, 4>(w, P, x);
     F::regroup(x, P.q, P.qinv);
     preload_twiddles<F, LOGN, PatY<LOGN>, 4, 0>(w, tid, P.itw);
     lds_put<PatZ<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatY<LOGN>>(lds, tid, x);
-    inv_stages_pre<F, 0, 4>(x, w, P);
+    stages_w<F, false, 0, 4>(w, P, x);
     F::regroup(x, P.q, P.qinv);
     lds_put<PatY<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatA<LOGN>>(lds, tid, x);
-    inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 3>(x, tid, P.itw, P);
+    inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 3>(tid, P.itw, P, /*pre=*/1u, x);
     inv_last_stage<F>(x, P.q, P.q2, ninv, ninv_s, ninvw, ninvw_s);
 }
 // PRESYNC as in fwd_core: the barrier that ends the previous transforms' use of the exchange buffers sits after the first group.
@@ -466,17 +420,17 @@ __device__ __forceinline__ void fwd_core2(typename F::E (&x0)[32], typename F::E
     using C = NttCfg<LOGN>;
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatM<LOGN>, 4, 0>(w, tid, P.tw);          // in flight under the first register group and the first exchange
-    fwd_stages2<F, LOGN, PatA<LOGN>, 4, 0>(x0, x1, tid, P.tw, P);
+    fwd_stages<F, LOGN, PatA<LOGN>, 4, 0>(tid, P.tw, P, /*pre=*/1u, x0, x1);
     if constexpr (PRESYNC) __syncthreads();
     lds_put2<PatA<LOGN>>(lds, tid, x0, x1);
     __syncthreads();
     lds_get2<PatM<LOGN>>(lds, tid, x0, x1);
-    fwd_stages2_pre<F, 4, 0>(x0, x1, w, P);
+    stages_w<F, true, 4, 0>(w, P, x0, x1);
     preload_twiddles<F, LOGN, PatZ<LOGN>, C::REM - 1, 0>(w, tid, P.tw);  // in flight under the second exchange
     lds_put2<PatM<LOGN>>(lds, tid, x0, x1);       // same slots this thread just read: no barrier needed before
     __syncthreads();
     lds_get2<PatZ<LOGN>>(lds, tid, x0, x1);
-    fwd_stages2_pre<F, C::REM - 1, 0>(x0, x1, w, P);
+    stages_w<F, true, C::REM - 1, 0>(w, P, x0, x1);
 }
 
 // NTT values in pattern Z, in [0, 2q)  ->  coefficients in pattern A, in [0, 2q), scaled by the (ninv..) constants
@@ -486,64 +440,47 @@ __device__ __forceinline__ void inv_core(typename F::E (&x)[32], typename F::E *
                                          const typename F::TW *twl = nullptr, uint32_t pre = 1) {
     using C = NttCfg<LOGN>;
     const typename F::TW *t2 = TWL ? twl : P.itw;
-    inv_stages<F, LOGN, PatZ<LOGN>, 0, 4, TWL, SUB, GTW>(x, tid, t2, P, pre);
+    inv_stages<F, LOGN, PatZ<LOGN>, 0, 4, TWL, SUB, GTW>(tid, t2, P, pre, x);
     F::regroup(x, P.q, P.qinv);
     if constexpr (PRESYNC) __syncthreads();
     lds_put<PatZ<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatY<LOGN>>(lds, tid, x);
-    inv_stages<F, LOGN, PatY<LOGN>, 0, 4, TWL, SUB, GTW>(x, tid, t2, P, pre);
+    inv_stages<F, LOGN, PatY<LOGN>, 0, 4, TWL, SUB, GTW>(tid, t2, P, pre, x);
     F::regroup(x, P.q, P.qinv);
     lds_put<PatY<LOGN>>(lds, tid, x);
     __syncthreads();
     lds_get<PatA<LOGN>>(lds, tid, x);
     if constexpr (SUB) {   // a block of a larger transform: bit LOGN-1 is an ordinary stage, the scaling belongs to the last pass
-        inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 4, false, true, GTW>(x, tid, P.itw, P, pre);
+        inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 4, false, true, GTW>(tid, P.itw, P, pre, x);
         F::regroup(x, P.q, P.qinv);
     } else {
         // index bits [10, LOGN-1) <-> r-bits [5-REM, 4) ; bit LOGN-1 <-> r-bit 4 is the scaled last stage
-        inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 3, false, false, GTW>(x, tid, P.itw, P);
+        inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 3, false, false, GTW>(tid, P.itw, P, /*pre=*/1u, x);
         inv_last_stage<F>(x, P.q, P.q2, ninv, ninv_s, ninvw, ninvw_s);
     }
 }
 
 // two inverse transforms in lock step (see fwd_core2)
-template <class F, int LOGN, class Pat, int KLO, int KHI>
-__device__ __forceinline__ void inv_stages2(typename F::E (&x0)[32], typename F::E (&x1)[32], uint32_t tid, const typename F::TW *__restrict__ itw,
-                                            const Limb<F> &P) {
-    const uint32_t base = Pat::TW_UNIFORM ? 0u : Pat::base(tid);
-#pragma unroll
-    for (int k = KLO; k <= KHI; k++) {
-        const int b = Pat::BIT0 + k;
-        const typename F::TW *p = itw + ((1u << (LOGN - 1 - b)) + (base >> (b + 1)));
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
-            if (r & (1 << k)) continue;
-            const typename F::TW w = load_global(p + (Pat::off(r) >> (b + 1)));
-            F::inv_bfly(x0[r], x0[r | (1 << k)], w, P);
-            F::inv_bfly(x1[r], x1[r | (1 << k)], w, P);
-        }
-    }
-}
 template <class F, int LOGN, bool PRESYNC = false>
 __device__ __forceinline__ void inv_core2(typename F::E (&x0)[32], typename F::E (&x1)[32], typename F::E *lds, uint32_t tid,
                                           const Limb<F> &P, typename F::E ninv, typename F::E ninv_s, typename F::E ninvw, typename F::E ninvw_s) {
     using C = NttCfg<LOGN>;
     typename F::TW w[31];
     preload_twiddles<F, LOGN, PatZ<LOGN>, 4, 0>(w, tid, P.itw);          // needed at once (issued together: one latency, not five)
-    inv_stages2_pre<F, 0, 4>(x0, x1, w, P);
+    stages_w<F, false, 0, 4>(w, P, x0, x1);
     F::regroup(x0, P.q, P.qinv); F::regroup(x1, P.q, P.qinv);
     preload_twiddles<F, LOGN, PatY<LOGN>, 4, 0>(w, tid, P.itw);          // in flight under the first exchange
     if constexpr (PRESYNC) __syncthreads();
     lds_put2<PatZ<LOGN>>(lds, tid, x0, x1);
     __syncthreads();
     lds_get2<PatY<LOGN>>(lds, tid, x0, x1);
-    inv_stages2_pre<F, 0, 4>(x0, x1, w, P);
+    stages_w<F, false, 0, 4>(w, P, x0, x1);
     F::regroup(x0, P.q, P.qinv); F::regroup(x1, P.q, P.qinv);
     lds_put2<PatY<LOGN>>(lds, tid, x0, x1);
     __syncthreads();
     lds_get2<PatA<LOGN>>(lds, tid, x0, x1);
-    inv_stages2<F, LOGN, PatA<LOGN>, 5 - C::REM, 3>(x0, x1, tid, P.itw, P);
+    inv_stages<F, LOGN, PatA<LOGN>, 5 - C::REM, 3>(tid, P.itw, P, /*pre=*/1u, x0, x1);
     inv_last_stage<F>(x0, P.q, P.q2, ninv, ninv_s, ninvw, ninvw_s);
     inv_last_stage<F>(x1, P.q, P.q2, ninv, ninv_s, ninvw, ninvw_s);
 }
@@ -839,7 +776,7 @@ __device__ __forceinline__ void ct_store(char *__restrict__ c, size_t p, typenam
         store_from_lds_rolled<F, LOGN>(c + p * (C::N * 32), lds, tid);
     }
 }
-template <class F, int LOGN, int MINW = 1, bool COMPACT_OUT = false, bool EARLY = false>
+template <class F, int LOGN, int MINW = 1, bool COMPACT_OUT = false>
 __global__ void __launch_bounds__(NttCfg<LOGN>::T, MINW)
 ntt_ct_a_kernel(char *__restrict__ c0, char *__restrict__ c1, char *__restrict__ c2, const char *__restrict__ a0, const char *__restrict__ a1,
                 const typename F::E *__restrict__ w0, const typename F::E *__restrict__ w1, const Limb<F> *__restrict__ limbs, uint32_t L) {
@@ -860,14 +797,13 @@ ntt_ct_a_kernel(char *__restrict__ c0, char *__restrict__ c1, char *__restrict__
     load_poly_buf<F, LOGN, true>(B0, tid, Y);
 #pragma unroll
     for (int r = 0; r < 32; r++) { X[r] = F::canon_fwd(X[r], P.q, P.q2, P.qinv); T[r] = F::pw_mul(X[r], Y[r], P.q, P.qinv); }
-    if constexpr (EARLY) load_poly_buf<F, LOGN, true>(B1, tid, Y);     // in flight under the inverse transform of c0 (a third live array)
-    else CT_FENCE();
+    CT_FENCE();
     inv_core<F, LOGN>(T, lds, tid, P, P.ninv_r, P.ninv_r_s, P.ninvw_r, P.ninvw_r_s);
 #pragma unroll
     for (int r = 0; r < 32; r++) T[r] = F::canon_inv(T[r], P.q);
     ct_store<F, LOGN, COMPACT_OUT>(c0, p, lds, tid, T);
     CT_FENCE();
-    if constexpr (!EARLY) load_poly_buf<F, LOGN, true>(B1, tid, Y);
+    load_poly_buf<F, LOGN, true>(B1, tid, Y);
 #pragma unroll
     for (int r = 0; r < 32; r++) T[r] = F::pw_mul(X[r], Y[r], P.q, P.qinv);          // A0 . B1
     CT_FENCE();
@@ -878,14 +814,13 @@ ntt_ct_a_kernel(char *__restrict__ c0, char *__restrict__ c1, char *__restrict__
     load_poly_buf<F, LOGN, true>(B0, tid, Y);
 #pragma unroll
     for (int r = 0; r < 32; r++) { X[r] = F::canon_fwd(X[r], P.q, P.q2, P.qinv); T[r] = F::pw_add(T[r], F::pw_mul(X[r], Y[r], P.q, P.qinv), P.q, P.q2); }
-    if constexpr (EARLY) load_poly_buf<F, LOGN, true>(B1, tid, Y);
-    else CT_FENCE();
+    CT_FENCE();
     inv_core<F, LOGN>(T, lds, tid, P, P.ninv_r, P.ninv_r_s, P.ninvw_r, P.ninvw_r_s);
 #pragma unroll
     for (int r = 0; r < 32; r++) T[r] = F::canon_inv(T[r], P.q);
     ct_store<F, LOGN, COMPACT_OUT>(c1, p, lds, tid, T);
     CT_FENCE();
-    if constexpr (!EARLY) load_poly_buf<F, LOGN, true>(B1, tid, Y);
+    load_poly_buf<F, LOGN, true>(B1, tid, Y);
 #pragma unroll
     for (int r = 0; r < 32; r++) T[r] = F::pw_mul(X[r], Y[r], P.q, P.qinv);          // A1 . B1
     CT_FENCE();
@@ -996,6 +931,19 @@ ntt_ct_multiply_kernel(char *__restrict__ c0, char *__restrict__ c1, char *__res
     }
 }
 
+// XCD-aware workgroup -> (ciphertext b, unit u) map of the key-switch and external-product kernels; LH = units per ciphertext (its limbs,
+// or limb x key half for the SPLIT forms): workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 names the L2 a workgroup
+// shares), and the workgroups of one ciphertext all re-read the same c2, so they are given block indices that are congruent mod 8 and
+// close together: the re-reads then hit one XCD's L2 instead of crossing the fabric.  Placement only changes speed, never results.
+struct BlockMap { uint32_t b, u; };
+__device__ __forceinline__ BlockMap block_map(uint32_t LH) {
+    const uint32_t bid = blockIdx.x, full = (gridDim.x / (8 * LH)) * (8 * LH);
+    uint32_t b, u;
+    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / LH); u = s % LH; }
+    else { b = bid / LH; u = bid % LH; }
+    return {b, u};
+}
+
 // ---- fused key switching (relinearisation): packed key tables are built by pack_keys_kernel (ntt_word.hip.h) --------------------
 // One workgroup per (ciphertext b, limb i): for every limb j of c2 and every digit k, the digit polynomial is formed in
 // registers, transformed under q_i, multiplied with both key halves and accumulated in the NTT domain; two inverse
@@ -1020,16 +968,9 @@ ntt_keyswitch_kernel(char *c0, char *c1, const char *__restrict__ c2, const char
     static_assert(!(TWL && SPLIT), "LDS twiddles are wired into the one-workgroup-per-limb form only");
     __shared__ E lds[C::LDS_ELEMS];
     __shared__ typename F::TW twl[TWL ? C::N : 1];
-    // XCD-aware workgroup -> (ciphertext, limb[, half]) map: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8
-    // names the L2 a workgroup shares), and the workgroups of one ciphertext all re-read the same c2, so they are given block
-    // indices that are congruent mod 8 and close together: the re-reads then hit one XCD's L2 instead of crossing the
-    // fabric.  Placement only changes speed, never results.
     constexpr uint32_t H = SPLIT ? 2 : 1;
-    const uint32_t LH = L * H;
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * LH)) * (8 * LH);
-    uint32_t b, u;
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / LH); u = s % LH; }
-    else { b = bid / LH; u = bid % LH; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, u] = block_map(L * H);                 // (ciphertext, limb[, half])
     const uint32_t i = u / H, half = u % H;
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
@@ -1127,10 +1068,8 @@ ntt_keyswitch3_kernel(char *c0, char *c1, const char *__restrict__ c2, const cha
     constexpr int VPL = 16 / sizeof(E), NCH = 32 / VPL;
     typedef E VecE __attribute__((ext_vector_type(VPL)));
     __shared__ E lds[C::LDS_ELEMS];
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * L)) * (8 * L);
-    uint32_t b, i;
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / L); i = s % L; }
-    else { b = bid / L; i = bid % L; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, i] = block_map(L);
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
     E acc0[32], acc1[32], d[32];
@@ -1243,11 +1182,8 @@ ntt_extprod_kernel(char *__restrict__ out0, char *__restrict__ out1, const char 
     __shared__ E lds[C::LDS_ELEMS];
     __shared__ typename F::TW twl[TWL ? C::N : 1];
     constexpr uint32_t H = SPLIT ? 2 : 1;
-    const uint32_t LH = L * H;
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * LH)) * (8 * LH);
-    uint32_t b, u;
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / LH); u = s % LH; }
-    else { b = bid / LH; u = bid % LH; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, u] = block_map(L * H);                 // (ciphertext, limb[, half])
     const uint32_t i = u / H, half = u % H;
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
@@ -1355,10 +1291,8 @@ ntt_extprod3_kernel(char *__restrict__ out0, char *__restrict__ out1, const char
     constexpr size_t IN_POLY = C::N * (IN_COMPACT ? sizeof(E) : 32);        // bytes of one input polynomial
     typedef E VecE __attribute__((ext_vector_type(VPL)));
     __shared__ E lds[C::LDS_ELEMS];
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * L)) * (8 * L);
-    uint32_t b, i;
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / L); i = s % L; }
-    else { b = bid / L; i = bid % L; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, i] = block_map(L);
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
     const uint32_t a = shifts[b] & (2 * C::N - 1);
@@ -1535,10 +1469,8 @@ ntt_keyswitch2_kernel(char *c0, char *c1, const char *__restrict__ c2, const cha
     using C = NttCfg<LOGN>;
     using E = typename F::E;
     __shared__ E lds[2 * C::LDS_ELEMS];
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * L)) * (8 * L);
-    uint32_t b, i;                                        // XCD-aware map, as in ntt_keyswitch_kernel
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / L); i = s % L; }
-    else { b = bid / L; i = bid % L; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, i] = block_map(L);
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
     const TableBuf C2(c2 + (size_t)b * L * (C::N * (COMPACT ? sizeof(E) : 32)));   // descriptor based at the first limb polynomial of this ciphertext's c2
@@ -1598,10 +1530,8 @@ ntt_extprod2_kernel(char *__restrict__ out0, char *__restrict__ out1, const char
     using C = NttCfg<LOGN>;
     using E = typename F::E;
     __shared__ E lds[2 * C::LDS_ELEMS];
-    const uint32_t tid = threadIdx.x, bid = blockIdx.x, full = (gridDim.x / (8 * L)) * (8 * L);
-    uint32_t b, i;
-    if (bid < full) { const uint32_t s = bid >> 3; b = (bid & 7) + 8 * (s / L); i = s % L; }
-    else { b = bid / L; i = bid % L; }
+    const uint32_t tid = threadIdx.x;
+    const auto [b, i] = block_map(L);
     const uint32_t p = b * L + i;
     const Limb<F> P = limbs[i];
     const uint32_t a = shifts[b] & (2 * C::N - 1);

@@ -87,57 +87,7 @@ __device__ __forceinline__ void preload16_uniform(typename F::TW (&w)[15], const
         for (int j = 0; j < (8 >> k); j++) w[(8 >> k) - 1 + j] = load_global(p + j);
     }
 }
-template <class F, int KHI, int KLO>
-__device__ __forceinline__ void fwd16_pre(typename F::E (&x)[16], const typename F::TW (&w)[15], const Limb<F> &P) {
-#pragma unroll
-    for (int k = KHI; k >= KLO; k--) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            if (r & (1 << k)) continue;
-            F::fwd_bfly(x[r], x[r | (1 << k)], w[(8 >> k) - 1 + (r >> (k + 1))], P);
-        }
-    }
-}
-template <class F, int KLO, int KHI>
-__device__ __forceinline__ void inv16_pre(typename F::E (&x)[16], const typename F::TW (&w)[15], const Limb<F> &P) {
-#pragma unroll
-    for (int k = KLO; k <= KHI; k++) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            if (r & (1 << k)) continue;
-            F::inv_bfly(x[r], x[r | (1 << k)], w[(8 >> k) - 1 + (r >> (k + 1))], P);
-        }
-    }
-}
-// stages with wave-uniform twiddles (pattern A): scalar loads where they are used
-template <class F, int LOGN, int KHI, int KLO>
-__device__ __forceinline__ void fwd16_uniform(typename F::E (&x)[16], const typename F::TW *__restrict__ tw, const Limb<F> &P) {
-    using Pat = P16A<LOGN>;
-#pragma unroll
-    for (int k = KHI; k >= KLO; k--) {
-        const int b = Pat::BIT0 + k;
-        const typename F::TW *p = tw + (1u << (LOGN - 1 - b));
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            if (r & (1 << k)) continue;
-            F::fwd_bfly(x[r], x[r | (1 << k)], load_global(p + (Pat::off(r) >> (b + 1))), P);
-        }
-    }
-}
-template <class F, int LOGN, int KLO, int KHI>
-__device__ __forceinline__ void inv16_uniform(typename F::E (&x)[16], const typename F::TW *__restrict__ itw, const Limb<F> &P) {
-    using Pat = P16A<LOGN>;
-#pragma unroll
-    for (int k = KLO; k <= KHI; k++) {
-        const int b = Pat::BIT0 + k;
-        const typename F::TW *p = itw + (1u << (LOGN - 1 - b));
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            if (r & (1 << k)) continue;
-            F::inv_bfly(x[r], x[r | (1 << k)], load_global(p + (Pat::off(r) >> (b + 1))), P);
-        }
-    }
-}
+// (the butterfly stages on these registers: stages_w of ntt_lds.hip.h, 15 twiddles for arrays of 16)
 template <class F>
 __device__ __forceinline__ void regroup16(typename F::E (&x)[16], typename F::E q, typename F::E qinv) {
 #pragma unroll
@@ -183,43 +133,43 @@ struct Twiddles16 {
 template <class F, int LOGN>
 __device__ __forceinline__ void fwd_core16(typename F::E (&x)[16], typename F::E *lds, uint32_t tid, const Limb<F> &P, const Twiddles16<F, LOGN> &W) {
     using C = Cfg16<LOGN>;
-    fwd16_pre<F, 3, 0>(x, W.fa, P);
+    stages_w<F, true, 3, 0>(W.fa, P, x);
     put16<P16A<LOGN>>(lds, tid, x);
     __syncthreads();
     using M1 = P16Mid<LOGN, LOGN - 8>;
     get16<M1>(lds, tid, x);
-    fwd16_pre<F, 3, 0>(x, W.f1, P);
+    stages_w<F, true, 3, 0>(W.f1, P, x);
     put16<M1>(lds, tid, x);                          // the slots this thread just read
     __syncthreads();
     if constexpr (C::NG == 4) {
         using M2 = P16Mid<LOGN, LOGN - 12>;
         get16<M2>(lds, tid, x);
-        fwd16_pre<F, 3, 0>(x, W.f2, P);
+        stages_w<F, true, 3, 0>(W.f2, P, x);
         put16<M2>(lds, tid, x);
         __syncthreads();
     }
     get16<P16Z<LOGN>>(lds, tid, x);
-    fwd16_pre<F, C::REM - 1, 0>(x, W.fz, P);
+    stages_w<F, true, C::REM - 1, 0>(W.fz, P, x);
 }
 // NTT values in pattern Z -> coefficients in pattern A, scaled by the (ninv..) constants
 template <class F, int LOGN, bool SUB = false>
 __device__ __forceinline__ void inv_core16(typename F::E (&x)[16], typename F::E *lds, uint32_t tid, const Limb<F> &P, const Twiddles16<F, LOGN> &W,
                                            typename F::E ninv, typename F::E ninv_s, typename F::E ninvw, typename F::E ninvw_s) {
     using C = Cfg16<LOGN>;
-    inv16_pre<F, 0, 3>(x, W.iz, P);
+    stages_w<F, false, 0, 3>(W.iz, P, x);
     regroup16<F>(x, P.q, P.qinv);
     put16<P16Z<LOGN>>(lds, tid, x);
     __syncthreads();
     using Y1 = P16Mid<LOGN, 4>;
     get16<Y1>(lds, tid, x);
-    inv16_pre<F, 0, 3>(x, W.i1, P);
+    stages_w<F, false, 0, 3>(W.i1, P, x);
     regroup16<F>(x, P.q, P.qinv);
     put16<Y1>(lds, tid, x);
     __syncthreads();
     if constexpr (C::NG == 4) {
         using Y2 = P16Mid<LOGN, 8>;
         get16<Y2>(lds, tid, x);
-        inv16_pre<F, 0, 3>(x, W.i2, P);
+        stages_w<F, false, 0, 3>(W.i2, P, x);
         regroup16<F>(x, P.q, P.qinv);
         put16<Y2>(lds, tid, x);
         __syncthreads();
@@ -227,10 +177,10 @@ __device__ __forceinline__ void inv_core16(typename F::E (&x)[16], typename F::E
     get16<P16A<LOGN>>(lds, tid, x);
     // index bits [4*(NG-1), LOGN-1) <-> r-bits [4-REM, 3) ; bit LOGN-1 <-> r-bit 3 is the scaled last stage
     if constexpr (SUB) {        // a block of a larger transform: every stage of the group is an ordinary one
-        inv16_pre<F, 4 - C::REM, 3>(x, W.ia, P);
+        stages_w<F, false, 4 - C::REM, 3>(W.ia, P, x);
         regroup16<F>(x, P.q, P.qinv);
     } else {
-        if constexpr (C::REM > 1) inv16_pre<F, 4 - C::REM, 2>(x, W.ia, P);
+        if constexpr (C::REM > 1) stages_w<F, false, 4 - C::REM, 2>(W.ia, P, x);
 #pragma unroll
         for (int r = 0; r < 8; r++) F::inv_last(x[r], x[r | 8], P.q, P.q2, ninv, ninv_s, ninvw, ninvw_s);
     }
