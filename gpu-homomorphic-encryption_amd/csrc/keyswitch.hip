@@ -85,6 +85,12 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
         fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
         for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
         digits_fit = (decomp_bits >= 64 ? q_max : (((fhe_host::u128)1 << decomp_bits) < q_max ? ((fhe_host::u128)1 << decomp_bits) : q_max)) <= q_min;
+    } else if (h->width == FHE_WIDTH_52) {
+        // floating-point field: the fused kernels add the L*K digit-times-key products of a limb as doubles and reduce the sum once
+        // (F52::regroup, stated for |x| < 2^49).  A product is below 0.76 q in magnitude, and the external product adds the second
+        // component's L*K products to the reduced sum of the first: (L*K + 1) * 0.76 * 2^43 < 2^49 holds up to L*K = 83 (DESIGN.md
+        // section 4.3).  More digits than that take the general composition, which reduces after every product.
+        digits_fit = (uint64_t)h->L * K <= 83;
     }
     // the fused kernels address a packed table through a buffer descriptor with 32-bit offsets (fhe_dev::TableBuf): a table of 4 GiB or
     // more (L*K*L*n residues: not reached by any parameter set of the reference) stays on the general composition

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """GPU stress: the LDS-resident word-sized kernels (FHE_WIDTH_32 / 52 / 64) against the full-width multi-pass kernels
 (FHE_HIP_FORCE_WIDTH=256: different kernels, same ABI) over random shapes, every call repeated.  Both sides run on the GPU.
+Each trial draws its primes from the bottom of the class (the smallest primes of the bit width) or from the top (the largest primes
+below the class limit 2^30 / 2^43 / 2^62 / 2^64), by the seeded generator.
 usage: stress_width_classes.py [seconds] [seed]"""
 import importlib
 import os
@@ -12,7 +14,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 pkg = importlib.import_module("gpu-homomorphic-encryption_amd")
+import ntt_math as nm  # noqa: E402
 from workload import rns_poly  # noqa: E402
+
+CLASS_LIMIT = {30: 30, 40: 43, 60: 62, 64: 64}         # bit width drawn below -> the limit of the class it lands in
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -29,7 +34,8 @@ while time.time() - t0 < budget:
     bits = int(rng.choice([30, 30, 40, 60, 64])) if log_n <= 15 else int(rng.choice([30, 30, 40, 64]))
     L = int(rng.integers(1, 5)) if log_n <= 14 else int(rng.integers(1, 3))
     batch = int(rng.integers(1, 13)) if log_n <= 13 else int(rng.integers(1, 4))
-    moduli = pkg.find_ntt_primes(bits, n, L)
+    top = bool(rng.integers(2))
+    moduli = nm.largest_ntt_primes(CLASS_LIMIT[bits], n, L) if top else pkg.find_ntt_primes(bits, n, L)
     os.environ.pop("FHE_HIP_FORCE_WIDTH", None)
     fast = pkg.RnsNttEngine(n, moduli)
     os.environ["FHE_HIP_SMALL_BATCH_POLYS"] = "0"; os.environ["FHE_HIP_COOP_POLYS"] = "0"      # the throughput multiply kernel for these small batches
@@ -52,7 +58,7 @@ while time.time() - t0 < budget:
     seed = int(rng.integers(1 << 30))
     x = [rns_poly(seed + i, moduli, n, batch) for i in range(4)]
     shape = x[0].shape
-    info = dict(n=n, bits=bits, L=L, batch=batch, seed=seed)
+    info = dict(n=n, bits=bits, top=top, L=L, batch=batch, seed=seed)
     ref = {}
     for rep in range(3):
         for eng, tag in ((wide, "wide"), (fast, "fast"), (fast_tp, "fast-throughput-kernel"), (fast_lat, "fast-latency-kernel"), (wide2, "wide-2-limb"), (wide2p, "wide-2-limb-passes"), (wide_c, "wide-canonical-tiles"), (fast, "fast"))[:8 if rep == 0 else 4]:

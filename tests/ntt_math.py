@@ -92,6 +92,19 @@ def ntt_primes(bits, n, count):
     return out
 
 
+def largest_ntt_primes(bits, n, count):
+    """The `count` largest primes below 2^bits with q = 1 (mod 2n): the top of a width class's range."""
+    out, step = [], 2 * n
+    q = ((1 << bits) // step) * step + 1
+    while q >= (1 << bits):
+        q -= step
+    while len(out) < count:
+        if is_prime(q):
+            out.append(q)
+        q -= step
+    return out
+
+
 def find_psi(n, q):
     """Same rule as the engine and the oracle: first x^((q-1)/2n), x = 2,3,..., of order exactly 2n."""
     e = (q - 1) // (2 * n)

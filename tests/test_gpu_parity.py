@@ -1408,19 +1408,6 @@ def test_reserve_covers_every_entry_point(eng, monkeypatch, n, spec, w, batch, f
         assert e.workspace_bytes() == held, f"a call of {nb} units grew a workspace after reserve({batch})"
 
 
-def _largest_ntt_primes(bits, n, count):
-    """The `count` largest primes below 2^bits with q = 1 (mod 2n): the top of a width class's range."""
-    out, step = [], 2 * n
-    q = ((1 << bits) // step) * step + 1
-    while q >= (1 << bits):
-        q -= step
-    while len(out) < count:
-        if nm.is_prime(q):
-            out.append(q)
-        q -= step
-    return out
-
-
 @pytest.mark.parametrize("n,bits,L,lazy", [(2048, 250, 2, True), (8192, 250, 1, True), (4096, 122, 2, True), (2048, 122, 1, True), (16384, 250, 1, True),
                                            (2048, 251, 1, False), (2048, 123, 1, False), (2048, 255, 1, False)])
 def test_full_width_lazy_tiles_at_the_top_of_their_range(eng, oracle, monkeypatch, n, bits, L, lazy):
@@ -1428,7 +1415,7 @@ def test_full_width_lazy_tiles_at_the_top_of_their_range(eng, oracle, monkeypatc
     forward butterflies unreduced (values below 23 q), inverse ones below 2q, canonical again before anything is stored.  The LARGEST primes of
     each range, operands at the top of [0, q): the lazy kernels, the canonical ones (FHE_HIP_NO_WIDE_LAZY=1) and the oracle agree bit for bit;
     one bit above the threshold the engine stays on the canonical kernels (same results either way)."""
-    moduli = _largest_ntt_primes(bits, n, L)
+    moduli = nm.largest_ntt_primes(bits, n, L)
     assert all(q.bit_length() == bits for q in moduli)
     e = eng.RnsNttEngine(n, moduli)
     monkeypatch.setenv("FHE_HIP_NO_WIDE_LAZY", "1")

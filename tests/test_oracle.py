@@ -517,3 +517,96 @@ def test_word_sized_cpu_port_equals_the_wide_oracle(oracle):
     with pytest.raises(ValueError):
         n = 64; moduli = nm.ntt_primes(250, n, 1)
         oracle.RnsPlan(n, moduli).polymul_narrow(rns_poly(1, moduli, n, 1), rns_poly(2, moduli, n, 1))
+
+
+# ---------------------------------------------------------------------------------- word-sized classes at the top of their ranges
+TOP_BITS = (30, 43, 62, 64)          # class limits of the four word-sized fields: q < 2^30, 2^43, 2^62, 2^64
+
+
+@pytest.mark.parametrize("n", [2048, 8192, 65536])
+@pytest.mark.parametrize("bits", TOP_BITS)
+def test_largest_ntt_primes_are_the_top_of_their_class(bits, n):
+    qs = nm.largest_ntt_primes(bits, n, 4)
+    assert len(qs) == 4
+    for q in qs:
+        assert q.bit_length() == bits and q % (2 * n) == 1 and nm.is_prime(q)
+    assert all(a > b for a, b in zip(qs, qs[1:]))
+    # nothing was skipped: no prime of the same form lies between two neighbours or above the first one
+    for lo, hi in zip(qs, [1 << bits] + qs[:-1]):
+        assert not any(nm.is_prime(c) for c in range(lo + 2 * n, hi, 2 * n))
+
+
+def _top_patterns(moduli, n, seed):
+    """[3][L][n] residues as Python integers: random, every coefficient q - 1, q - 1 and 0 alternating."""
+    rng = random.Random(seed)
+    return [[[rng.randrange(q) for _ in range(n)] for q in moduli],
+            [[q - 1] * n for q in moduli],
+            [[(q - 1) if i % 2 == 0 else 0 for i in range(n)] for q in moduli]]
+
+
+def _pack(oracle, polys):
+    """[batch][L][n] Python integers -> container array."""
+    b, L, n = len(polys), len(polys[0]), len(polys[0][0])
+    return oracle.to_limbs([v for p in polys for row in p for v in row]).reshape(b, L, n, 4)
+
+
+def _unpack(oracle, arr):
+    b, L, n = arr.shape[:3]
+    flat = oracle.from_limbs(arr)
+    return [[flat[(bi * L + l) * n:(bi * L + l + 1) * n] for l in range(L)] for bi in range(b)]
+
+
+@pytest.mark.parametrize("bits", TOP_BITS)
+def test_oracle_transforms_and_products_at_the_top_primes(oracle, bits):
+    """Two largest primes of each word-sized class, n = 64: forward == the direct definition, inverse undoes it, polymul == the direct
+    negacyclic product, with operands random, all q - 1, and q - 1 / 0 alternating."""
+    n = 64
+    moduli = nm.largest_ntt_primes(bits, n, 2)
+    rp = oracle.RnsPlan(n, moduli)
+    pats = _top_patterns(moduli, n, bits)
+    x = _pack(oracle, pats)
+    f = rp.forward(x, threads=2)
+    got = _unpack(oracle, f)
+    for bi in range(3):
+        for l, q in enumerate(moduli):
+            assert got[bi][l] == nm.negacyclic_ntt_direct(pats[bi][l], q, nm.find_psi(n, q)), (bi, q)
+    assert np.array_equal(rp.inverse(f, threads=2), x)
+    others = _top_patterns(moduli, n, bits + 1000)
+    others[0] = pats[1]                                     # random x all q - 1; all q - 1 squared; alternating squared
+    y = _pack(oracle, others)
+    prod = _unpack(oracle, rp.polymul(x, y, threads=2))
+    for bi in range(3):
+        for l, q in enumerate(moduli):
+            assert prod[bi][l] == nm.negacyclic_mul_direct(pats[bi][l], others[bi][l], q), (bi, q)
+
+
+@pytest.mark.parametrize("w", [16, "bits"])
+@pytest.mark.parametrize("bits", TOP_BITS)
+def test_oracle_relinearize_at_the_top_primes_matches_big_integers(oracle, bits, w):
+    """include/fhe_hip.h: c0 += sum_{j,k} D_{j,k} b_{j,k}, c1 += sum_{j,k} D_{j,k} a_{j,k}; D_{j,k} = bits [k w, (k+1) w) of c2 mod q_j as an
+    integer polynomial, K = ceil(bits(q_max) / w), key row j K + k.  Evaluated here with Python integers and the direct negacyclic product."""
+    n = 64
+    w = bits if w == "bits" else w
+    moduli = nm.largest_ntt_primes(bits, n, 2); L = 2
+    rp = oracle.RnsPlan(n, moduli)
+    K = (max(q.bit_length() for q in moduli) + w - 1) // w
+    assert rp.num_digits(w) == K
+    rng = random.Random(bits * 100 + w)
+    kb = [[[rng.randrange(q) for _ in range(n)] for q in moduli] for _ in range(L * K)]
+    ka = [[[rng.randrange(q) for _ in range(n)] for q in moduli] for _ in range(L * K)]
+    c2 = _top_patterns(moduli, n, 7)                         # batch 3: random, all q - 1 (the largest digits), alternating
+    c0 = _top_patterns(moduli, n, 8); c1 = _top_patterns(moduli, n, 9)
+    c0[2], c1[2] = c0[1], c1[1]                              # accumulators at q - 1 in two slots
+    o0, o1 = rp.relinearize(w, _pack(oracle, c0), _pack(oracle, c1), _pack(oracle, c2), [_pack(oracle, [k])[0] for k in kb], [_pack(oracle, [k])[0] for k in ka], threads=2)
+    g0, g1 = _unpack(oracle, o0), _unpack(oracle, o1)
+    for bi in range(3):
+        want0 = [list(r) for r in c0[bi]]; want1 = [list(r) for r in c1[bi]]
+        for j in range(L):
+            for k in range(K):
+                D = [(v >> (k * w)) & ((1 << w) - 1) for v in c2[bi][j]]
+                for i, q in enumerate(moduli):
+                    Dq = [d % q for d in D]
+                    pb = nm.negacyclic_mul_direct(Dq, kb[j * K + k][i], q); pa = nm.negacyclic_mul_direct(Dq, ka[j * K + k][i], q)
+                    want0[i] = [(u + v) % q for u, v in zip(want0[i], pb)]
+                    want1[i] = [(u + v) % q for u, v in zip(want1[i], pa)]
+        assert g0[bi] == want0 and g1[bi] == want1, bi
