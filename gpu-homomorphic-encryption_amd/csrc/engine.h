@@ -45,6 +45,14 @@ int post_launch(hipStream_t s, const char *what);        // launch error of the 
             return fail(FHE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
     } while (0)
 
+// Every d_* container pointer of the ABI: 16-byte aligned (the kernels load and store containers as 16-byte halves; include/fhe_hip.h,
+// Conventions).  Null pointers pass: the null checks beside each call of this report those.
+inline int check_aligned(std::initializer_list<const void *> ptrs, const char *what) {
+    for (const void *p : ptrs)
+        if ((uintptr_t)p & 15) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": container pointers must be 16-byte aligned");
+    return FHE_OK;
+}
+
 inline fhe_dev::u256 to_dev(const uint64_t q[4]) { fhe_dev::u256 r; std::memcpy(r.l, q, 32); return r; }
 
 inline unsigned ew_grid(size_t items) {

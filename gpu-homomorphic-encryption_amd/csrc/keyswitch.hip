@@ -54,6 +54,7 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
         return fail(FHE_ERR_INVALID_ARG, buf);
     }
     for (uint32_t i = 0; i < num_keys; i++) if (!d_keys_b[i] || !d_keys_a[i]) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null key pointer");
+    for (uint32_t i = 0; i < num_keys; i++) if (int rc = check_aligned({d_keys_b[i], d_keys_a[i]}, "relin_keys_create")) return rc;
     (void)hipGetLastError();
     fhe_relin_keys *rk = new (std::nothrow) fhe_relin_keys();
     if (!rk) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
@@ -165,6 +166,7 @@ static int join_chunks(fhe_rns_ntt *h) {
 extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_c0, void *d_c1, const void *d_c2, uint32_t batch) {
     int rc = check_call(h, batch, "ct_relinearize"); if (rc) return rc;
     if (!rk || !d_c0 || !d_c1 || !d_c2) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: null argument");
+    if ((rc = check_aligned({d_c0, d_c1, d_c2}, "ct_relinearize"))) return rc;
     if (rk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: keys were imported for a different engine");
     if (d_c0 == d_c1 || d_c0 == d_c2 || d_c1 == d_c2) return fail(FHE_ERR_INVALID_ARG, "ct_relinearize: components must be distinct buffers");
     if ((rc = check_inputs(h, {d_c0, d_c1, d_c2}, batch))) return rc;
@@ -233,6 +235,7 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
                                      const void *d_b0, const void *d_b1, uint32_t batch) {
     int rc = check_call(h, batch, "ct_multiply_relin"); if (rc) return rc;
     if (!rk || !d_c0 || !d_c1 || !d_a0 || !d_a1 || !d_b0 || !d_b1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: null argument");
+    if ((rc = check_aligned({d_c0, d_c1, d_a0, d_a1, d_b0, d_b1}, "ct_multiply_relin"))) return rc;
     if (rk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: keys were imported for a different engine");
     const void *ins[4] = {d_a0, d_a1, d_b0, d_b1};
     for (const void *i : ins) if (d_c0 == i || d_c1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must not alias inputs");
@@ -338,6 +341,7 @@ static int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, con
 extern "C" int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t galois_elt, uint32_t batch) {
     int rc = check_call(h, batch, "automorphism"); if (rc) return rc;
     if (!d_out || !d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: null argument");
+    if ((rc = check_aligned({d_out, d_in}, "automorphism"))) return rc;
     if (d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "automorphism: the permutation is out of place (out must differ from in)");
     if ((rc = check_galois_element(h, galois_elt, "automorphism"))) return rc;
     if ((rc = check_inputs(h, {d_in}, batch))) return rc;
@@ -352,6 +356,7 @@ extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk,
                                    const void *d_c1, uint32_t batch) {
     int rc = check_call(h, batch, "ct_apply_galois"); if (rc) return rc;
     if (!gk || !d_out0 || !d_out1 || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: null argument");
+    if ((rc = check_aligned({d_out0, d_out1, d_c0, d_c1}, "ct_apply_galois"))) return rc;
     if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: keys were imported for a different engine");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must be distinct");
     for (const void *i : {d_c0, d_c1}) if (d_out0 == i || d_out1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois: outputs must not alias inputs");
@@ -395,6 +400,7 @@ static int monomial_lds(fhe_rns_ntt *h, void *out, const void *in, const uint32_
 extern "C" int fhe_rns_monomial_mul_sub(fhe_rns_ntt_t *h, void *d_out, const void *d_in, const uint32_t *d_shifts, uint32_t batch) {
     int rc = check_call(h, batch, "monomial_mul_sub"); if (rc) return rc;
     if (!d_out || !d_in || !d_shifts || d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "monomial_mul_sub: null or aliased argument");
+    if ((rc = check_aligned({d_out, d_in}, "monomial_mul_sub"))) return rc;
     if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return monomial_lds<decltype(f)>(h, d_out, d_in, d_shifts, batch); });
     size_t count = (size_t)batch * h->L * h->n;
     hipLaunchKernelGGL(fhe_dev::monomial_mul_sub256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out,
@@ -430,6 +436,7 @@ extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const 
                                 void *d_acc0, void *d_acc1, const uint32_t *d_shifts, void *d_tmp0, void *d_tmp1, uint32_t batch) {
     int rc = check_call(h, batch, "blind_rotate"); if (rc) return rc;
     if (!d_acc0 || !d_acc1 || !d_tmp0 || !d_tmp1 || !d_shifts || (steps && (!rows_c0 || !rows_c1))) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: null argument");
+    if ((rc = check_aligned({d_acc0, d_acc1, d_tmp0, d_tmp1}, "blind_rotate"))) return rc;
     {   // the four buffers must be pairwise distinct
         const void *bufs[4] = {d_acc0, d_acc1, d_tmp0, d_tmp1};
         for (int x = 0; x < 4; x++) for (int y = x + 1; y < 4; y++)

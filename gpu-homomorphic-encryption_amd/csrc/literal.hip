@@ -6,6 +6,7 @@ template <int OP>
 static int launch_ew256(void *d_r, const void *d_a, const void *d_b, const uint64_t q[4], const uint64_t *scalar,
                         uint64_t inv0, size_t count, void *stream, const char *what) {
     if (!d_r || !d_a || (OP != 3 && !d_b) || !q) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": null argument");
+    if (int rc = check_aligned({d_r, d_a, d_b}, what)) return rc;
     int rc = ensure_device(); if (rc) return rc;
     if (!count) return FHE_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -31,6 +32,7 @@ extern "C" int fhe_u256_mont_mul_scalar(void *r, const void *a, const uint64_t s
 // the reference's transform kernels as written (L1 parity; see ntt256.hip.h)
 static int ref_literal_check(const void *d_data, const void *d_table, const uint64_t q[4], uint32_t n, uint32_t batch, const char *what) {
     if (!d_data || !d_table || !q) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": null argument");
+    if (int rc = check_aligned({d_data, d_table}, what)) return rc;
     if (n < 2 || (n & (n - 1)) || n > 65536) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": n must be a power of two in [2, 65536]");
     if (!batch) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": batch must be >= 1");
     return ensure_device();
@@ -56,6 +58,7 @@ extern "C" int fhe_ref_stockham_stage_literal(void *d_output, const void *d_inpu
                                              uint32_t stage, uint32_t batch, void *stream) {
     int rc = ref_literal_check(d_output, d_twiddles, q, n, batch, "fhe_ref_stockham_stage_literal"); if (rc) return rc;
     if (!d_input || d_input == d_output) return fail(FHE_ERR_INVALID_ARG, "fhe_ref_stockham_stage_literal: the stage is out of place");
+    if ((rc = check_aligned({d_input}, "fhe_ref_stockham_stage_literal"))) return rc;
     if ((2u << stage) > n) return fail(FHE_ERR_INVALID_ARG, "fhe_ref_stockham_stage_literal: stage must satisfy 2^(stage+1) <= n");
     (void)hipGetLastError();
     const size_t count = (size_t)batch * (n / 2);
@@ -66,6 +69,7 @@ extern "C" int fhe_ref_stockham_stage_literal(void *d_output, const void *d_inpu
 
 extern "C" int fhe_bit_reverse(void *d_data, uint32_t n, uint32_t batch, void *stream) {
     if (!d_data) return fail(FHE_ERR_INVALID_ARG, "fhe_bit_reverse: null argument");
+    if (int rc = check_aligned({d_data}, "fhe_bit_reverse")) return rc;
     if (n < 2 || (n & (n - 1))) return fail(FHE_ERR_INVALID_ARG, "fhe_bit_reverse: n must be a power of two >= 2");
     if (!batch) return fail(FHE_ERR_INVALID_ARG, "fhe_bit_reverse: batch must be >= 1");
     int rc = ensure_device(); if (rc) return rc;

@@ -88,6 +88,7 @@ static int to_rns_word(fhe_rns_ntt *h, void *d_rns, const void *d_values, uint32
 extern "C" int fhe_rns_to_rns(fhe_rns_ntt_t *h, void *d_rns, const void *d_values, uint32_t batch) {
     int rc = check_call(h, batch, "to_rns"); if (rc) return rc;
     if (!d_rns || !d_values || d_rns == d_values) return fail(FHE_ERR_INVALID_ARG, "to_rns: null or aliased argument");
+    if ((rc = check_aligned({d_rns, d_values}, "to_rns"))) return rc;
     // (to_rns_word_kernel stores through lane pairs of WHOLE waves, store_wave_containers: every wave must cover 64 consecutive containers
     //  of one polynomial, i.e. n a multiple of 256.  Word-sized classes exist from n = 2^11, the guard keeps that an explicit condition.)
     if (h->width != FHE_WIDTH_256 && !h->env.no_word_conversions && h->log_n >= 8)       // word-sized classes: a streaming kernel on the field type
@@ -123,6 +124,7 @@ static int from_rns_word(fhe_rns_ntt *h, void *d_values, const void *d_rns, uint
 extern "C" int fhe_rns_from_rns(fhe_rns_ntt_t *h, void *d_values, const void *d_rns, uint32_t batch) {
     int rc = check_call(h, batch, "from_rns"); if (rc) return rc;
     if (!d_rns || !d_values || d_rns == d_values) return fail(FHE_ERR_INVALID_ARG, "from_rns: null or aliased argument");
+    if ((rc = check_aligned({d_rns, d_values}, "from_rns"))) return rc;
     if ((rc = ensure_crt(h))) return rc;
     if (h->crt_state < 0) return fail(FHE_ERR_UNSUPPORTED, "from_rns: the product of the moduli must be below 2^255 to fit a 256-bit container");
     if (h->width != FHE_WIDTH_256 && !h->env.no_word_conversions)       // word-sized classes: word x 256-bit accumulation instead of 256-bit Montgomery products
@@ -181,6 +183,7 @@ static int base_convert_word(fhe_rns_ntt *h, fhe_rns_ntt *t, void *d_out, const 
 extern "C" int fhe_rns_rescale_drop_last(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t batch) {
     int rc = check_call(h, batch, "rescale_drop_last"); if (rc) return rc;
     if (!d_out || !d_in || d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "rescale_drop_last: null or aliased argument");
+    if ((rc = check_aligned({d_out, d_in}, "rescale_drop_last"))) return rc;
     if (h->L < 2) return fail(FHE_ERR_INVALID_ARG, "rescale_drop_last: needs at least two primes");
     if (h->width != FHE_WIDTH_256 && !h->env.no_word_conversions)       // word-sized classes: streaming kernels on the field type
         return with_word_field(h, [&](auto f) { return rescale_word<decltype(f)>(h, d_out, d_in, batch); });
@@ -206,6 +209,7 @@ extern "C" int fhe_rns_rescale_drop_last(fhe_rns_ntt_t *h, void *d_out, const vo
 extern "C" int fhe_rns_fast_base_convert(fhe_rns_ntt_t *h, fhe_rns_ntt_t *target, void *d_out, const void *d_in, uint32_t batch) {
     int rc = check_call(h, batch, "fast_base_convert"); if (rc) return rc;
     if (!target || !d_out || !d_in || d_out == d_in) return fail(FHE_ERR_INVALID_ARG, "fast_base_convert: null or aliased argument");
+    if ((rc = check_aligned({d_out, d_in}, "fast_base_convert"))) return rc;
     if (target->n != h->n) return fail(FHE_ERR_INVALID_ARG, "fast_base_convert: source and target engines differ in degree");
     if (h->width == target->width && h->width != FHE_WIDTH_256 && !h->env.no_word_conversions && h->log_n >= 8)   // whole waves per polynomial, as in to_rns
         return with_word_field(h, [&](auto f) { return base_convert_word<decltype(f)>(h, target, d_out, d_in, batch); });

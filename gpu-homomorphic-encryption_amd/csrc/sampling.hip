@@ -8,6 +8,7 @@
 template <int KIND>
 static int sample_literal(void *d_out, const uint64_t q[4], uint64_t seed, size_t count, void *stream, const char *what) {
     if (!d_out || !q) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": null argument");
+    if (int rc = check_aligned({d_out}, what)) return rc;
     if (!q[0]) return fail(FHE_ERR_BAD_MODULUS, std::string(what) + ": modulus.limbs[0] is zero (the reference would divide by zero)");
     if (count > 0xffffffffull) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the reference indexes with a uint32_t");
     int rc = ensure_device(); if (rc) return rc;
@@ -55,6 +56,7 @@ static bool small_fits(const fhe_rns_ntt *h, uint64_t max_magnitude) {   // max_
 extern "C" int fhe_rns_sample_ternary(fhe_rns_ntt_t *h, void *d_out, double probability, uint64_t seed, uint32_t batch) {
     int rc = check_call(h, batch, "rns_sample_ternary"); if (rc) return rc;
     if (!d_out) return fail(FHE_ERR_INVALID_ARG, "rns_sample_ternary: null output");
+    if ((rc = check_aligned({d_out}, "rns_sample_ternary"))) return rc;
     if (!(probability >= 0.0 && probability <= 1.0)) return fail(FHE_ERR_INVALID_ARG, "rns_sample_ternary: probability must be in [0, 1]");
     if ((rc = ensure_crt(h))) return rc;
     const uint64_t thr = (uint64_t)(probability * 4294967296.0);
@@ -66,6 +68,7 @@ extern "C" int fhe_rns_sample_ternary(fhe_rns_ntt_t *h, void *d_out, double prob
 extern "C" int fhe_rns_sample_gaussian(fhe_rns_ntt_t *h, void *d_out, double sigma, uint64_t seed, uint32_t batch) {
     int rc = check_call(h, batch, "rns_sample_gaussian"); if (rc) return rc;
     if (!d_out) return fail(FHE_ERR_INVALID_ARG, "rns_sample_gaussian: null output");
+    if ((rc = check_aligned({d_out}, "rns_sample_gaussian"))) return rc;
     if (h->cdt_sigma != sigma || !h->d_cdt) {
         uint32_t len = 0;
         if ((rc = fhe_gaussian_cdt(sigma, nullptr, 0, &len))) return rc;
@@ -87,6 +90,7 @@ extern "C" int fhe_rns_sample_gaussian(fhe_rns_ntt_t *h, void *d_out, double sig
 extern "C" int fhe_rns_sample_uniform(fhe_rns_ntt_t *h, void *d_out, uint64_t seed, uint32_t batch) {
     int rc = check_call(h, batch, "rns_sample_uniform"); if (rc) return rc;
     if (!d_out) return fail(FHE_ERR_INVALID_ARG, "rns_sample_uniform: null output");
+    if ((rc = check_aligned({d_out}, "rns_sample_uniform"))) return rc;
     if ((rc = ensure_crt(h))) return rc;
     const size_t count = (size_t)batch * h->L * h->n;
     hipLaunchKernelGGL(fhe_dev::sample_uniform_rns_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out,
@@ -95,6 +99,7 @@ extern "C" int fhe_rns_sample_uniform(fhe_rns_ntt_t *h, void *d_out, uint64_t se
 }
 extern "C" int fhe_poly_mod_switch(void *d_r, const void *d_a, const uint64_t old_q[4], const uint64_t new_q[4], size_t count, void *stream) {
     if (!d_r || !d_a || !old_q || !new_q) return fail(FHE_ERR_INVALID_ARG, "poly_mod_switch: null argument");
+    if (int rc = check_aligned({d_r, d_a}, "poly_mod_switch")) return rc;
     U256 O = U256::from(old_q);
     if (O.bit_length() < 2 || (O.w[3] >> 63)) return fail(FHE_ERR_BAD_MODULUS, "poly_mod_switch: old modulus must be in [2, 2^255)");
     if (new_q[1] | new_q[2] | new_q[3]) return fail(FHE_ERR_UNSUPPORTED, "poly_mod_switch: the new modulus must be below 2^64");
@@ -108,6 +113,7 @@ extern "C" int fhe_poly_mod_switch(void *d_r, const void *d_a, const uint64_t ol
 }
 extern "C" int fhe_negacyclic_reduce(void *d_data, const uint64_t q[4], size_t n, void *stream) {
     if (!d_data || !q) return fail(FHE_ERR_INVALID_ARG, "negacyclic_reduce: null argument");
+    if (int rc = check_aligned({d_data}, "negacyclic_reduce")) return rc;
     int rc = ensure_device(); if (rc) return rc;
     if (!n) return FHE_OK;
     (void)hipGetLastError();

@@ -408,29 +408,34 @@ int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0,
 extern "C" int fhe_rns_ntt_forward(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) {
     int rc = check_call(h, batch, "forward"); if (rc) return rc;
     if (!d_data) return fail(FHE_ERR_INVALID_ARG, "forward: null data");
+    if ((rc = check_aligned({d_data}, "forward"))) return rc;
     if ((rc = check_inputs(h, {d_data}, batch))) return rc;
     return do_forward(h, d_data, batch);
 }
 extern "C" int fhe_rns_ntt_inverse(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) {
     int rc = check_call(h, batch, "inverse"); if (rc) return rc;
     if (!d_data) return fail(FHE_ERR_INVALID_ARG, "inverse: null data");
+    if ((rc = check_aligned({d_data}, "inverse"))) return rc;
     if ((rc = check_inputs(h, {d_data}, batch))) return rc;
     return do_inverse(h, d_data, batch);
 }
 extern "C" int fhe_rns_ntt_pointwise(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "pointwise"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "pointwise: null argument");
+    if ((rc = check_aligned({r, a, b}, "pointwise"))) return rc;
     return do_ew<0>(h, r, a, b, batch, "pointwise");
 }
 extern "C" int fhe_rns_ntt_multiply(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "multiply"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "multiply: null argument");
+    if ((rc = check_aligned({r, a, b}, "multiply"))) return rc;
     if ((rc = check_inputs(h, {a, b}, batch))) return rc;
     return do_multiply(h, r, a, b, batch);
 }
 extern "C" int fhe_rns_ntt_multiply_bcast(fhe_rns_ntt_t *h, void *r, const void *a, const void *b_one, uint32_t batch) {
     int rc = check_call(h, batch, "multiply_bcast"); if (rc) return rc;
     if (!r || !a || !b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: null argument");
+    if ((rc = check_aligned({r, a, b_one}, "multiply_bcast"))) return rc;
     if (r == b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: the result must not overwrite the shared operand");
     if (h->width != FHE_WIDTH_256 && !h->sub_top)   // every workgroup reads limb (p % L) of the one shared polynomial: L2 hits after the first use
         return lds_multiply(h, r, a, b_one, batch * h->L, h->L);
@@ -442,11 +447,13 @@ extern "C" int fhe_rns_ntt_multiply_bcast(fhe_rns_ntt_t *h, void *r, const void 
 extern "C" int fhe_rns_poly_add(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "poly_add"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "poly_add: null argument");
+    if ((rc = check_aligned({r, a, b}, "poly_add"))) return rc;
     return do_ew<1>(h, r, a, b, batch, "poly_add");
 }
 extern "C" int fhe_rns_mul_mont_literal(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "mul_mont_literal"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "mul_mont_literal: null argument");
+    if ((rc = check_aligned({r, a, b}, "mul_mont_literal"))) return rc;
     if (h->width != FHE_WIDTH_256) return fail(FHE_ERR_UNSUPPORTED, "mul_mont_literal: R = 2^256 Montgomery products exist on full-width handles only "
                                                                     "(an RNS base from fhe_rns_base_create, or FHE_HIP_FORCE_WIDTH=256)");
     return run256_ew<3>(h, r, a, b, batch * h->L, "mul_mont_literal");
@@ -454,12 +461,14 @@ extern "C" int fhe_rns_mul_mont_literal(fhe_rns_ntt_t *h, void *r, const void *a
 extern "C" int fhe_rns_poly_sub(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "poly_sub"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "poly_sub: null argument");
+    if ((rc = check_aligned({r, a, b}, "poly_sub"))) return rc;
     return do_ew<2>(h, r, a, b, batch, "poly_sub");
 }
 extern "C" int fhe_ct_multiply(fhe_rns_ntt_t *h, void *c0, void *c1, void *c2, const void *a0, const void *a1,
                                const void *b0, const void *b1, uint32_t batch) {
     int rc = check_call(h, batch, "ct_multiply"); if (rc) return rc;
     if (!c0 || !c1 || !c2 || !a0 || !a1 || !b0 || !b1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply: null argument");
+    if ((rc = check_aligned({c0, c1, c2, a0, a1, b0, b1}, "ct_multiply"))) return rc;
     const void *ins[4] = {a0, a1, b0, b1}; void *outs[3] = {c0, c1, c2};
     for (void *o : outs) for (const void *i : ins) if (o == i) return fail(FHE_ERR_INVALID_ARG, "ct_multiply: outputs must not alias inputs");
     if (c0 == c1 || c0 == c2 || c1 == c2) return fail(FHE_ERR_INVALID_ARG, "ct_multiply: outputs must be distinct");
@@ -469,6 +478,7 @@ extern "C" int fhe_ct_multiply(fhe_rns_ntt_t *h, void *c0, void *c1, void *c2, c
 extern "C" int fhe_rns_check_canonical(fhe_rns_ntt_t *h, const void *d_data, uint32_t batch) {
     int rc = check_call(h, batch, "check_canonical"); if (rc) return rc;
     if (!d_data) return fail(FHE_ERR_INVALID_ARG, "check_canonical: null data");
+    if ((rc = check_aligned({d_data}, "check_canonical"))) return rc;
     const uint32_t polys = batch * h->L;
     HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(uint32_t), h->stream));
     if (h->width != FHE_WIDTH_256) rc = with_word_field(h, [&](auto f) { return lds_check<decltype(f)>(h, d_data, polys); });

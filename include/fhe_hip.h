@@ -10,9 +10,13 @@
  *
  * Conventions
  *   - 256-bit values are the reference's `uint256_t` (include/bigint.cuh:9-11): 4 x uint64_t,
- *     little-endian limbs, 32 bytes, 8-byte aligned.  Host-side moduli are passed as `const uint64_t[4]`.
+ *     little-endian limbs, 32 bytes.  Host-side moduli are passed as `const uint64_t[4]` (8-byte aligned).
  *   - `d_*` arguments are raw DEVICE pointers owned by the caller (hipMalloc / fhe_hip_malloc /
  *     torch tensor storage), exactly as the reference takes cudaMalloc'd pointers (src/ntt.cu:30-75).
+ *   - Every `d_*` pointer to containers must be 16-byte aligned: the kernels move a container as two 16-byte
+ *     halves.  An allocation base is, and so is any whole-container slice of a buffer that is (offsets are
+ *     multiples of 32 bytes).  A pointer that is not is rejected with FHE_ERR_INVALID_ARG before anything is
+ *     launched.  (`d_shifts` arrays hold uint32_t and need 4-byte alignment only.)
  *   - Polynomial data is limb-major `[batch][L][n]` containers (src/ntt.cu:161).
  *   - Coefficients handed to the NTT entry points must be canonical residues (< q_limb).
  *   - Work is enqueued on the handle's stream and NOT synchronised (callers sync, as the
