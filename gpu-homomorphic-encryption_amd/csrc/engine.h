@@ -4,7 +4,7 @@
 //   core.hip        last error, device / memory entry points, host number theory, timers
 //   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
 //   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
-//   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve
+//   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve (= the merge of need_* below)
 //   transforms.hip  wide and LDS launchers, the planners, forward / inverse / element-wise / multiply / tensor product (ntt_wide.hip.h,
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
 //   keyswitch.hip   key import, relinearisation, multiply + relinearise, Galois, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,9 +142,15 @@ int check_inputs(fhe_rns_ntt *h, std::initializer_list<const void *> operands, u
 // d_ws2: c0, c1, c2 of the fused multiply + relinearise and the compact accumulators of a blind-rotation loop
 // d_ws3: the compact polynomials between the two launches of a two-pass transform (N beyond the LDS range)
 int grow_ws(fhe_rns_ntt *h, void **ws, size_t *have, size_t bytes);
-inline int ensure_ws(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws, &h->ws_bytes, bytes); }
-inline int ensure_ws2(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws2, &h->ws2_bytes, bytes); }
-inline int ensure_ws3(fhe_rns_ntt *h, size_t bytes) { return grow_ws(h, &h->d_ws3, &h->ws3_bytes, bytes); }
+struct WsNeed {
+    size_t ws = 0, ws2 = 0, ws3 = 0;     // bytes of d_ws, d_ws2, d_ws3
+    WsNeed &operator|=(const WsNeed &o) { ws = std::max(ws, o.ws); ws2 = std::max(ws2, o.ws2); ws3 = std::max(ws3, o.ws3); return *this; }
+    friend WsNeed operator|(WsNeed a, const WsNeed &b) { return a |= b; }
+};
+inline int ensure_need(fhe_rns_ntt *h, const WsNeed &n) {
+    int rc = grow_ws(h, &h->d_ws, &h->ws_bytes, n.ws); if (!rc) rc = grow_ws(h, &h->d_ws2, &h->ws2_bytes, n.ws2);
+    return rc ? rc : grow_ws(h, &h->d_ws3, &h->ws3_bytes, n.ws3);
+}
 int ensure_aux_stream(fhe_rns_ntt *h);   // second stream + events of the chunked two-stage pipelines, created on first use
 
 template <class T>
@@ -157,18 +164,19 @@ int upload(fhe_rns_ntt *h, const std::vector<T> &v, void **out) {    // a table 
 }
 
 // ---- transforms.hip -------------------------------------------------------------------------------------------------------------
-// Which form runs a multiply, tensor product, key switch or external product is decided by the planners and nowhere else: every entry point
-// plans, ensures the plan's workspace, fills LdsArgs and launches; fhe_rns_ntt_reserve sizes the workspaces with the same planners.
+// Which form runs a multiply, tensor product, key switch or external product is decided by the planners and nowhere else.  A plan also says what the
+// form needs of the workspaces; need_* merges the plans of an entry point's calls, the entry point ensures that, and so does fhe_rns_ntt_reserve.
 struct LdsPlan {
-    fhe_dev::LdsForm form;
-    int ws = 0;                          // the form's workspace: 0 none, 1 d_ws, 3 d_ws3
+    fhe_dev::LdsForm form = fhe_dev::LDS_ONE_LAUNCH;
+    int ws = 0;                          // the form's own workspace (LdsArgs::ws): 0 none, 1 d_ws, 3 d_ws3
     size_t bytes = 0;
     bool compact = false;                // key switch: c2 is read compact (compacted first, or from the fused tensor product); external product: the
                                          // blind-rotation loop keeps the accumulator pair compact
-    bool prerot = false;                 // external product: the loop applies the monomial factor once per step (rotated digit sources b0, b1)
+    bool add_compact = false;            // key switch: separate compact addends (KS_FUSED) instead of accumulating in place
+    bool prerot = false;                 // external product: the loop applies the monomial factor once per step (rotated digit sources rot0, rot1)
+    size_t ws2 = 0;                      // compact polynomials in d_ws2: 3 components (KS_FUSED), 1 (compacted KS_C2), 4 or 6 (compact external-product loop)
+    WsNeed need() const { return {ws == 1 ? bytes : 0, ws2, ws == 3 ? bytes : 0}; }
 };
-inline void *plan_ws(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? h->d_ws : p.ws == 3 ? h->d_ws3 : nullptr; }
-inline int ensure_plan(fhe_rns_ntt *h, const LdsPlan &p) { return p.ws == 1 ? ensure_ws(h, p.bytes) : p.ws == 3 ? ensure_ws3(h, p.bytes) : FHE_OK; }
 // Key switch source.  KS_C2: c2 in containers, compacted first where that pays; KS_C2_AS_IS: containers that must stay where they are (c2 already
 // in d_ws2: the composed multiply + relinearise under a testing switch); KS_FUSED: c2 and the addends are compact polynomials
 enum KsSource { KS_C2, KS_C2_AS_IS, KS_FUSED };
@@ -177,6 +185,20 @@ LdsPlan plan_ct_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands,
 bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys);
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone);
 LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
+// What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
+WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
+WsNeed need_multiply(const fhe_rns_ntt *h, uint32_t batch);
+WsNeed need_ct_multiply(const fhe_rns_ntt *h, uint32_t batch, bool same_operands);
+WsNeed need_relinearize(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed, KsSource src);
+WsNeed need_ct_multiply_relin(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed);
+WsNeed need_apply_galois(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed);
+WsNeed need_blind_rotate(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed);
+inline fhe_dev::LdsArgs lds_args(fhe_rns_ntt *h, int op, const LdsPlan &p, uint32_t polys) {   // everything but the operands and layouts of the op
+    fhe_dev::LdsArgs A;
+    A.op = op; A.form = p.form; A.ws = p.ws == 1 ? h->d_ws : p.ws == 3 ? h->d_ws3 : nullptr;
+    A.limbs = h->d_limbs; A.L = h->L; A.polys = polys; A.stream = h->stream;
+    return A;
+}
 // one call of the (field, log_n) instance: the instance launches exactly the form A asks for, or nothing and says so
 int lds_launch(fhe_rns_ntt *h, const fhe_dev::LdsArgs &A, const char *what, int log_n = 0);
 int do_forward(fhe_rns_ntt *h, void *d_data, uint32_t batch);

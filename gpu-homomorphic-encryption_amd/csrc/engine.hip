@@ -321,37 +321,22 @@ extern "C" int fhe_rns_ntt_set_stream(fhe_rns_ntt_t *h, void *stream) {
     h->stream = stream ? (hipStream_t)stream : h->own_stream;
     return FHE_OK;
 }
-// Pre-sizes the library-owned workspaces for calls of up to `batch` units, so that no later call allocates (hipMalloc synchronises
-// and cannot be captured into a hipGraph): the compact / container workspace of fhe_ct_multiply_relin, fhe_ct_apply_galois and fhe_blind_rotate, and the
-// transform workspace of the general paths (full-width class, two-pass sizes).  Relinearisation on the general path sizes its digit
-// workspace by itself (bounded to 1 GiB, chunked).
+// Pre-sizes the library-owned workspaces for calls of up to `batch` units, so that no later call allocates (hipMalloc synchronises and cannot be captured into a hipGraph):
+// the merge of every entry point's need_* (engine.h), for the largest K of the key sets imported so far, with and without packed tables (import keys first).
 extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
-    // The union of what every entry point asks of ensure_ws / ws2 / ws3 for `batch` units, so that none of them allocates afterwards.  The
-    // key-switch workspaces depend on the digit count: the largest K of the key sets imported so far (import keys first).
     int rc = check_call(h, batch, "reserve"); if (rc) return rc;
-    const size_t polys = (size_t)batch * h->L, S = (size_t)h->L * h->n * 32, eb = residue_bytes(h), cbytes = polys * h->n * eb;
-    const bool lds_class = h->width != FHE_WIDTH_256 && !h->sub_top;
-    size_t ws = 0, ws2 = (size_t)batch * S, ws3 = 0;                   // ws2: one container component (c2 of multiply + relinearise on the general path) ...
-    if (6 * cbytes > ws2) ws2 = 6 * cbytes;                            // ... or the 3 compact components of the fused multiply + relinearise, the 4 or 6 of a blind-rotation loop
-    if (!lds_class) ws = 5 * (size_t)batch * S;                        // 4 transformed operands + one product (tensor product of the general / two-pass paths)
-    if (h->max_composed_digits) {                                      // digit polynomials + two accumulators of the composed key switch (key sets without packed tables)
-        const size_t LK = (size_t)h->L * h->max_composed_digits;
-        size_t chunk = ((size_t)1 << 30) / ((LK + 2) * S); if (chunk < 1) chunk = 1; if (chunk > batch) chunk = batch;
-        if ((LK + 2) * chunk * S > ws) ws = (LK + 2) * chunk * S;
+    WsNeed n;
+    // the few-polynomial forms are taken by every call of at most split_pairs_polys / coop_polys limb polynomials: the largest batch below each threshold as well
+    for (uint32_t b : {batch, std::min(batch, h->env.split_pairs_polys / h->L), std::min(batch, h->env.coop_polys / h->L)}) {
+        if (!b) continue;
+        n |= need_transform(h, (size_t)b * h->L) | need_multiply(h, b) | need_ct_multiply(h, b, false);
+        const bool lds_class = h->width != FHE_WIDTH_256 && !h->sub_top;             // where packed key tables exist
+        for (bool packed : {true, false}) {
+            const uint32_t K = packed ? (lds_class ? std::max(h->max_digits, 1u) : 0) : h->max_composed_digits;
+            if (K) n |= need_relinearize(h, b, K, packed, KS_C2) | need_ct_multiply_relin(h, b, K, packed) | need_apply_galois(h, b, K, packed) | need_blind_rotate(h, b, K, packed);
+        }
     }
-    if (h->sub_top) ws3 = 2 * cbytes;                                  // two compact operands of a two-pass multiply
-    if (lds_class) {
-        // the workspace of every form the planners pick for up to `batch` units: the few-polynomial forms are taken by every call of at most
-        // split_pairs_polys / coop_polys limb polynomials, a smaller batch than the reserved one included
-        const uint32_t K = h->max_digits ? h->max_digits : 1;
-        for (size_t p : {polys, std::min<size_t>(polys, h->env.split_pairs_polys), std::min<size_t>(polys, h->env.coop_polys)})
-            for (const LdsPlan &P : {plan_multiply(h, p, false), plan_ct_multiply(h, p, false, false, true), plan_ct_multiply(h, p, false, true, true),
-                                     plan_keyswitch(h, p, K, KS_C2, true), plan_keyswitch(h, p, K, KS_FUSED, true), plan_extprod(h, p, K)}) {
-                size_t &need = P.ws == 1 ? ws : ws3;
-                if (P.ws && P.bytes > need) need = P.bytes;
-            }
-    }
-    if ((rc = ensure_ws(h, ws)) || (rc = ensure_ws2(h, ws2)) || (ws3 && (rc = ensure_ws3(h, ws3)))) return rc;
+    if ((rc = ensure_need(h, n))) return rc;
     return ensure_aux_stream(h);                                       // second stream + events of the chunked pipelines
 }
 extern "C" int fhe_rns_ntt_workspace_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {

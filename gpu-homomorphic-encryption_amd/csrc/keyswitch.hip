@@ -77,15 +77,12 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
     // integer butterflies accept inputs below 4*q_i; bases mixing very different prime sizes go through the general
     // composition, which reduces every digit modulo q_i first.
     bool digits_fit = true;
-    if (h->width == FHE_WIDTH_32 || h->width == FHE_WIDTH_64) {
+    if (h->width == FHE_WIDTH_32 || h->width == FHE_WIDTH_64 || h->width == FHE_WIDTH_64X) {
         fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
         for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
-        fhe_host::u128 digit_bound = decomp_bits >= 64 ? q_max : (((fhe_host::u128)1 << decomp_bits) < q_max ? ((fhe_host::u128)1 << decomp_bits) : q_max);
-        digits_fit = digit_bound <= 4 * q_min;
-    } else if (h->width == FHE_WIDTH_64X) {   // canonical butterflies: a digit must be a residue of q_i as it stands
-        fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
-        for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
-        digits_fit = (decomp_bits >= 64 ? q_max : (((fhe_host::u128)1 << decomp_bits) < q_max ? ((fhe_host::u128)1 << decomp_bits) : q_max)) <= q_min;
+        const fhe_host::u128 digit_bound = decomp_bits < 64 ? std::min((fhe_host::u128)1 << decomp_bits, q_max) : q_max;
+        // the full-range field's butterflies are canonical: there a digit must be a residue of q_i as it stands
+        digits_fit = digit_bound <= (h->width == FHE_WIDTH_64X ? q_min : 4 * q_min);
     } else if (h->width == FHE_WIDTH_52) {
         // floating-point field: the fused kernels add the L*K digit-times-key products of a limb as doubles and reduce the sum once
         // (F52::regroup, stated for |x| < 2^49).  A product is below 0.76 q in magnitude, and the external product adds the second
@@ -141,14 +138,43 @@ static int relin_embed_mac(fhe_rns_ntt *h, const fhe_relin_keys *rk, char *D, ch
     return post_launch(h->stream, "relin_mac256_kernel");
 }
 
-// The key-switch call of a plan: digit source c2 (compact where the plan says so), results r0 / r1, addends add0 / add1 (nullptr: r0 / r1 are
-// accumulated in place), `polys` limb polynomials on stream s
+// The key-switch call of a plan: digit source c2 (compact where the plan says so), results r0 / r1, compact addends add0 / add1 (nullptr: in place)
 static fhe_dev::LdsArgs keyswitch_args(fhe_rns_ntt *h, const fhe_relin_keys *rk, const LdsPlan &P, void *r0, void *r1, const void *c2, const void *add0,
                                        const void *add1, uint32_t polys, hipStream_t s) {
-    fhe_dev::LdsArgs B{fhe_dev::LDS_KEYSWITCH, P.form, r0, r1, nullptr, c2, add0, add1, nullptr, h->d_limbs, h->L, polys, s};
-    B.in_compact = P.compact; B.ws = plan_ws(h, P);
+    fhe_dev::LdsArgs B = lds_args(h, fhe_dev::LDS_KEYSWITCH, P, polys);
+    B.r0 = r0; B.r1 = r1; B.c2 = c2; B.add0 = add0; B.add1 = add1; B.stream = s; B.in_compact = P.compact; B.add_compact = P.add_compact;
     B.kb = rk->d_pkb; B.ka = rk->d_pka; B.K = rk->K; B.w = rk->decomp_bits;
     return B;
+}
+// The two chunked pipelines (stand-alone relinearisation, one-call multiply + relinearise) cut the batch into chunks of whole ciphertexts: as many
+// as wanted, fewer while a chunk would not fill the chip (1024 limb polynomials: 256 CUs x 4 workgroups) or hold one ciphertext
+struct Pipeline {
+    uint32_t chunks = 1;
+    struct { LdsPlan first, ks; } c[16]; // per chunk: tensor product (the relinearisation's first stage, the compaction, has no plan), key switch
+    WsNeed need;                         // of the whole call
+    void add(const LdsPlan &p) { const size_t ws2 = need.ws2 + p.ws2; need |= p.need(); need.ws2 = ws2; }   // every chunk has its own slice of d_ws2
+};
+static uint32_t pipeline_chunks(const fhe_rns_ntt *h, uint32_t batch, uint32_t want) { while (want > 1 && ((size_t)batch * h->L / want < 1024 || batch < want)) want--; return want; }
+static uint32_t chunk_begin(uint32_t batch, uint32_t chunks, uint32_t c) { return c * (batch / chunks) + std::min(c, batch % chunks); }   // first ciphertext of chunk c
+// Chunks of whole ciphertexts on two streams: the compaction of chunk i+1 (HBM-bound) runs beside the key switch of chunk i.
+// (measured, N = 8192 x 4 x 30-bit, batch 1024: compaction alone 773 K -> 805 K relin/s at w = 16, 948 K -> 1007 K at w = 30; with the key switch of
+//  chunk i beside the compaction of chunk i+1 on a second stream 807 K / 953 K at two chunks, 772 K / 948 K at four: one stream unless asked)
+static Pipeline relin_pipeline(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, KsSource src) {
+    Pipeline pl;
+    const LdsPlan P = plan_keyswitch(h, (size_t)batch * h->L, K, src, true);
+    if (P.compact && h->width == FHE_WIDTH_32 && h->env.relin_chunks_forced) pl.chunks = pipeline_chunks(h, batch, h->env.overlap_chunks);
+    for (uint32_t c = 0; c < pl.chunks; c++)
+        pl.add(pl.c[c].ks = pl.chunks == 1 ? P : plan_keyswitch(h, (size_t)(chunk_begin(batch, pl.chunks, c + 1) - chunk_begin(batch, pl.chunks, c)) * h->L, K, KS_C2, false));
+    return pl;
+}
+// The composed key switch (no packed tables): digit polynomials D[L K][chunk] + two accumulators in d_ws, bounded to ~1 GiB: ciphertexts per chunk
+static uint32_t composed_chunk(const fhe_rns_ntt *h, uint32_t batch, uint32_t K) {
+    return (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / (((size_t)h->L * K + 2) * h->L * h->n * 32), 1), batch);
+}
+WsNeed need_relinearize(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed, KsSource src) {
+    const size_t LK = (size_t)h->L * K, chunk = composed_chunk(h, batch, K);
+    if (packed) return relin_pipeline(h, batch, K, src).need;
+    return {(LK + 2) * chunk * h->L * h->n * 32, 0, 0};   // (the transforms of the digit polynomials and accumulators ensure their own d_ws3, as before)
 }
 // Two-stream chunk pipeline: what the engine's stream has queued for chunk c is done -> the second stream may start on it; at the end the
 // engine's stream joins the second one, so the call stays ordered on the engine's stream (and can be captured: fork / join through events).
@@ -173,42 +199,27 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
     if (rk->d_pkb) {   // word-sized paths: fused launches
         // (c2 already in the workspace: the composed multiply + relinearise under a testing switch -- it stays where it is)
         const bool c2_in_ws2 = h->d_ws2 && (const char *)d_c2 >= (const char *)h->d_ws2 && (const char *)d_c2 < (const char *)h->d_ws2 + h->ws2_bytes;
-        const LdsPlan P = plan_keyswitch(h, batch * h->L, rk->K, c2_in_ws2 ? KS_C2_AS_IS : KS_C2, true);
+        const Pipeline pl = relin_pipeline(h, batch, rk->K, c2_in_ws2 ? KS_C2_AS_IS : KS_C2);
         const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * residue_bytes(h);
-        uint32_t chunks = 1;
-        if (P.compact) {
-            if ((rc = ensure_ws2(h, (size_t)batch * Sc))) return rc;
-            // Chunks of whole ciphertexts on two streams: the compaction of chunk i+1 (HBM-bound) runs beside the key switch of chunk i.
-            // (measured, N = 8192 x 4 x 30-bit, batch 1024: compaction alone 773 K -> 805 K relin/s at w = 16, 948 K -> 1007 K at w = 30; with the key switch of
-            //  chunk i beside the compaction of chunk i+1 on a second stream 807 K / 953 K at two chunks, 772 K / 948 K at four: one stream unless asked)
-            if (h->width == FHE_WIDTH_32 && h->env.relin_chunks_forced) chunks = h->env.overlap_chunks;
-            while (chunks > 1 && ((size_t)batch * h->L / chunks < 1024 || batch < chunks)) chunks--;
-            if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
-        }
-        for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
-            const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
+        if ((rc = ensure_need(h, pl.need)) || (pl.chunks > 1 && (rc = ensure_aux_stream(h)))) return rc;
+        for (uint32_t c = 0; c < pl.chunks; c++) {
+            const uint32_t b0 = chunk_begin(batch, pl.chunks, c), nb = chunk_begin(batch, pl.chunks, c + 1) - b0;
+            const LdsPlan &Q = pl.c[c].ks;
             const void *c2 = (const char *)d_c2 + (size_t)b0 * S;
-            if (P.compact) {
+            if (Q.compact) {
                 char *c2c = (char *)h->d_ws2 + (size_t)b0 * Sc;
                 if ((rc = compact_poly(h, c2c, c2, (size_t)nb * h->L * h->n))) return rc;
                 c2 = c2c;
             }
-            const LdsPlan Q = chunks == 1 ? P : plan_keyswitch(h, nb * h->L, rk->K, KS_C2, false);
-            if ((rc = ensure_plan(h, Q))) return rc;
-            if (chunks > 1 && (rc = fork_chunk(h, c))) return rc;
+            if (pl.chunks > 1 && (rc = fork_chunk(h, c))) return rc;
             if ((rc = lds_launch(h, keyswitch_args(h, rk, Q, (char *)d_c0 + (size_t)b0 * S, (char *)d_c1 + (size_t)b0 * S, c2, nullptr, nullptr, nb * h->L,
-                                                   chunks > 1 ? h->aux_stream : h->stream), "ntt_keyswitch_kernel"))) return rc;
-            b0 += nb;
+                                                   pl.chunks > 1 ? h->aux_stream : h->stream), "ntt_keyswitch_kernel"))) return rc;
         }
-        return chunks > 1 ? join_chunks(h) : FHE_OK;
+        return pl.chunks > 1 ? join_chunks(h) : FHE_OK;
     }
-    const uint32_t LK = h->L * rk->K;
+    const uint32_t LK = h->L * rk->K, chunk = composed_chunk(h, batch, rk->K);
     const size_t S = (size_t)h->L * h->n * 32;
-    // workspace: digit polynomials D[LK][chunk] + two accumulators; bounded to ~1 GiB, the batch is processed in chunks
-    uint32_t chunk = (uint32_t)(((size_t)1 << 30) / ((LK + 2) * S));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
-    if ((rc = ensure_ws(h, (size_t)(LK + 2) * chunk * S))) return rc;
+    if ((rc = ensure_need(h, need_relinearize(h, batch, rk->K, false, KS_C2)))) return rc;
     char *D = (char *)h->d_ws, *acc0 = D + (size_t)LK * chunk * S, *acc1 = acc0 + (size_t)chunk * S;
     for (uint32_t done = 0; done < batch; done += chunk) {
         const uint32_t nb = batch - done < chunk ? batch - done : chunk;
@@ -225,6 +236,23 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
     return FHE_OK;
 }
 
+static Pipeline ct_relin_pipeline(const fhe_rns_ntt *h, uint32_t batch, uint32_t K) {
+    Pipeline pl;
+    const LdsPlan T = plan_ct_multiply(h, (size_t)batch * h->L, false, true, true);
+    const bool two = T.form == fhe_dev::LDS_TWO_LAUNCH;                  // at N >= 2^14: 128+ KiB of LDS per workgroup, the two stages cannot share a CU anyway
+    pl.chunks = pipeline_chunks(h, batch, two && h->log_n >= 14 ? 1 : h->env.overlap_chunks);
+    pl.add(T);                           // the two-launch form's workspace is sized for the whole batch, every chunk has its slice
+    for (uint32_t c = 0; c < pl.chunks; c++) {
+        const size_t polys = (size_t)(chunk_begin(batch, pl.chunks, c + 1) - chunk_begin(batch, pl.chunks, c)) * h->L;
+        pl.add(pl.c[c].first = pl.chunks == 1 ? T : plan_ct_multiply(h, polys, false, true, false));
+        pl.add(pl.c[c].ks = plan_keyswitch(h, polys, K, KS_FUSED, pl.chunks == 1 && !two));   // (the few-ciphertext parts take d_ws: never beside the two-launch form)
+    }
+    return pl;
+}
+WsNeed need_ct_multiply_relin(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {   // composed: the tensor product's c2 as containers in d_ws2
+    return plan_fused_ct_relin(h, packed) ? ct_relin_pipeline(h, batch, K).need
+                                          : WsNeed{0, (size_t)batch * h->L * h->n * 32, 0} | need_ct_multiply(h, batch, false) | need_relinearize(h, batch, K, packed, KS_C2_AS_IS);
+}
 // FHEContext::multiply as the reference declares it (src/fhe.cu:199-224: tensor product, then relinearize): (c0, c1) = relin(a (x) b).
 // On the LDS-resident sizes of the word-sized classes the three components of the tensor product never take the 32-byte container
 // form: the tensor-product kernel(s) write c0, c1, c2 to a compact workspace (sizeof(residue) bytes per coefficient) and the
@@ -241,45 +269,33 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
     for (const void *i : ins) if (d_c0 == i || d_c1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must not alias inputs");
     if (d_c0 == d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_multiply_relin: outputs must be distinct");
     if ((rc = check_inputs(h, {d_a0, d_a1, d_b0, d_b1}, batch))) return rc;
-    const uint32_t polys = batch * h->L;
     if (plan_fused_ct_relin(h, rk->d_pkb != nullptr)) {
-        const size_t eb = residue_bytes(h), cbytes = (size_t)polys * h->n * eb;         // one compact component
-        if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
-        char *c0c = (char *)h->d_ws2, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
         // The two kernels of the call sit on different roofs: the tensor product streams 4 S in at the HBM rate, the key switch (compact
         // operands) is bound by instruction issue.  The call is therefore a two-stage pipeline over chunks of whole ciphertexts: every
         // tensor product runs on the engine's stream, back to back; the key switch of chunk i runs on a second stream as soon as
         // tensor product i is done (event), i.e. beside tensor product i+1 on the same CUs.  The engine's stream joins the second one
         // at the end, so the call stays ordered on the engine's stream (and can be captured into a graph: fork / join through events).
-        // Every chunk has its own slice of the compact workspace (and of the two-launch form's, sized here for the whole batch).
-        const LdsPlan T = plan_ct_multiply(h, polys, false, true, true);
-        if ((rc = ensure_plan(h, T))) return rc;
-        const bool two = T.form == fhe_dev::LDS_TWO_LAUNCH;
-        uint32_t chunks = h->env.overlap_chunks;
-        if (two && h->log_n >= 14) chunks = 1;                  // 128+ KiB of LDS per workgroup: the two stages cannot share a CU anyway
-        while (chunks > 1 && (polys / chunks < 1024 || batch < chunks)) chunks--;   // every chunk must fill the chip: >= 256 CUs x 4 workgroups (one per limb polynomial)
-        if (chunks > 1 && (rc = ensure_aux_stream(h))) return rc;
+        // Every chunk has its own slice of the compact workspace (and of the two-launch form's, sized for the whole batch).
+        const Pipeline pl = ct_relin_pipeline(h, batch, rk->K);             // (its need is need_ct_multiply_relin's)
+        if ((rc = ensure_need(h, pl.need)) || (pl.chunks > 1 && (rc = ensure_aux_stream(h)))) return rc;
+        const size_t eb = residue_bytes(h), cbytes = (size_t)batch * h->L * h->n * eb;       // one compact component
+        char *c0c = (char *)h->d_ws2, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
         const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * eb;   // bytes of one ciphertext component: containers / compact
-        for (uint32_t c = 0, b0 = 0; c < chunks; c++) {
-            const uint32_t nb = batch / chunks + (c < batch % chunks ? 1 : 0);
+        for (uint32_t c = 0; c < pl.chunks; c++) {
+            const uint32_t b0 = chunk_begin(batch, pl.chunks, c), nb = chunk_begin(batch, pl.chunks, c + 1) - b0;
             const size_t o = (size_t)b0 * S, oc = (size_t)b0 * Sc;
-            const LdsPlan Tc = chunks == 1 ? T : plan_ct_multiply(h, nb * h->L, false, true, false);
-            fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, Tc.form, c0c + oc, c1c + oc, c2c + oc, (const char *)d_a0 + o, (const char *)d_a1 + o, (const char *)d_b0 + o,
-                               (const char *)d_b1 + o, h->d_limbs, h->L, nb * h->L, h->stream};
-            A.out_compact = true;
-            if (Tc.ws) A.ws = (char *)plan_ws(h, Tc) + (two ? 2 * oc : 0);   // two-launch: two compact polynomials per limb polynomial of the chunk
+            fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_CT_MULTIPLY, pl.c[c].first, nb * h->L);
+            A.r0 = c0c + oc; A.r1 = c1c + oc; A.r2 = c2c + oc; A.out_compact = true;
+            A.a0 = (const char *)d_a0 + o; A.a1 = (const char *)d_a1 + o; A.b0 = (const char *)d_b0 + o; A.b1 = (const char *)d_b1 + o;
+            if (A.ws && A.form == fhe_dev::LDS_TWO_LAUNCH) A.ws = (char *)A.ws + 2 * oc;   // two compact polynomials per limb polynomial of the chunk
             if ((rc = lds_launch(h, A, "tensor product (compact outputs)"))) return rc;
-            if (chunks > 1 && (rc = fork_chunk(h, c))) return rc;
-            // (the few-ciphertext parts take d_ws: never beside the two-launch tensor product, which the 4-byte field up to 2^14 does not use anyway)
-            const LdsPlan Kc = plan_keyswitch(h, nb * h->L, rk->K, KS_FUSED, chunks == 1 && !two);
-            if ((rc = ensure_plan(h, Kc))) return rc;
-            if ((rc = lds_launch(h, keyswitch_args(h, rk, Kc, (char *)d_c0 + o, (char *)d_c1 + o, c2c + oc, c0c + oc, c1c + oc, nb * h->L,
-                                                   chunks > 1 ? h->aux_stream : h->stream), "key switch (compact operands)"))) return rc;
-            b0 += nb;
+            if (pl.chunks > 1 && (rc = fork_chunk(h, c))) return rc;
+            if ((rc = lds_launch(h, keyswitch_args(h, rk, pl.c[c].ks, (char *)d_c0 + o, (char *)d_c1 + o, c2c + oc, c0c + oc, c1c + oc, nb * h->L,
+                                                   pl.chunks > 1 ? h->aux_stream : h->stream), "key switch (compact operands)"))) return rc;
         }
-        return chunks > 1 ? join_chunks(h) : FHE_OK;
+        return pl.chunks > 1 ? join_chunks(h) : FHE_OK;
     }
-    if ((rc = ensure_ws2(h, (size_t)polys * h->n * 32))) return rc;
+    if ((rc = ensure_need(h, need_ct_multiply_relin(h, batch, rk->K, rk->d_pkb != nullptr)))) return rc;
     if ((rc = do_ct_multiply(h, d_c0, d_c1, h->d_ws2, d_a0, d_a1, d_b0, d_b1, batch))) return rc;
     return fhe_ct_relinearize(h, rk, d_c0, d_c1, h->d_ws2, batch);
 }
@@ -352,6 +368,10 @@ extern "C" int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d
 // polynomial as compact polynomials into the three slices of d_ws2 that fhe_ct_multiply_relin uses, then ONE compact-operand key switch
 // (KS_FUSED) reads them -- HBM traffic 2 S in + 2 S out plus the compact round trip.  Elsewhere: sigma(c0) -> out0, zero -> out1 and
 // sigma(c1) -> d_ws2 as containers in one launch, then fhe_ct_relinearize.
+WsNeed need_apply_galois(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {
+    if (plan_fused_ct_relin(h, packed) && !h->env.no_fused_galois) return plan_keyswitch(h, (size_t)batch * h->L, K, KS_FUSED, true).need();
+    return WsNeed{0, (size_t)batch * h->L * h->n * 32, 0} | need_relinearize(h, batch, K, packed, KS_C2_AS_IS);
+}
 extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1, const void *d_c0,
                                    const void *d_c1, uint32_t batch) {
     int rc = check_call(h, batch, "ct_apply_galois"); if (rc) return rc;
@@ -363,16 +383,14 @@ extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk,
     if ((rc = check_galois_element(h, galois_elt, "ct_apply_galois"))) return rc;
     if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
     const size_t polys = (size_t)batch * h->L;
+    if ((rc = ensure_need(h, need_apply_galois(h, batch, gk->K, gk->d_pkb != nullptr)))) return rc;
     if (plan_fused_ct_relin(h, gk->d_pkb != nullptr) && !h->env.no_fused_galois) {
         const size_t cbytes = polys * h->n * residue_bytes(h);
-        if ((rc = ensure_ws2(h, 3 * cbytes))) return rc;
         char *s0 = (char *)h->d_ws2, *s1 = s0 + cbytes, *zero = s1 + cbytes;      // sigma(c0): addend of c0'; sigma(c1): digit source; 0: addend of c1'
         const LdsPlan P = plan_keyswitch(h, polys, gk->K, KS_FUSED, true);
-        if ((rc = ensure_plan(h, P))) return rc;
         if ((rc = do_galois(h, s0, s1, zero, d_c0, d_c1, galois_elt, polys, true))) return rc;
         return lds_launch(h, keyswitch_args(h, gk, P, d_out0, d_out1, s1, s0, zero, (uint32_t)polys, h->stream), "key switch (rotation)");
     }
-    if ((rc = ensure_ws2(h, polys * h->n * 32))) return rc;
     if ((rc = do_galois(h, d_out0, h->d_ws2, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
     return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->d_ws2, batch);
 }
@@ -421,9 +439,10 @@ static int blind_rotate_step_general(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
 static int blind_rotate_step_fused(fhe_rns_ntt_t *h, const LdsPlan &P, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1, void *out0, void *out1,
                                    const void *in0, const void *in1, const uint32_t *d_shifts, uint32_t batch, bool in_compact, bool out_compact,
                                    const void *rot0, const void *rot1) {
-    fhe_dev::LdsArgs A{fhe_dev::LDS_EXTPROD, P.form, out0, out1, nullptr, in0, in1, rot0, rot1, h->d_limbs, h->L, batch * h->L, h->stream};
+    fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_EXTPROD, P, batch * h->L);
+    A.r0 = out0; A.r1 = out1; A.a0 = in0; A.a1 = in1; A.rot0 = rot0; A.rot1 = rot1;
     A.kb = r0->d_pkb; A.ka = r0->d_pka; A.kb1 = r1->d_pkb; A.ka1 = r1->d_pka; A.K = r0->K; A.w = r0->decomp_bits; A.shifts = d_shifts;
-    A.in_compact = in_compact; A.out_compact = out_compact; A.ws = plan_ws(h, P);
+    A.in_compact = in_compact; A.out_compact = out_compact;
     return lds_launch(h, A, "ntt_extprod_kernel");
 }
 static int check_rows(const fhe_rns_ntt_t *h, const fhe_relin_keys_t *r0, const fhe_relin_keys_t *r1) {
@@ -431,6 +450,10 @@ static int check_rows(const fhe_rns_ntt_t *h, const fhe_relin_keys_t *r0, const 
     if (r0->owner != h || r1->owner != h) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: rows were imported for a different engine");
     if (r0->decomp_bits != r1->decomp_bits || r0->K != r1->K) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: the two row sets use different digit widths");
     return FHE_OK;
+}
+static bool blind_rotate_fused(const fhe_rns_ntt *h, bool packed) { return packed && h->width != FHE_WIDTH_256 && !h->env.no_fused_blind_rotate; }
+WsNeed need_blind_rotate(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {   // fused loop: the plan's; else every step is two stand-alone key switches
+    return blind_rotate_fused(h, packed) ? plan_extprod(h, (size_t)batch * h->L, K).need() : need_relinearize(h, batch, K, packed, KS_C2);
 }
 extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *rows_c0, const fhe_relin_keys_t *const *rows_c1, uint32_t steps,
                                 void *d_acc0, void *d_acc1, const uint32_t *d_shifts, void *d_tmp0, void *d_tmp1, uint32_t batch) {
@@ -443,30 +466,28 @@ extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const 
             if (bufs[x] == bufs[y]) return fail(FHE_ERR_INVALID_ARG, "blind_rotate: accumulators and scratch must be distinct buffers");
     }
     if ((rc = check_inputs(h, {d_acc0, d_acc1}, batch))) return rc;
-    bool fused = h->width != FHE_WIDTH_256 && !h->env.no_fused_blind_rotate;
-    uint32_t kmax = 0;
+    bool packed = true; uint32_t kmax = 0;
     for (uint32_t s = 0; s < steps; s++) {
         if ((rc = check_rows(h, rows_c0[s], rows_c1[s]))) return rc;
-        fused = fused && rows_c0[s]->d_pkb && rows_c1[s]->d_pkb;
+        packed = packed && rows_c0[s]->d_pkb && rows_c1[s]->d_pkb;
         kmax = rows_c0[s]->K > kmax ? rows_c0[s]->K : kmax;
     }
-    if (!fused) {
+    if (!blind_rotate_fused(h, packed)) {
         for (uint32_t s = 0; s < steps; s++)
             if ((rc = blind_rotate_step_general(h, rows_c0[s], rows_c1[s], d_acc0, d_acc1, d_shifts + (size_t)s * batch, d_tmp0, d_tmp1, batch))) return rc;
         return FHE_OK;
     }
     if (!steps) return FHE_OK;
     const LdsPlan P = plan_extprod(h, batch * h->L, kmax);
+    if ((rc = ensure_need(h, P.need()))) return rc;
     if (P.compact) {
         // The accumulator pair is compacted first (one streaming pass), every step reads compact input from a workspace ping-pong (4 compact
         // polynomials; 2 more hold the pre-rotated pair of the current step), all but the last write compact output, the last one writes the
         // caller's containers.  The caller's scratch pair is not touched.
         const size_t cbytes = (size_t)batch * h->L * h->n * residue_bytes(h), count = (size_t)batch * h->L * h->n;
-        if ((rc = ensure_ws2(h, (P.form == fhe_dev::LDS_PAIRED ? 4 : 6) * cbytes))) return rc;
         char *w0 = (char *)h->d_ws2;
         char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
         char *rot0 = w0 + 4 * cbytes, *rot1 = w0 + 5 * cbytes;       // (X^a - 1) * acc of the current step
-        if ((rc = ensure_plan(h, P))) return rc;
         if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;
         if ((rc = compact_poly(h, pp[1][1], d_acc1, count))) return rc;
         for (uint32_t s = 0; s < steps; s++) {

@@ -1,15 +1,22 @@
-// lds_launch.h -- host-side launch table for the LDS-resident kernels (one translation unit per
-// (field, log2 n) instance so the instances compile in parallel).
+// lds_launch.h -- host-side launch table for the LDS-resident kernels (one translation unit per (field, log2 n) instance so the
+// instances compile in parallel): the ops and forms with their names, where each form exists, and LdsArgs, the one launch request --
+// operands named by role, one layout flag per role.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace fhe_dev {
 
-enum LdsOp { LDS_FORWARD = 0, LDS_INVERSE = 1, LDS_MULTIPLY = 2, LDS_CT_MULTIPLY = 3, LDS_KEYSWITCH = 4, LDS_EXTPROD = 5,
-             // transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass over
-             // the top stages (r0 = dst, a0 = src) and the sub-transforms of the 2^top blocks (r0 = dst, a0 = src, b0 = second operand)
-             LDS_PASS_FWD = 6, LDS_PASS_INV = 7, LDS_SUB_FORWARD = 8, LDS_SUB_INVERSE = 9, LDS_SUB_MULTIPLY = 10 };
+// One list per enum: the enumerators and the names that the "no LDS kernel for ..." error prints come out of the same lines.
+// The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
+// over the top stages and the sub-transforms of the 2^top blocks
+#define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
+    X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") \
+    X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
+#define LDS_ENUMERATOR(id, name) id,
+#define LDS_NAME_CASE(id, name) case id: return name;
+enum LdsOp { LDS_OPS(LDS_ENUMERATOR) };
+constexpr const char *lds_op_name(int op) { switch (op) { LDS_OPS(LDS_NAME_CASE) } return "unknown"; }
 
 // Which kernel form runs an op is decided on the host, once, by the planner of transforms.hip (plan_*), which also says which library workspace
 // the form needs; the instance launches exactly that form or returns false.  The predicates below say where a form exists.
@@ -49,41 +56,47 @@ constexpr bool lds_small_multiply(int elem_bytes, int log_n) { return elem_bytes
 constexpr bool lds_coop4_multiply(int elem_bytes, int log_n) { return elem_bytes == 4 && (log_n == 13 || log_n == 14); }
 
 // The kernel form of LDS_MULTIPLY / LDS_CT_MULTIPLY / LDS_KEYSWITCH / LDS_EXTPROD (the other ops have one form each).
-enum LdsForm {
-    // LDS_MULTIPLY, LDS_CT_MULTIPLY
-    LDS_ONE_LAUNCH = 0,                  // one workgroup per limb polynomial, one launch
-    LDS_SQUARE,                          // the same with b == a: the squaring kernels (container outputs)
-    LDS_SMALL16,                         // few polynomials: the 16-per-thread latency kernels (tensor product: compact outputs)
-    LDS_COOP4,                           // a handful: four workgroups per limb polynomial, three launches, ws = 3 (multiply) / 7 (tensor product) compact polynomials per limb polynomial
-    LDS_TWO_LAUNCH,                      // tensor product: NTT(b0), NTT(b1) into ws (2 compact polynomials per limb polynomial), then the rest
-    LDS_THREE_LAUNCH,                    // tensor product where the one-launch kernel does not exist and no workspace is wanted
-    // LDS_KEYSWITCH, LDS_EXTPROD
-    LDS_SPLIT,                           // two workgroups per (ciphertext, limb), one per key half
-    LDS_JOINT3,                          // one workgroup per limb, three live arrays
-    LDS_PAIRED,                          // one workgroup per (ciphertext, limb), digit transforms two at a time
-    LDS_SINGLE_LDS_TW,                   // one workgroup per (ciphertext, limb), one digit transform at a time, twiddles in LDS
-    LDS_SINGLE_L2_TW,                    // ... twiddles read through L2
-    LDS_PARTS16,                         // one workgroup per digit (16-per-thread transforms) + a combining launch, ws = partial sums
-    LDS_PART_PAIRS,                      // one workgroup per digit PAIR (paired transforms) + a combining launch, ws = partial sums
-};
+#define LDS_FORMS(X) /* LDS_MULTIPLY, LDS_CT_MULTIPLY */ \
+    X(LDS_ONE_LAUNCH, "one-launch")              /* one workgroup per limb polynomial, one launch */ \
+    X(LDS_SQUARE, "square")                      /* the same with b == a: the squaring kernels (container outputs) */ \
+    X(LDS_SMALL16, "16-per-thread")              /* few polynomials: the 16-per-thread latency kernels (tensor product: compact outputs) */ \
+    X(LDS_COOP4, "four-workgroup")               /* a handful: four workgroups per limb polynomial, three launches, ws = 3 (multiply) / 7 (tensor product) compact polynomials per limb polynomial */ \
+    X(LDS_TWO_LAUNCH, "two-launch")              /* tensor product: NTT(b0), NTT(b1) into ws (2 compact polynomials per limb polynomial), then the rest */ \
+    X(LDS_THREE_LAUNCH, "three-launch")          /* tensor product where the one-launch kernel does not exist and no workspace is wanted */ \
+    /* LDS_KEYSWITCH, LDS_EXTPROD */ \
+    X(LDS_SPLIT, "split")                        /* two workgroups per (ciphertext, limb), one per key half */ \
+    X(LDS_JOINT3, "three-array")                 /* one workgroup per limb, three live arrays */ \
+    X(LDS_PAIRED, "paired")                      /* one workgroup per (ciphertext, limb), digit transforms two at a time */ \
+    X(LDS_SINGLE_LDS_TW, "single (LDS twiddles)")   /* one workgroup per (ciphertext, limb), one digit transform at a time, twiddles in LDS */ \
+    X(LDS_SINGLE_L2_TW, "single (L2 twiddles)")  /* ... twiddles read through L2 */ \
+    X(LDS_PARTS16, "per-digit parts")            /* one workgroup per digit (16-per-thread transforms) + a combining launch, ws = partial sums */ \
+    X(LDS_PART_PAIRS, "per-digit-pair parts")    /* one workgroup per digit PAIR (paired transforms) + a combining launch, ws = partial sums */
+enum LdsForm { LDS_FORMS(LDS_ENUMERATOR) };
+constexpr const char *lds_form_name(int form) { switch (form) { LDS_FORMS(LDS_NAME_CASE) } return "unknown"; }
 
+// One launch request.  The host fills the members that are operands of ITS op, by name (lds_args of engine.h sets the common ones from the
+// engine and the plan); everything else keeps its default.
 struct LdsArgs {
-    int op, form;
-    void *r0, *r1, *r2;                  // outputs (forward / inverse: r0 is the in-place buffer)
-    const void *a0, *a1, *b0, *b1;       // inputs
-    const void *limbs;                   // device array of Limb<F>
-    uint32_t L, polys;
-    hipStream_t stream;
-    // layout: compact polynomials (sizeof(residue) bytes per coefficient) instead of 32-byte containers
-    bool in_compact = false;             // every input a0, a1, b0, b1 is compact
-    bool out_compact = false;            // every output r0, r1, r2 is compact
+    int op = LDS_FORWARD, form = LDS_ONE_LAUNCH;
+    void *r0 = nullptr, *r1 = nullptr, *r2 = nullptr;   // outputs (forward / inverse: r0 is the in-place buffer; pass / sub: r0 = dst)
+    const void *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;   // inputs of multiply / tensor product (pass / sub: a0 = src, b0 = second operand)
+    // LDS_KEYSWITCH: r0 = add0 + c2 x kb, r1 = add1 + c2 x ka (no addends given: r0, r1 are accumulated in place)
+    const void *c2 = nullptr, *add0 = nullptr, *add1 = nullptr;
+    // LDS_EXTPROD (fused blind-rotation step): (r0, r1) = (a0, a1) + ExtProd((X^shift - 1) (a0, a1)); kb / ka = rows of component 0, kb1 / ka1 = rows
+    // of component 1; rot0, rot1 = (X^shift - 1) (a0, a1) where the loop pre-rotated them (always compact), else nullptr
+    const void *rot0 = nullptr, *rot1 = nullptr;
+    const void *limbs = nullptr;         // device array of Limb<F>
+    uint32_t L = 0, polys = 0;
+    hipStream_t stream = nullptr;
+    // Layout: compact polynomials (sizeof(residue) bytes per coefficient) instead of 32-byte containers.  Set by the host, from the plan,
+    // for every op; the instance never derives a layout from a pointer and refuses a combination it has no kernel for.
+    bool in_compact = false;             // what the workgroups transform: a0, a1, b0, b1 (LDS_EXTPROD: the accumulator pair a0, a1, which is its own
+                                         // addend; pass / sub: the source a0, b0); LDS_KEYSWITCH: the digit source c2
+    bool add_compact = false;            // LDS_KEYSWITCH: the addends add0, add1 (given, and beside a compact digit source only)
+    bool out_compact = false;            // every output r0, r1, r2
     void *ws = nullptr;                  // the form's workspace (LdsForm)
-    // LDS_KEYSWITCH: r0 += c2 x kb, r1 += c2 x ka with c2 = a0; a1, b0 = addends of r0, r1 (nullptr: r0, r1 are accumulated in place)
-    // LDS_EXTPROD (fused blind-rotation step): (r0, r1) = (a0, a1) + ExtProd((X^shift - 1) (a0, a1)); kb / ka = rows of component 0,
-    // kb1 / ka1 = rows of component 1, shifts = device array of per-ciphertext monomial exponents; b0, b1 = (X^shift - 1) (a0, a1) when the
-    // host pre-rotated them (compact), else nullptr
-    const void *kb = nullptr, *ka = nullptr, *kb1 = nullptr, *ka1 = nullptr;
-    const uint32_t *shifts = nullptr;
+    const void *kb = nullptr, *ka = nullptr, *kb1 = nullptr, *ka1 = nullptr;   // packed key tables / RGSW rows
+    const uint32_t *shifts = nullptr;    // LDS_EXTPROD: device array of per-ciphertext monomial exponents
     uint32_t K = 0, w = 0;
     uint32_t b_polys = 0;                // LDS_MULTIPLY: polynomials behind b0 (0 = as many as the batch; L = one RNS polynomial broadcast over the batch)
     uint32_t top = 0;                    // LDS_PASS_* / LDS_SUB_*: number of stages above the 2^13 blocks (log2 n = 13 + top)

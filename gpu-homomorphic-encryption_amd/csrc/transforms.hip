@@ -103,17 +103,13 @@ static int run256_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint
 // ---- LDS-resident path launchers (kernels live in lds_inst.hip, one object per (field, log2 n)) ---------
 // Two-pass transforms of the word-sized classes (log2 n = 13 + sub_top): one launch of the LOGN = 13 instance per pass.  Between the
 // two launches the polynomials are COMPACT (sizeof(residue) bytes per coefficient, d_ws3); *_compact tell which pointers are.
-static const char *const lds_op_name[] = {"forward", "inverse", "multiply", "tensor product", "key switch", "external product",
-                                          "pass forward", "pass inverse", "sub forward", "sub inverse", "sub multiply"};
-static const char *const lds_form_name[] = {"one-launch", "square", "16-per-thread", "four-workgroup", "two-launch", "three-launch", "split",
-                                            "three-array", "paired", "single (LDS twiddles)", "single (L2 twiddles)", "per-digit parts", "per-digit-pair parts"};
 int lds_launch(fhe_rns_ntt *h, const fhe_dev::LdsArgs &A, const char *what, int log_n) {
     if (!log_n) log_n = (int)h->log_n;
     fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), log_n);
     if (!fn) return fail(FHE_ERR_UNSUPPORTED, "transform size outside the LDS-resident range");
     if (!fn(A)) {
         char buf[256];
-        snprintf(buf, sizeof buf, "no LDS kernel for the %s in the %s form (%s inputs, %s outputs) at width %d, log2 N = %d", lds_op_name[A.op], lds_form_name[A.form],
+        snprintf(buf, sizeof buf, "no LDS kernel for the %s in the %s form (%s inputs, %s outputs) at width %d, log2 N = %d", fhe_dev::lds_op_name(A.op), fhe_dev::lds_form_name(A.form),
                  A.in_compact ? "compact" : "container", A.out_compact ? "compact" : "container", lds_width_id(h), log_n);
         return fail(FHE_ERR_UNSUPPORTED, buf);
     }
@@ -125,21 +121,23 @@ static int lds_big(fhe_rns_ntt *h, int op, void *dst, bool dst_compact, const vo
     const size_t dstep = (size_t)h->n * (dst_compact ? residue_bytes(h) : 32), sstep = (size_t)h->n * (src_compact ? residue_bytes(h) : 32);
     for (uint32_t done = 0; done < polys;) {
         const uint32_t chunk = polys - done < chunk_max ? polys - done : chunk_max;
-        fhe_dev::LdsArgs A{op, 0, (char *)dst + done * dstep, nullptr, nullptr, (const char *)src + done * sstep, nullptr,
-                           src2 ? (const char *)src2 + done * sstep : nullptr, nullptr, h->d_limbs, h->L, chunk, h->stream};
-        A.top = h->sub_top; A.rconst = rconst;
+        fhe_dev::LdsArgs A = lds_args(h, op, {}, chunk);
+        A.r0 = (char *)dst + done * dstep; A.a0 = (const char *)src + done * sstep; A.b0 = src2 ? (const char *)src2 + done * sstep : nullptr;
+        A.in_compact = src_compact; A.out_compact = dst_compact; A.top = h->sub_top; A.rconst = rconst;
         int rc = lds_launch(h, A, what, 13); if (rc) return rc;
         done += chunk;
     }
     return FHE_OK;
 }
+// forward / inverse: at the two-pass sizes the compact polynomials between the two launches
+WsNeed need_transform(const fhe_rns_ntt *h, size_t polys) { return {0, 0, h->sub_top ? polys * h->n * residue_bytes(h) : 0}; }
 static int big_forward(fhe_rns_ntt *h, void *dst, const void *src, uint32_t polys) {
-    int rc = ensure_ws3(h, (size_t)polys * h->n * residue_bytes(h)); if (rc) return rc;
+    int rc = ensure_need(h, need_transform(h, polys)); if (rc) return rc;
     if ((rc = lds_big(h, fhe_dev::LDS_PASS_FWD, h->d_ws3, true, src, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
     return lds_big(h, fhe_dev::LDS_SUB_FORWARD, dst, false, h->d_ws3, true, nullptr, polys, false, "ntt_sub_kernel");
 }
 static int big_inverse(fhe_rns_ntt *h, void *data, uint32_t polys) {
-    int rc = ensure_ws3(h, (size_t)polys * h->n * residue_bytes(h)); if (rc) return rc;
+    int rc = ensure_need(h, need_transform(h, polys)); if (rc) return rc;
     if ((rc = lds_big(h, fhe_dev::LDS_SUB_INVERSE, h->d_ws3, true, data, false, nullptr, polys, false, "ntt_sub_kernel"))) return rc;
     return lds_big(h, fhe_dev::LDS_PASS_INV, data, false, h->d_ws3, true, nullptr, polys, false, "word_pass_kernel");
 }
@@ -220,6 +218,8 @@ LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource 
     } else {
         p.form = fhe_dev::lds_twiddles_in_lds(eb, ln) && !h->env.global_twiddles ? fhe_dev::LDS_SINGLE_LDS_TW : fhe_dev::LDS_SINGLE_L2_TW;
     }
+    p.add_compact = src == KS_FUSED;
+    if (p.compact) p.ws2 = (src == KS_FUSED ? 3 : 1) * polys * h->n * eb;   // c0, c1, c2 of the fused tensor product (rotation: sigma(c0), sigma(c1), 0) / the compacted c2
     return p;
 }
 // External product of a blind-rotation loop over `polys` limb polynomials per accumulator component, K digits (the largest of the loop's rows).
@@ -256,15 +256,14 @@ LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K) {
     } else {
         p.form = fhe_dev::lds_twiddles_in_lds(eb, ln) && !h->env.global_twiddles ? fhe_dev::LDS_SINGLE_LDS_TW : fhe_dev::LDS_SINGLE_L2_TW;
     }
+    if (p.compact) p.ws2 = (p.prerot ? 6 : 4) * polys * h->n * eb;   // the ping-pong of compact accumulator pairs, and the pre-rotated pair of the current step
     return p;
 }
 
-// r = a * b on the LDS-resident sizes; b_polys: polynomials behind b (0 = as many as the batch, L = one RNS polynomial broadcast over the batch)
+// r = a * b on the LDS-resident sizes (the caller has ensured need_multiply); b_polys: polynomials behind b (0 = as many as the batch, L = one RNS polynomial broadcast over the batch)
 static int lds_multiply(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t polys, uint32_t b_polys) {
-    const LdsPlan P = plan_multiply(h, polys, a == b && !b_polys);
-    int rc = ensure_plan(h, P); if (rc) return rc;
-    fhe_dev::LdsArgs A{fhe_dev::LDS_MULTIPLY, P.form, r, nullptr, nullptr, a, nullptr, b, nullptr, h->d_limbs, h->L, polys, h->stream};
-    A.ws = plan_ws(h, P); A.b_polys = b_polys;
+    fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_MULTIPLY, plan_multiply(h, polys, a == b && !b_polys), polys);
+    A.r0 = r; A.a0 = a; A.b0 = b; A.b_polys = b_polys;
     return lds_launch(h, A, "ntt_multiply_kernel");
 }
 template <class F, int OP>
@@ -293,20 +292,15 @@ int compact_poly(fhe_rns_ntt *h, void *out, const void *in, size_t containers) {
 }
 
 
-int do_forward(fhe_rns_ntt *h, void *d_data, uint32_t batch) {
+static int do_transform(fhe_rns_ntt *h, void *d_data, uint32_t batch, bool fwd) {
     const uint32_t polys = batch * h->L;
-    if (h->sub_top) return big_forward(h, d_data, d_data, polys);
-    if (h->width != FHE_WIDTH_256)
-        return lds_launch(h, {fhe_dev::LDS_FORWARD, 0, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->d_limbs, h->L, polys, h->stream}, "ntt_forward_kernel");
-    return run256_transform(h, (fhe_dev::u256 *)d_data, polys, true);
+    if (h->sub_top) return fwd ? big_forward(h, d_data, d_data, polys) : big_inverse(h, d_data, polys);
+    if (h->width == FHE_WIDTH_256) return run256_transform(h, (fhe_dev::u256 *)d_data, polys, fwd);
+    fhe_dev::LdsArgs A = lds_args(h, fwd ? fhe_dev::LDS_FORWARD : fhe_dev::LDS_INVERSE, {}, polys); A.r0 = d_data;
+    return lds_launch(h, A, fwd ? "ntt_forward_kernel" : "ntt_inverse_kernel");
 }
-int do_inverse(fhe_rns_ntt *h, void *d_data, uint32_t batch) {
-    const uint32_t polys = batch * h->L;
-    if (h->sub_top) return big_inverse(h, d_data, polys);
-    if (h->width != FHE_WIDTH_256)
-        return lds_launch(h, {fhe_dev::LDS_INVERSE, 0, d_data, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->d_limbs, h->L, polys, h->stream}, "ntt_inverse_kernel");
-    return run256_transform(h, (fhe_dev::u256 *)d_data, polys, false);
-}
+int do_forward(fhe_rns_ntt *h, void *d_data, uint32_t batch) { return do_transform(h, d_data, batch, true); }
+int do_inverse(fhe_rns_ntt *h, void *d_data, uint32_t batch) { return do_transform(h, d_data, batch, false); }
 template <int OP>
 int do_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t batch, const char *what) {
     const uint32_t polys = batch * h->L;
@@ -328,7 +322,6 @@ static int wide_multiply_t(fhe_rns_ntt *h, void *d_r, const void *d_a, const voi
     const u256 *A = (const u256 *)d_a, *B = (const u256 *)d_b;
     if (!h->log_n) return run256_ew<0>(h, d_r, d_a, d_b, polys, "pointwise");     // degree 1: the product in Z_q
     if (top) {
-        int rc = ensure_ws(h, 2 * bytes); if (rc) return rc;
         u256 *wa = (u256 *)h->d_ws, *wb = (u256 *)((char *)h->d_ws + bytes);
         wide_forward_top<NL>(h, wa, A, polys);
         if (d_b != d_a) wide_forward_top<NL>(h, wb, B, polys);
@@ -349,9 +342,9 @@ static int wide_ct_multiply_t(fhe_rns_ntt *h, void *c0, void *c1, void *c2, cons
     using fhe_dev::u256;
     // 4 forward transforms into the workspace (no copies), one pass for the three NTT-domain products, 3 inverse transforms
     const size_t bytes = (size_t)polys * h->n * 32;
-    int rc = ensure_ws(h, 4 * bytes); if (rc) return rc;
     char *ws = (char *)h->d_ws;
     const void *src[4] = {a0, a1, b0, b1};
+    int rc;
     for (int i = 0; i < 4; i++)
         if ((rc = run256_transform(h, (u256 *)(ws + i * bytes), (const u256 *)src[i], polys, true, 0))) return rc;
     const size_t count = (size_t)polys * h->n;
@@ -362,13 +355,25 @@ static int wide_ct_multiply_t(fhe_rns_ntt *h, void *c0, void *c1, void *c2, cons
         if ((rc = run256_transform(h, (u256 *)c, (const u256 *)c, polys, false, 2))) return rc;
     return FHE_OK;
 }
+WsNeed need_multiply(const fhe_rns_ntt *h, uint32_t batch) {   // (no form's workspace depends on b == a)
+    const size_t polys = (size_t)batch * h->L;
+    if (h->sub_top) return {0, 0, 2 * polys * h->n * residue_bytes(h)};              // two compact operands
+    if (h->width != FHE_WIDTH_256) return plan_multiply(h, polys, false).need();
+    return {h->log_n && wide_top_stages(h) ? 2 * polys * h->n * 32 : 0, 0, 0};       // full width: both operands after their top forward stages
+}
+WsNeed need_ct_multiply(const fhe_rns_ntt *h, uint32_t batch, bool same_operands) {
+    const size_t polys = (size_t)batch * h->L;
+    if (h->sub_top) return WsNeed{5 * polys * h->n * 32, 0, 0} | need_transform(h, polys);   // 4 transformed operands + one product as containers
+    if (h->width != FHE_WIDTH_256) return plan_ct_multiply(h, polys, same_operands, false, true).need();
+    return {4 * polys * h->n * 32, 0, 0};                                            // full width: 4 transformed operands
+}
 static int do_multiply(fhe_rns_ntt *h, void *d_r, const void *d_a, const void *d_b, uint32_t batch) {
     const uint32_t polys = batch * h->L;
+    int rc = ensure_need(h, need_multiply(h, batch)); if (rc) return rc;
     // d_r may alias d_a and/or d_b, as in the reference (which copies its operands first, src/ntt.cu:50-58): every
     // workgroup loads both of its operand polynomials completely before its first store, and the general path works on copies.
     if (h->sub_top) {   // two-pass: the top stages of both operands go to the COMPACT workspace, one fused launch over the 2^13 blocks (compact in and out), last pass into the result
         const size_t cbytes = (size_t)polys * h->n * residue_bytes(h);
-        int rc = ensure_ws3(h, 2 * cbytes); if (rc) return rc;
         char *wa = (char *)h->d_ws3, *wb = d_b != d_a ? wa + cbytes : wa;
         if ((rc = lds_big(h, fhe_dev::LDS_PASS_FWD, wa, true, d_a, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
         if (d_b != d_a && (rc = lds_big(h, fhe_dev::LDS_PASS_FWD, wb, true, d_b, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
@@ -381,9 +386,9 @@ static int do_multiply(fhe_rns_ntt *h, void *d_r, const void *d_a, const void *d
 int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0,
                           const void *b1, uint32_t batch) {
     const uint32_t polys = batch * h->L;
+    int rc = ensure_need(h, need_ct_multiply(h, batch, a0 == b0 && a1 == b1)); if (rc) return rc;
     if (h->sub_top) {   // 4 forward transforms into the workspace, NTT-domain products on the field type, 3 inverse transforms
         const size_t bytes = (size_t)polys * h->n * 32;
-        int rc = ensure_ws(h, 5 * bytes); if (rc) return rc;
         char *ws = (char *)h->d_ws, *T = ws + 4 * bytes;
         const void *src[4] = {a0, a1, b0, b1};
         for (int i = 0; i < 4; i++) if ((rc = big_forward(h, ws + i * bytes, src[i], polys))) return rc;
@@ -396,35 +401,30 @@ int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0,
         return FHE_OK;
     }
     if (h->width != FHE_WIDTH_256) {
-        const LdsPlan P = plan_ct_multiply(h, polys, a0 == b0 && a1 == b1, false, true);
-        int rc = ensure_plan(h, P); if (rc) return rc;
-        fhe_dev::LdsArgs A{fhe_dev::LDS_CT_MULTIPLY, P.form, c0, c1, c2, a0, a1, b0, b1, h->d_limbs, h->L, polys, h->stream};
-        A.ws = plan_ws(h, P);
+        fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_CT_MULTIPLY, plan_ct_multiply(h, polys, a0 == b0 && a1 == b1, false, true), polys);
+        A.r0 = c0; A.r1 = c1; A.r2 = c2; A.a0 = a0; A.a1 = a1; A.b0 = b0; A.b1 = b1;
         return lds_launch(h, A, "ntt_ct_multiply_kernel");
     }
     return h->wide_nl == 2 ? wide_ct_multiply_t<2>(h, c0, c1, c2, a0, a1, b0, b1, polys) : wide_ct_multiply_t<4>(h, c0, c1, c2, a0, a1, b0, b1, polys);
 }
 
-extern "C" int fhe_rns_ntt_forward(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) {
-    int rc = check_call(h, batch, "forward"); if (rc) return rc;
-    if (!d_data) return fail(FHE_ERR_INVALID_ARG, "forward: null data");
-    if ((rc = check_aligned({d_data}, "forward"))) return rc;
+static int transform_call(fhe_rns_ntt *h, void *d_data, uint32_t batch, bool fwd, const char *what) {
+    int rc = check_call(h, batch, what); if (rc) return rc;
+    if (!d_data) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": null data");
+    if ((rc = check_aligned({d_data}, what))) return rc;
     if ((rc = check_inputs(h, {d_data}, batch))) return rc;
-    return do_forward(h, d_data, batch);
+    return do_transform(h, d_data, batch, fwd);
 }
-extern "C" int fhe_rns_ntt_inverse(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) {
-    int rc = check_call(h, batch, "inverse"); if (rc) return rc;
-    if (!d_data) return fail(FHE_ERR_INVALID_ARG, "inverse: null data");
-    if ((rc = check_aligned({d_data}, "inverse"))) return rc;
-    if ((rc = check_inputs(h, {d_data}, batch))) return rc;
-    return do_inverse(h, d_data, batch);
+extern "C" int fhe_rns_ntt_forward(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) { return transform_call(h, d_data, batch, true, "forward"); }
+extern "C" int fhe_rns_ntt_inverse(fhe_rns_ntt_t *h, void *d_data, uint32_t batch) { return transform_call(h, d_data, batch, false, "inverse"); }
+template <int OP>
+static int ew_call(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t batch, const char *what) {
+    int rc = check_call(h, batch, what); if (rc) return rc;
+    if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": null argument");
+    if ((rc = check_aligned({r, a, b}, what))) return rc;
+    return do_ew<OP>(h, r, a, b, batch, what);
 }
-extern "C" int fhe_rns_ntt_pointwise(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
-    int rc = check_call(h, batch, "pointwise"); if (rc) return rc;
-    if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "pointwise: null argument");
-    if ((rc = check_aligned({r, a, b}, "pointwise"))) return rc;
-    return do_ew<0>(h, r, a, b, batch, "pointwise");
-}
+extern "C" int fhe_rns_ntt_pointwise(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) { return ew_call<0>(h, r, a, b, batch, "pointwise"); }
 extern "C" int fhe_rns_ntt_multiply(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "multiply"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "multiply: null argument");
@@ -437,19 +437,16 @@ extern "C" int fhe_rns_ntt_multiply_bcast(fhe_rns_ntt_t *h, void *r, const void 
     if (!r || !a || !b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: null argument");
     if ((rc = check_aligned({r, a, b_one}, "multiply_bcast"))) return rc;
     if (r == b_one) return fail(FHE_ERR_INVALID_ARG, "multiply_bcast: the result must not overwrite the shared operand");
-    if (h->width != FHE_WIDTH_256 && !h->sub_top)   // every workgroup reads limb (p % L) of the one shared polynomial: L2 hits after the first use
+    if (h->width != FHE_WIDTH_256 && !h->sub_top) { // every workgroup reads limb (p % L) of the one shared polynomial: L2 hits after the first use
+        if ((rc = ensure_need(h, need_multiply(h, batch)))) return rc;
         return lds_multiply(h, r, a, b_one, batch * h->L, h->L);
+    }
     const size_t S = (size_t)h->L * h->n * 32;
     for (uint32_t i = 0; i < batch; i++)
         if ((rc = do_multiply(h, (char *)r + i * S, (const char *)a + i * S, b_one, 1))) return rc;
     return FHE_OK;
 }
-extern "C" int fhe_rns_poly_add(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
-    int rc = check_call(h, batch, "poly_add"); if (rc) return rc;
-    if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "poly_add: null argument");
-    if ((rc = check_aligned({r, a, b}, "poly_add"))) return rc;
-    return do_ew<1>(h, r, a, b, batch, "poly_add");
-}
+extern "C" int fhe_rns_poly_add(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) { return ew_call<1>(h, r, a, b, batch, "poly_add"); }
 extern "C" int fhe_rns_mul_mont_literal(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
     int rc = check_call(h, batch, "mul_mont_literal"); if (rc) return rc;
     if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "mul_mont_literal: null argument");
@@ -458,12 +455,7 @@ extern "C" int fhe_rns_mul_mont_literal(fhe_rns_ntt_t *h, void *r, const void *a
                                                                     "(an RNS base from fhe_rns_base_create, or FHE_HIP_FORCE_WIDTH=256)");
     return run256_ew<3>(h, r, a, b, batch * h->L, "mul_mont_literal");
 }
-extern "C" int fhe_rns_poly_sub(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) {
-    int rc = check_call(h, batch, "poly_sub"); if (rc) return rc;
-    if (!r || !a || !b) return fail(FHE_ERR_INVALID_ARG, "poly_sub: null argument");
-    if ((rc = check_aligned({r, a, b}, "poly_sub"))) return rc;
-    return do_ew<2>(h, r, a, b, batch, "poly_sub");
-}
+extern "C" int fhe_rns_poly_sub(fhe_rns_ntt_t *h, void *r, const void *a, const void *b, uint32_t batch) { return ew_call<2>(h, r, a, b, batch, "poly_sub"); }
 extern "C" int fhe_ct_multiply(fhe_rns_ntt_t *h, void *c0, void *c1, void *c2, const void *a0, const void *a1,
                                const void *b0, const void *b1, uint32_t batch) {
     int rc = check_call(h, batch, "ct_multiply"); if (rc) return rc;

@@ -1403,6 +1403,7 @@ def test_reserve_covers_every_entry_point(eng, monkeypatch, n, spec, w, batch, f
         e.ct_multiply(o[0], o[1], o[2], d[0], d[1], d[2], d[3], nb)
         e.relinearize(rk, o[0], o[1], o[2], nb)
         e.ct_multiply_relin(rk, o[0], o[1], d[0], d[1], d[2], d[3], nb)
+        e.apply_galois(rk, 3, o[0], o[1], d[0], d[1], nb)            # (the imported set serves as the Galois key: only growth is checked)
         sh = _up(eng, np.arange(3 * nb, dtype=np.uint32).reshape(3, nb) % (2 * n))
         e.blind_rotate([rk] * 3, [rk] * 3, d[0], d[1], sh, o[0], o[1], nb)
         assert e.workspace_bytes() == held, f"a call of {nb} units grew a workspace after reserve({batch})"
