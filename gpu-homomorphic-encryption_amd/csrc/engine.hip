@@ -41,6 +41,16 @@ static int build_limb_table(fhe_rns_ntt *h, const std::vector<Consts> &cs, void 
     }
     return upload(h, limbs, out);
 }
+// ... and a limb table without twiddle tables: fill(c, P) sets the constants of P (zeroed first)
+template <class LimbT, class Fill>
+static int build_limb_table(fhe_rns_ntt *h, const std::vector<Consts> &cs, void **out, Fill &&fill) {
+    std::vector<LimbT> limbs(h->L);
+    for (uint32_t l = 0; l < h->L; l++) {
+        std::memset(&limbs[l], 0, sizeof(LimbT));
+        fill(cs[l], limbs[l]);
+    }
+    return upload(h, limbs, out);
+}
 
 static int build_limbs(fhe_rns_ntt *h, const std::vector<Consts> &cs, fhe_dev::F32) {
     using Lm = fhe_dev::Limb32;
@@ -123,14 +133,11 @@ static int build_limbs(fhe_rns_ntt *h, const std::vector<Consts> &cs, fhe_dev::F
     });
 }
 
+// Constants of the container-level kernels of a full-width handle (ntt256.hip.h): radix R = 2^256, no twiddle tables
 static int build_limbs256(fhe_rns_ntt *h, const std::vector<Consts> &cs) {
     using Lm = fhe_dev::Limb256;
-    return build_limb_table<Lm>(h, cs, &h->d_limbs, &Lm::tw_m, &Lm::itw_m, [](const Consts &c, Lm &P, auto &tw, auto &itw) {
+    return build_limb_table<Lm>(h, cs, &h->d_limbs, [](const Consts &c, Lm &P) {
         fhe_host::Mod M(c.q);
-        for (size_t k = 0; k < tw.size(); k++) {
-            U256 a = M.to_mont(c.tw[k]), b = M.to_mont(c.itw[k]);
-            std::memcpy(tw[k].l, a.w, 32); std::memcpy(itw[k].l, b.w, 32);
-        }
         std::memcpy(P.q.l, c.q.w, 32);
         std::memcpy(P.r2.l, M.r2.w, 32);
         U256 nm = M.to_mont(c.n_inv);
@@ -139,7 +146,7 @@ static int build_limbs256(fhe_rns_ntt *h, const std::vector<Consts> &cs) {
     });
 }
 
-// Constants of the LDS-staged wide kernels (ntt_wide.hip.h): Montgomery radix R = 2^(64 NL).
+// Constants and twiddle tables of the full-width transforms (ntt_wide.hip.h): Montgomery radix R = 2^(64 NL).
 template <int NL>
 static int build_wlimbs(fhe_rns_ntt *h, const std::vector<Consts> &cs) {
     using W = fhe_dev::wint<NL>; using Lm = fhe_dev::WLimb<NL>;
@@ -255,7 +262,7 @@ int create_impl(fhe_rns_ntt **out, uint32_t n, const uint64_t (*moduli)[4], uint
         if (h->log_n > (h->width == FHE_WIDTH_32 ? 15u : 14u)) h->sub_top = h->log_n - 13;
     } else if (!(rc = build_limbs256(h, cs))) {
         h->wide_nl = (max_bits <= 127 && floor_w != 256) ? 2 : 4;
-        // six spare bits above the largest modulus: the tile kernels run their butterflies without full reductions (ntt_wide.hip.h: wct_l)
+        // six spare bits above the largest modulus: the tile kernels run their butterflies without full reductions (ntt_wide.hip.h: wbfly)
         h->wide_lazy = max_bits + 6 <= 64 * h->wide_nl && !h->env.no_wide_lazy;
         rc = h->wide_nl == 2 ? build_wlimbs<2>(h, cs) : build_wlimbs<4>(h, cs);
     }

@@ -1,19 +1,14 @@
-// ntt256.hip.h -- FHE_WIDTH_256 kernels: full-width (q < 2^255) negacyclic NTT and element-wise ops.
+// ntt256.hip.h -- FHE_WIDTH_256: the types shared by the container-level kernels of a full-width handle (q < 2^255, or any handle
+// where an entry point works on whole 32-byte containers: RNS entry / exit, mixed-class conversions).
 //
-// The general path behind NTTEngine / RNS_NTTEngine for moduli that do not fit the word-sized fast
-// paths (and for transform sizes outside 2^11..2^15).  It is built only from the reference's own
-// primitives (u256_dev.h: add_mod / sub_mod / mul_mod_montgomery / ct_butterfly / gs_butterfly,
-// include/bigint.cuh:27-140, include/ntt.cuh:147-167) with Montgomery-form twiddles, so data stays in
-// plain form exactly as in the reference.
+// A full-width engine keeps TWO limb tables.  Limb256 (here, h->d_limbs) holds the constants of the container-level kernels --
+// element-wise ops, canonical check, composed key switch, conversions -- which compute with mont_mul_fips / mont_mul of u256_dev.h at
+// the reference's radix R = 2^256 and leave data in plain form exactly as the reference does.  WLimb<NL> (ntt_wide.hip.h,
+// h->d_wlimbs) holds the constants and the twiddle tables of the transforms: global-memory passes over the top stages, LDS tiles of 2^11
+// coefficients below them, on the one-block products of wide_asm.inc at radix 2^(64 NL).  Limb256 has no twiddle tables of its own.
 //
-// Roofline note: one 256-bit Montgomery product is 128 v_mad_u64_u32 + 128 v_addc_co_u32 (hand-scheduled
-// mont_mul_fips, u256_dev.h); at ~14 integer MADs per byte of compulsory traffic this path is bound by
-// integer issue, not by HBM, so it runs as plain
-// multi-pass radix-2^R register kernels over global memory (R <= 3 stages per launch, every access a
-// whole 32-byte container, consecutive lanes on consecutive containers) without LDS staging.
-//
-// This file holds the types every part shares; the kernels are in ntt256_{transforms,literal,keyswitch,rns}.hip.h, one part per host
-// source, so that each kernel is compiled into exactly one object.
+// The kernels are in ntt256_{transforms,literal,keyswitch,rns}.hip.h, one part per host source, so that each kernel is compiled into
+// exactly one object.
 #pragma once
 #include "u256_dev.h"
 
@@ -25,9 +20,9 @@ struct Limb256 {
     u256 ninv_m;      // n^-1 * R mod q
     uint64_t inv0;    // -q^-1 mod 2^64  (MontgomeryParams::inv.limbs[0], include/bigint.cuh:167-173)
     uint64_t _pad;
-    const u256 *tw_m;   // [n] psi^bitrev(k) * R mod q
-    const u256 *itw_m;  // [n] psi^-bitrev(k) * R mod q
+    const void *_pad_tw[2];   // where two twiddle-table pointers were: sizeof(Limb256) and every offset stay as the kernels index them
 };
+static_assert(sizeof(Limb256) == 128 && alignof(Limb256) == 16, "the kernels index limbs[p % L] with this layout");
 
 // ---- RNS entry / exit (RNS_NTTEngine::to_rns / from_rns, include/ntt.cuh:114-117; src/rns.cu:93-141 are placeholders) ---
 // Container-level operations, independent of the width class of the transforms.

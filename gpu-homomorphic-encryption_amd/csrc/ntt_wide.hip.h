@@ -16,8 +16,13 @@
 //     4 S per transform instead of the 10 S of five un-staged passes.
 //   * Fused multiply (wide_tile_kernel<NL, TILE_MUL>): forward(a tile), forward(b tile), pointwise Montgomery product, inverse
 //     stages, one store -- no operand copies, no NTT-domain round trip: 3 S at N = 2^11, 9 S at N = 8192 (was 37 S).
-//   * The Montgomery product is finely integrated product scanning over 32-bit words on v_mad_u64_u32 with the carry-outs in
-//     SGPR pairs (mac1 / mac2 / mac3 in u256_dev.h): 2 NW^2 + NW multiplies for NW = 2 NL words.
+//   * Arithmetic: the generated asm blocks of wide_asm.inc (scripts/gen_wide_asm.py), each ONE inline-asm statement, for 4 and 8 32-bit
+//     words under one overloaded name.  wmontc is the whole canonical Montgomery product (2 NW^2 v_mad_u64_u32 for NW = 2 NL words, the
+//     carry-outs in SGPR pairs), wmontl the same without its closing subtraction, waddsub / wfree the butterfly tails, wcsub4 the
+//     reduction ladder of the lazy class.  Every kernel of this file computes with these and nothing else; mont_mul_fips / mont_mul of
+//     u256_dev.h (radix 2^256 on u256 containers) belong to the container-level kernels of ntt256_*.hip.h.
+//   * Files: wide_asm.inc = the blocks; this file = wint / WLimb, the butterflies, the pass kernel, the tile kernel and the three
+//     element-wise NTT-domain kernels; transforms.hip = their launchers (wide_pass, wide_tile, wide_*_t); engine.hip = build_wlimbs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,62 +50,14 @@ struct WLimb {
 };
 
 // a * b * R^-1 mod q, canonical, for a, b < q (odd, < 2^(64 NL - 1)), R = 2^(64 NL); qinv32 = -q^-1 mod 2^32.  The value
-// mul_mod_montgomery (include/bigint.cuh:76-140) returns with that radix.  Finely integrated product scanning over 32-bit
-// words: column k sums a_i b_(k-i) and m_i q_(k-i) in one asm block (wide_asm.inc: macn), m_k = column * qinv clears its low
-// word, and the words of the result are compared against q as they become final (macn_e), so the closing conditional
-// subtraction is two more steps and a select (wsel).
-template <int NL, int K>
-__device__ __forceinline__ void wmont_column(uint64_t &lo, uint32_t &hi, const uint32_t (&a)[2 * NL], const uint32_t (&b)[2 * NL], const uint32_t (&q)[2 * NL],
-                                             uint32_t (&m)[2 * NL], uint32_t (&t)[2 * NL], uint32_t (&tq)[2 * NL], uint64_t &bor, uint32_t qinv32) {
-    constexpr int NW = 2 * NL;
-    constexpr int CNT_AB = (K < NW ? K + 1 : 2 * NW - 1 - K), CNT_MQ = (K < NW ? K : 2 * NW - 1 - K), CNT = CNT_AB + CNT_MQ;
-    uint32_t xs[16], ys[16];
-    int cnt = 0;
-#pragma unroll
-    for (int i = 0; i < NW; i++) { const int j = K - i; if (j >= 0 && j < NW) { xs[cnt] = a[i]; ys[cnt] = b[j]; cnt++; } }
-#pragma unroll
-    for (int i = 0; i < NW; i++) { const int j = K - i; if (j >= 0 && j < NW && i < K) { xs[cnt] = m[i]; ys[cnt] = q[j]; cnt++; } }
-    if constexpr (K == NW + 1) macn_e0<CNT>(lo, hi, bor, tq[0], t[0], q[0], xs, ys);
-    else if constexpr (K > NW + 1) macn_e<CNT>(lo, hi, bor, tq[K - NW - 1], t[K - NW - 1], q[K - NW - 1], xs, ys);
-    else macn<CNT>(lo, hi, xs, ys);
-    if constexpr (K < NW) {
-        m[K] = (uint32_t)lo * qinv32;
-        macn_1(lo, hi, m[K], q[0]);                 // clears the low word of the column
-    } else {
-        t[K - NW] = (uint32_t)lo;
-    }
-    lo = (lo >> 32) | ((uint64_t)hi << 32);
-    hi = 0;
-    if constexpr (K + 1 < 2 * NW - 1) wmont_column<NL, K + 1>(lo, hi, a, b, q, m, t, tq, bor, qinv32);
-}
+// mul_mod_montgomery (include/bigint.cuh:76-140) returns with that radix, as one asm block (wide_asm.inc: wmontc).
 template <int NL>
 __device__ __forceinline__ wint<NL> wmont(const wint<NL> &a, const wint<NL> &b, const wint<NL> &q, uint32_t qinv32) {
-    constexpr int NW = 2 * NL;
     wint<NL> t;
-#ifndef FHE_WIDE_COLUMN_BLOCKS      // round 3: the whole product as ONE asm block (wide_asm.inc: wmontc); -DFHE_WIDE_COLUMN_BLOCKS restores one block per column
-    if constexpr (NL == 4) wmontc_8(t.w, a.w, b.w, q.w, qinv32); else wmontc_4(t.w, a.w, b.w, q.w, qinv32);
+    wmontc(t.w, a.w, b.w, q.w, qinv32);
     return t;
-#endif
-    uint32_t m[NW], tq[NW];
-    uint64_t lo = 0, bor = 0; uint32_t hi = 0;
-    wmont_column<NL, 0>(lo, hi, a.w, b.w, q.w, m, t.w, tq, bor, qinv32);
-    t.w[NW - 1] = (uint32_t)lo;                      // the sum is below 2q < 2^(32 NW): nothing above this word
-    if constexpr (NL == 4) wsel_8(t.w, tq, q.w, bor); else wsel_4(t.w, tq, q.w, bor);
-    return t;
-}
-template <int NL> __device__ __forceinline__ void waddsub(wint<NL> &a, wint<NL> &t, const wint<NL> &q) {
-    if constexpr (NL == 4) waddsub_8(a.w, t.w, q.w); else waddsub_4(a.w, t.w, q.w);
 }
 
-// ct_butterfly / gs_butterfly (include/ntt.cuh:147-167) on the radix-R product: (a, b) <- (a + b w, a - b w) / (a + b, (a - b) w)
-template <int NL> __device__ __forceinline__ void wct(wint<NL> &a, wint<NL> &b, const wint<NL> &w, const wint<NL> &q, uint32_t qi) {
-    b = wmont<NL>(b, w, q, qi);
-    waddsub<NL>(a, b, q);
-}
-template <int NL> __device__ __forceinline__ void wgs(wint<NL> &a, wint<NL> &b, const wint<NL> &w, const wint<NL> &q, uint32_t qi) {
-    waddsub<NL>(a, b, q);
-    b = wmont<NL>(b, w, q, qi);
-}
 // ---- the lazy class (round 3): q < 2^(64 NL - 6) ----------------------------------------------------------------------------------------
 // Six spare bits let a tile's forward transform run WITHOUT any reduction: with inputs below B q, T = b w R^-1 needs no closing subtraction
 // (T < q (1 + B q / R) < 2q), and (a, b) <- (a + T, a - T + 2q) stays below (B + 2) q: canonical input (B = 1), eleven stages -> below 23 q
@@ -110,7 +67,7 @@ template <int NL> __device__ __forceinline__ void wgs(wint<NL> &a, wint<NL> &b, 
 // product (input below 2q), and where there is none a ladder of conditional subtractions (16q, 8q, 4q, 2q, q) follows.
 template <int NL> __device__ __forceinline__ wint<NL> wmontl(const wint<NL> &a, const wint<NL> &b, const wint<NL> &q, uint32_t qinv32) {
     wint<NL> t;
-    if constexpr (NL == 4) wmontl_8(t.w, a.w, b.w, q.w, qinv32); else wmontl_4(t.w, a.w, b.w, q.w, qinv32);
+    wmontl(t.w, a.w, b.w, q.w, qinv32);
     return t;
 }
 template <int NL> __device__ __forceinline__ wint<NL> wshl(const wint<NL> &q, int s) {     // q << s, 0 <= s < 32 (the caller knows it fits)
@@ -124,22 +81,23 @@ template <int NL, int STEPS, int LAST = 0> __device__ __forceinline__ void wredu
 #pragma unroll
     for (int s = STEPS - 1; s >= LAST; s--) {
         const wint<NL> c = wshl<NL>(q, s);
-        if constexpr (NL == 4) { wcsub4_8(x[0].w, x[1].w, x[2].w, x[3].w, c.w); wcsub4_8(x[4].w, x[5].w, x[6].w, x[7].w, c.w); }
-        else { wcsub4_4(x[0].w, x[1].w, x[2].w, x[3].w, c.w); wcsub4_4(x[4].w, x[5].w, x[6].w, x[7].w, c.w); }
+        wcsub4(x[0].w, x[1].w, x[2].w, x[3].w, c.w); wcsub4(x[4].w, x[5].w, x[6].w, x[7].w, c.w);
     }
 }
-// forward: (a, b) <- (a + b w, a - b w + 2q), nothing reduced;  inverse: (a, b) <- (a + b mod 2q, (a - b mod 2q) w), inputs and outputs below 2q
-template <int NL> __device__ __forceinline__ void wct_l(wint<NL> &a, wint<NL> &b, const wint<NL> &w, const wint<NL> &q, const wint<NL> &q2, uint32_t qi) {
-    b = wmontl<NL>(b, w, q, qi);
-    if constexpr (NL == 4) wfree_8(a.w, b.w, q2.w); else wfree_4(a.w, b.w, q2.w);
-}
-template <int NL> __device__ __forceinline__ void wgs_l(wint<NL> &a, wint<NL> &b, const wint<NL> &w, const wint<NL> &q, const wint<NL> &q2, uint32_t qi) {
-    waddsub<NL>(a, b, q2);
-    b = wmontl<NL>(b, w, q, qi);
+// One butterfly on the radix-R product (ct_butterfly / gs_butterfly, include/ntt.cuh:147-167), q2 = q:
+//   forward (a, b) <- (a + b w, a - b w), inverse (a, b) <- (a + b, (a - b) w), canonical in and out;
+// and of the lazy class, q2 = 2q:
+//   forward (a, b) <- (a + b w, a - b w + 2q), nothing reduced; inverse (a, b) <- (a + b mod 2q, (a - b mod 2q) w), inputs and outputs below 2q.
+template <int NL, bool LZ, bool FWD>
+__device__ __forceinline__ void wbfly(wint<NL> &a, wint<NL> &b, const wint<NL> &w, const wint<NL> &q, const wint<NL> &q2, uint32_t qi) {
+    if constexpr (!FWD) waddsub(a.w, b.w, q2.w);
+    if constexpr (LZ) b = wmontl<NL>(b, w, q, qi); else b = wmont<NL>(b, w, q, qi);
+    if constexpr (FWD && LZ) wfree(a.w, b.w, q2.w);
+    else if constexpr (FWD) waddsub(a.w, b.w, q2.w);
 }
 
 // a + b mod q alone (tensor product): the butterfly tail on copies
-template <int NL> __device__ __forceinline__ wint<NL> waddmod(wint<NL> a, wint<NL> b, const wint<NL> &q) { waddsub<NL>(a, b, q); return a; }
+template <int NL> __device__ __forceinline__ wint<NL> waddmod(wint<NL> a, wint<NL> b, const wint<NL> &q) { waddsub(a.w, b.w, q.w); return a; }
 
 // 32-byte container <-> registers.  NL = 2 reads the low 16 bytes (the upper words of a canonical residue are zero) and
 // writes them back as zeros.
@@ -196,8 +154,7 @@ wide_pass_kernel(u256 *dst, const u256 *src, const WLimb<NL> *__restrict__ limbs
             const int k = ((hh >> pos) << (pos + 1)) | (hh & ((1 << pos) - 1));
             const uint32_t i = i0 + ((uint32_t)k << b_lo);
             const wint<NL> w = wload_t<NL>((FWD ? P.tw : P.itw) + (n >> (b + 1)) + (i >> (b + 1)));
-            if (FWD) wct<NL>(x[k], x[k | (1 << pos)], w, q, qi);
-            else wgs<NL>(x[k], x[k | (1 << pos)], w, q, qi);
+            wbfly<NL, false, FWD>(x[k], x[k | (1 << pos)], w, q, q, qi);
         }
     }
     if (!FWD && scale) {
@@ -246,80 +203,42 @@ __device__ __forceinline__ void wt_get(const uint32_t *lds, uint32_t tid, wint<N
     }
 }
 
-// One register group: r-bits KHI .. KLO of pattern B0 (tile-index bits B0+KHI .. B0+KLO), forward order (descending).
+// One butterfly stage in registers: r-bit K of pattern B0 (tile-index bit B0 + K), forward or inverse.  ibase = index of the thread's first
+// coefficient inside its polynomial.
+template <int NL, int B0, int K, bool LZ, bool FWD>
+__device__ __forceinline__ void wt_stage(wint<NL> (&x)[8], uint32_t ibase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
+    constexpr int b = B0 + K;
+    const wint<NL> *tw = (FWD ? P.tw : P.itw) + ((1u << (log_n - 1 - b)) + (ibase >> (b + 1)));
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if (r & (1 << K)) continue;
+        const wint<NL> w = wload_t<NL>(tw + (r >> (K + 1)));
+        wbfly<NL, LZ, FWD>(x[r], x[r | (1 << K)], w, q, q2, P.qinv32);
+    }
+}
+// One register group: the NK (2 or 3) low r-bits of pattern B0, descending (forward) or ascending (inverse).
 // gbase = index of the tile's first coefficient inside its polynomial.
-template <int NL, int B0, int K, bool LZ>
-__device__ __forceinline__ void wt_fwd_stage(wint<NL> (&x)[8], uint32_t ibase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
-    constexpr int b = B0 + K;
-    const wint<NL> *tw = P.tw + ((1u << (log_n - 1 - b)) + (ibase >> (b + 1)));
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        if (r & (1 << K)) continue;
-        const wint<NL> w = wload_t<NL>(tw + (r >> (K + 1)));
-        if constexpr (LZ) wct_l<NL>(x[r], x[r | (1 << K)], w, q, q2, P.qinv32);
-        else wct<NL>(x[r], x[r | (1 << K)], w, q, P.qinv32);
-    }
-}
-template <int NL, int B0, int K, bool LZ>
-__device__ __forceinline__ void wt_inv_stage(wint<NL> (&x)[8], uint32_t ibase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
-    constexpr int b = B0 + K;
-    const wint<NL> *tw = P.itw + ((1u << (log_n - 1 - b)) + (ibase >> (b + 1)));
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        if (r & (1 << K)) continue;
-        const wint<NL> w = wload_t<NL>(tw + (r >> (K + 1)));
-        if constexpr (LZ) wgs_l<NL>(x[r], x[r | (1 << K)], w, q, q2, P.qinv32);
-        else wgs<NL>(x[r], x[r | (1 << K)], w, q, P.qinv32);
-    }
-}
-template <int NL, int B0, int KHI, int KLO, bool LZ>
-__device__ __forceinline__ void wt_fwd_group(wint<NL> (&x)[8], uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
+template <int NL, int B0, int NK, bool LZ, bool FWD>
+__device__ __forceinline__ void wt_group(wint<NL> (&x)[8], uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
     const uint32_t ibase = gbase + wt_base<B0>(tid);
-    wt_fwd_stage<NL, B0, KHI, LZ>(x, ibase, log_n, P, q, q2);
-    if constexpr (KHI - 1 >= KLO) wt_fwd_stage<NL, B0, KHI - 1, LZ>(x, ibase, log_n, P, q, q2);
-    if constexpr (KHI - 2 >= KLO) wt_fwd_stage<NL, B0, KHI - 2, LZ>(x, ibase, log_n, P, q, q2);
+    wt_stage<NL, B0, FWD ? NK - 1 : 0, LZ, FWD>(x, ibase, log_n, P, q, q2);
+    wt_stage<NL, B0, FWD ? NK - 2 : 1, LZ, FWD>(x, ibase, log_n, P, q, q2);
+    if constexpr (NK == 3) wt_stage<NL, B0, FWD ? 0 : 2, LZ, FWD>(x, ibase, log_n, P, q, q2);
 }
-template <int NL, int B0, int KLO, int KHI, bool LZ>
-__device__ __forceinline__ void wt_inv_group(wint<NL> (&x)[8], uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
-    const uint32_t ibase = gbase + wt_base<B0>(tid);
-    wt_inv_stage<NL, B0, KLO, LZ>(x, ibase, log_n, P, q, q2);
-    if constexpr (KLO + 1 <= KHI) wt_inv_stage<NL, B0, KLO + 1, LZ>(x, ibase, log_n, P, q, q2);
-    if constexpr (KLO + 2 <= KHI) wt_inv_stage<NL, B0, KLO + 2, LZ>(x, ibase, log_n, P, q, q2);
-}
-
-// the low 11 stages of a forward transform: coefficients in pattern 8 (coalesced order) -> values in pattern 0 (8 consecutive per thread)
-template <int NL, bool LZ>
-__device__ __forceinline__ void wt_forward(wint<NL> (&x)[8], uint32_t *lds, uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
-    wt_fwd_group<NL, 8, 2, 0, LZ>(x, tid, gbase, log_n, P, q, q2);          // tile bits 10, 9, 8
-    wt_put<NL, 8>(lds, tid, x);
-    __syncthreads();
-    wt_get<NL, 5>(lds, tid, x);
-    wt_fwd_group<NL, 5, 2, 0, LZ>(x, tid, gbase, log_n, P, q, q2);          // 7, 6, 5
-    wt_put<NL, 5>(lds, tid, x);                                     // the slots this thread just read: no barrier needed before
-    __syncthreads();
-    wt_get<NL, 2>(lds, tid, x);
-    wt_fwd_group<NL, 2, 2, 0, LZ>(x, tid, gbase, log_n, P, q, q2);          // 4, 3, 2
-    wt_put<NL, 2>(lds, tid, x);
-    __syncthreads();
-    wt_get<NL, 0>(lds, tid, x);
-    wt_fwd_group<NL, 0, 1, 0, LZ>(x, tid, gbase, log_n, P, q, q2);          // 1, 0
-}
-// the low 11 stages of an inverse transform: values in pattern 0 -> coefficients in pattern 8
-template <int NL, bool LZ>
-__device__ __forceinline__ void wt_inverse(wint<NL> (&x)[8], uint32_t *lds, uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
-    wt_inv_group<NL, 0, 0, 1, LZ>(x, tid, gbase, log_n, P, q, q2);          // tile bits 0, 1
-    wt_put<NL, 0>(lds, tid, x);
-    __syncthreads();
-    wt_get<NL, 2>(lds, tid, x);
-    wt_inv_group<NL, 2, 0, 2, LZ>(x, tid, gbase, log_n, P, q, q2);          // 2, 3, 4
-    wt_put<NL, 2>(lds, tid, x);
-    __syncthreads();
-    wt_get<NL, 5>(lds, tid, x);
-    wt_inv_group<NL, 5, 0, 2, LZ>(x, tid, gbase, log_n, P, q, q2);          // 5, 6, 7
-    wt_put<NL, 5>(lds, tid, x);
-    __syncthreads();
-    wt_get<NL, 8>(lds, tid, x);
-    wt_inv_group<NL, 8, 0, 2, LZ>(x, tid, gbase, log_n, P, q, q2);          // 8, 9, 10
+// The low 11 stages of a transform.  Forward: coefficients in pattern 8 (coalesced order) -> values in pattern 0 (8 consecutive per thread), as
+// register groups on tile bits (10, 9, 8), (7, 6, 5), (4, 3, 2), (1, 0) with an exchange through LDS between two groups.  Inverse: the same
+// schedule walked backwards, values in pattern 0 -> coefficients in pattern 8.  STEP = how many groups are done.
+template <int NL, bool LZ, bool FWD, int STEP = 0>
+__device__ __forceinline__ void wt_transform(wint<NL> (&x)[8], uint32_t *lds, uint32_t tid, uint32_t gbase, uint32_t log_n, const WLimb<NL> &P, const wint<NL> &q, const wint<NL> &q2) {
+    constexpr int PAT[4] = {8, 5, 2, 0};
+    constexpr int B0 = PAT[FWD ? STEP : 3 - STEP];
+    wt_group<NL, B0, B0 ? 3 : 2, LZ, FWD>(x, tid, gbase, log_n, P, q, q2);
+    if constexpr (STEP < 3) {
+        wt_put<NL, B0>(lds, tid, x);                                // from the second exchange on: the slots this thread just read, no barrier needed before
+        __syncthreads();
+        wt_get<NL, PAT[FWD ? STEP + 1 : 2 - STEP]>(lds, tid, x);
+        wt_transform<NL, LZ, FWD, STEP + 1>(x, lds, tid, gbase, log_n, P, q, q2);
+    }
 }
 
 enum { TILE_FWD = 0, TILE_INV = 1, TILE_MUL = 2 };
@@ -330,7 +249,7 @@ enum { TILE_FWD = 0, TILE_INV = 1, TILE_MUL = 2 };
 //   TILE_MUL : dst tile = inverse stages of (forward(src tile) .* forward(src2 tile)); the result carries R^-1 until the scaling
 //              by n^-1 R^2 (here when n = 2^11, else in the inverse top pass)
 // dst may alias src / src2 tile for tile: every workgroup loads its tiles completely before its first store.
-// LZ: the lazy class (every q < 2^(64 NL - 6), see wct_l): same inputs, same canonical outputs, fewer instructions in between.
+// LZ: the lazy class (every q < 2^(64 NL - 6), see wbfly): same inputs, same canonical outputs, fewer instructions in between.
 template <int NL, int MODE, bool LZ>
 __global__ void __launch_bounds__(WT_T, 2)
 wide_tile_kernel(u256 *dst, const u256 *src, const u256 *src2, const WLimb<NL> *__restrict__ limbs, uint32_t L, uint32_t log_n, uint32_t scale) {
@@ -346,7 +265,7 @@ wide_tile_kernel(u256 *dst, const u256 *src, const u256 *src2, const WLimb<NL> *
 #pragma unroll
     for (int r = 0; r < 8; r++) x[r] = wload_c<NL>(src + off + tid + r * WT_T);
     if constexpr (MODE == TILE_FWD) {
-        wt_forward<NL, LZ>(x, lds, tid, gbase, log_n, P, q, q2);
+        wt_transform<NL, LZ, true>(x, lds, tid, gbase, log_n, P, q, q2);
         if constexpr (LZ) wreduce<NL, 5>(x, q);                     // below 23 q -> canonical
         wt_put<NL, 0>(lds, tid, x);
         __syncthreads();
@@ -355,14 +274,14 @@ wide_tile_kernel(u256 *dst, const u256 *src, const u256 *src2, const WLimb<NL> *
         wt_put<NL, 8>(lds, tid, x);
         __syncthreads();
         wt_get<NL, 0>(lds, tid, x);
-        wt_inverse<NL, LZ>(x, lds, tid, gbase, log_n, P, q, q2);
+        wt_transform<NL, LZ, false>(x, lds, tid, gbase, log_n, P, q, q2);
     } else {
         wint<NL> y[8];
 #pragma unroll
         for (int r = 0; r < 8; r++) y[r] = wload_c<NL>(src2 + off + tid + r * WT_T);   // issued early: hides under a's butterflies
-        wt_forward<NL, LZ>(x, lds, tid, gbase, log_n, P, q, q2);
+        wt_transform<NL, LZ, true>(x, lds, tid, gbase, log_n, P, q, q2);
         __syncthreads();                                            // a's last exchange reads are over before b's first put
-        wt_forward<NL, LZ>(y, lds, tid, gbase, log_n, P, q, q2);
+        wt_transform<NL, LZ, true>(y, lds, tid, gbase, log_n, P, q, q2);
         if constexpr (LZ) {                                         // x < 23 q, y < 23 q -> y < 2q: the product is below q (1 + 46 q / R) < 2q
             wreduce<NL, 5, 1>(y, q);
 #pragma unroll
@@ -371,7 +290,7 @@ wide_tile_kernel(u256 *dst, const u256 *src, const u256 *src2, const WLimb<NL> *
 #pragma unroll
             for (int r = 0; r < 8; r++) x[r] = wmont<NL>(x[r], y[r], q, P.qinv32);
         }
-        wt_inverse<NL, LZ>(x, lds, tid, gbase, log_n, P, q, q2);    // starts in the pattern both transforms ended in: no exchange
+        wt_transform<NL, LZ, false>(x, lds, tid, gbase, log_n, P, q, q2);    // starts in the pattern both transforms ended in: no exchange
     }
     if (MODE != TILE_FWD && scale) {                                // canonical product: input below 2q (lazy) or q
         const wint<NL> c = scale == 2 ? P.ninv_r2 : P.ninv_m;

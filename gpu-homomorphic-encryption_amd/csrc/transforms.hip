@@ -6,19 +6,16 @@
 #include "ntt_wide.hip.h"
 #include "ntt_word.hip.h"
 
-// ---- general (256-bit) path launchers -----------------------------------------------------------------
-// One radix-2^R global-memory pass over `polys` polynomials (src -> dst).  forward: stages s0 .. s0+R-1; inverse: index bits s0 .. s0+R-1.
+// ---- full-width launchers (kernels: ntt_wide.hip.h; container-level element-wise ops: ntt256_transforms.hip.h) ---------------------------------
+// One radix-2^R (R = 1 .. 3) global-memory pass over `polys` polynomials (src -> dst).  forward: stages s0 .. s0+R-1; inverse: index bits s0 .. s0+R-1.
 template <int NL, bool FWD>
 static void wide_pass(fhe_rns_ntt *h, fhe_dev::u256 *dst, const fhe_dev::u256 *src, uint32_t polys, uint32_t s0, uint32_t R, uint32_t scale) {
     const uint32_t chunk_max = (65535u / h->L) * h->L;      // grid.y limit; chunks keep the limb phase (polynomial index mod L)
-    const fhe_dev::WLimb<NL> *limbs = (const fhe_dev::WLimb<NL> *)h->d_wlimbs;
+    decltype(&fhe_dev::wide_pass_kernel<NL, 3, FWD>) const kernels[3] = {fhe_dev::wide_pass_kernel<NL, 3, FWD>, fhe_dev::wide_pass_kernel<NL, 2, FWD>, fhe_dev::wide_pass_kernel<NL, 1, FWD>};
     for (uint32_t done = 0; done < polys;) {
         const uint32_t chunk = polys - done < chunk_max ? polys - done : chunk_max;
-        fhe_dev::u256 *d = dst + (size_t)done * h->n; const fhe_dev::u256 *sp = src + (size_t)done * h->n;
-        dim3 grid(((h->n >> R) + 255) / 256, chunk), block(256);
-        if (R == 3) hipLaunchKernelGGL((fhe_dev::wide_pass_kernel<NL, 3, FWD>), grid, block, 0, h->stream, d, sp, limbs, h->L, h->log_n, s0, scale);
-        else if (R == 2) hipLaunchKernelGGL((fhe_dev::wide_pass_kernel<NL, 2, FWD>), grid, block, 0, h->stream, d, sp, limbs, h->L, h->log_n, s0, scale);
-        else hipLaunchKernelGGL((fhe_dev::wide_pass_kernel<NL, 1, FWD>), grid, block, 0, h->stream, d, sp, limbs, h->L, h->log_n, s0, scale);
+        const size_t o = (size_t)done * h->n;
+        hipLaunchKernelGGL(kernels[3 - R], dim3(((h->n >> R) + 255) / 256, chunk), dim3(256), 0, h->stream, dst + o, src + o, (const fhe_dev::WLimb<NL> *)h->d_wlimbs, h->L, h->log_n, s0, scale);
         done += chunk;
     }
 }
@@ -26,15 +23,12 @@ template <int NL, int MODE>
 static void wide_tile(fhe_rns_ntt *h, fhe_dev::u256 *dst, const fhe_dev::u256 *src, const fhe_dev::u256 *src2, uint32_t polys, uint32_t scale) {
     const uint32_t tiles_log = h->log_n - fhe_dev::WT_LOG;
     const uint32_t chunk_max = (0x7fffffffu >> tiles_log) / h->L * h->L;
+    const auto kernel = h->wide_lazy ? fhe_dev::wide_tile_kernel<NL, MODE, true> : fhe_dev::wide_tile_kernel<NL, MODE, false>;
     for (uint32_t done = 0; done < polys;) {
         const uint32_t chunk = polys - done < chunk_max ? polys - done : chunk_max;
         const size_t o = (size_t)done * h->n;
-        if (h->wide_lazy)
-            hipLaunchKernelGGL((fhe_dev::wide_tile_kernel<NL, MODE, true>), dim3(chunk << tiles_log), dim3(fhe_dev::WT_T), 0, h->stream, dst + o, src + o,
-                               src2 ? src2 + o : nullptr, (const fhe_dev::WLimb<NL> *)h->d_wlimbs, h->L, h->log_n, scale);
-        else
-            hipLaunchKernelGGL((fhe_dev::wide_tile_kernel<NL, MODE, false>), dim3(chunk << tiles_log), dim3(fhe_dev::WT_T), 0, h->stream, dst + o, src + o,
-                               src2 ? src2 + o : nullptr, (const fhe_dev::WLimb<NL> *)h->d_wlimbs, h->L, h->log_n, scale);
+        hipLaunchKernelGGL(kernel, dim3(chunk << tiles_log), dim3(fhe_dev::WT_T), 0, h->stream, dst + o, src + o, src2 ? src2 + o : nullptr,
+                           (const fhe_dev::WLimb<NL> *)h->d_wlimbs, h->L, h->log_n, scale);
         done += chunk;
     }
 }

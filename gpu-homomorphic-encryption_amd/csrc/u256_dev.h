@@ -1,13 +1,16 @@
-// u256_dev.h -- 256-bit modular arithmetic for gfx950 (full-width path, FHE_WIDTH_256).
+// u256_dev.h -- 256-bit modular arithmetic on 32-byte containers for gfx950: what the container-level kernels of a full-width
+// handle (FHE_WIDTH_256) compute with.
 //
-// Semantics are the reference's, bit for bit (include/bigint.cuh:27-140), including the top-limb
-// borrow test and the lost carry out of the 512-bit accumulator, so the element-wise
-// kernels reproduce the reference primitives even on unreduced operands.
-//
-// Where the reference chains PTX add.cc / addc / madc through the implicit carry flag
-// (kernels/ptx_bigint.cuh:34-117), this code keeps every limb as 2 x 32-bit VGPRs and lets the
-// 64x64->128 products lower to v_mad_u64_u32 with v_add_co_u32 / v_addc_co_u32 carry chains
-// (checked with `hipcc -S`: see DESIGN.md "ISA check").  No MFMA: integer modular arithmetic.
+//   * add_mod / sub_mod / mont_mul: the reference's semantics bit for bit (include/bigint.cuh:27-140), including the top-limb borrow
+//     test and the lost carry out of the 512-bit accumulator, so the literal kernels (ntt256_literal.hip.h, OP 3 of
+//     ew256_rns_kernel) and the conversion kernels (ntt256_rns.hip.h) reproduce the reference primitives even on unreduced operands.  Where the reference chains PTX add.cc / addc /
+//     madc through the implicit carry flag (kernels/ptx_bigint.cuh:34-117), every limb here is 2 x 32-bit VGPRs and the 64x64->128
+//     products lower to v_mad_u64_u32 with v_add_co_u32 / v_addc_co_u32 carry chains (DESIGN.md "ISA check").
+//   * mont_mul_fips (on mac1 / mac2 / mac3): the hand-scheduled R = 2^256 product for reduced operands.  It serves ew256_rns_kernel
+//     (OP 0) and relin_mac256_kernel (ntt256_keyswitch.hip.h).
+//   * load_u256 / store_u256: a container as two 16-byte accesses.
+// The full-width TRANSFORMS use neither product: their butterflies are the one-block products of wide_asm.inc (wmontc / wmontl, radix
+// 2^(64 NL)), see ntt_wide.hip.h.  No MFMA anywhere: integer modular arithmetic.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,7 +107,7 @@ __device__ __forceinline__ u256 mont_mul(const u256 &a, const u256 &b, const u25
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Hand-scheduled Montgomery product for the NTT passes (odd q, exact inv0): finely integrated product scanning over
+// Hand-scheduled Montgomery product for reduced operands (odd q, exact inv0): finely integrated product scanning over
 // eight 32-bit words.  Every 32x32 product is one v_mad_u64_u32 into a 64-bit column accumulator whose carry-out goes
 // to its own SGPR pair and is folded into a third accumulator word by v_addc_co_u32.  On gfx950 a VALU read of an SGPR
 // (incl. VCC) written by the previous VALU instruction needs two wait states -- the compiler pads its own carry chains
@@ -190,31 +193,6 @@ __device__ __forceinline__ u256 mont_mul_fips(const u256 &a_, const u256 &b_, co
 #pragma unroll
     for (int i = 0; i < 4; i++) r.l[i] = underflow ? u.l[i] : d.l[i];
     return r;
-}
-
-// include/ntt.cuh:147-155
-__device__ __forceinline__ void ct_butterfly(u256 &a, u256 &b, const u256 &w, const u256 &q, uint64_t inv0) {
-    u256 t = mont_mul(b, w, q, inv0);
-    b = sub_mod(a, t, q);
-    a = add_mod(a, t, q);
-}
-// include/ntt.cuh:158-167
-__device__ __forceinline__ void gs_butterfly(u256 &a, u256 &b, const u256 &w, const u256 &q, uint64_t inv0) {
-    u256 s = add_mod(a, b, q);
-    b = mont_mul(sub_mod(a, b, q), w, q, inv0);
-    a = s;
-}
-
-// the same butterflies on the hand-scheduled product (NTT passes; q odd prime, inv0 exact)
-__device__ __forceinline__ void ct_butterfly_fast(u256 &a, u256 &b, const u256 &w, const u256 &q, uint32_t qinv32) {
-    u256 t = mont_mul_fips(b, w, q, qinv32);
-    b = sub_mod(a, t, q);
-    a = add_mod(a, t, q);
-}
-__device__ __forceinline__ void gs_butterfly_fast(u256 &a, u256 &b, const u256 &w, const u256 &q, uint32_t qinv32) {
-    u256 s = add_mod(a, b, q);
-    b = mont_mul_fips(sub_mod(a, b, q), w, q, qinv32);
-    a = s;
 }
 
 // 32-byte container <-> registers: two 16-byte accesses per lane.
