@@ -30,17 +30,21 @@ int ensure_crt(fhe_rns_ntt *h) {
     for (uint32_t l = 0; l < L; l++) {
         fhe_host::Mod M(h->moduli[l]);
         std::memcpy(limbs[l].q.l, M.q.w, 32); std::memcpy(limbs[l].r2.l, M.r2.w, 32); limbs[l].inv0 = M.inv0;
+        // ((Q/q)^-1 mod q) * R from the other primes modulo q: the fast base conversion needs it for ANY basis, also one whose product Q
+        // does not fit a container (only from_rns needs Q itself)
+        U256 Mi_m = M.r1;
+        for (uint32_t k = 0; k < L; k++) if (k != l) Mi_m = M.mont(Mi_m, M.to_mont(M.reduce(h->moduli[k])));
+        U256 qm2; fhe_host::sub_to(qm2, M.q, U256(2));
+        const U256 minv_m = M.pow_m(Mi_m, qm2);
+        std::memcpy(limbs[l].minv_m.l, minv_m.w, 32);
     }
     if (fits) {
         fhe_host::Mod MQ(Q);
         for (uint32_t l = 0; l < L; l++) {
             U256 Mi(1);
             for (uint32_t k = 0; k < L; k++) if (k != l) { U256 t; mul_checked(t, Mi, h->moduli[k]); Mi = t; }
-            fhe_host::Mod M(h->moduli[l]);
-            U256 qm2; fhe_host::sub_to(qm2, M.q, U256(2));
-            U256 minv_m = M.pow_m(M.to_mont(M.reduce(Mi)), qm2);                 // ((Q/q)^-1 mod q) * R
-            U256 Mi_mQ = MQ.to_mont(Mi);
-            std::memcpy(limbs[l].minv_m.l, minv_m.w, 32); std::memcpy(limbs[l].Mi_mQ.l, Mi_mQ.w, 32);
+            const U256 Mi_mQ = MQ.to_mont(Mi);
+            std::memcpy(limbs[l].Mi_mQ.l, Mi_mQ.w, 32);
         }
         std::memcpy(h->crt_big.Q.l, Q.w, 32); h->crt_big.inv0 = MQ.inv0; h->crt_big._pad = 0;
     }

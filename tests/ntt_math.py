@@ -105,6 +105,77 @@ def largest_ntt_primes(bits, n, count):
     return out
 
 
+def words32(q):
+    """q as little-endian 32-bit words, up to and including its top non-zero word."""
+    return [(q >> (32 * i)) & 0xFFFFFFFF for i in range((q.bit_length() + 31) // 32)]
+
+
+def has_generic_words(q):
+    """Every 32-bit word of q below its top word is neither 0 nor 0xFFFFFFFF: no term m_i * q_j of a word-wise Montgomery product is
+    a product by zero, and no borrow or carry passes a word of q for free."""
+    return all(w not in (0, 0xFFFFFFFF) for w in words32(q)[:-1])
+
+
+def generic_ntt_primes(bits, n, count, seed):
+    """`count` distinct primes of exactly `bits` bits with q = 1 (mod 2n) and generic words (has_generic_words), drawn from
+    random.Random(seed): deterministic for a seed.  ntt_primes / largest_ntt_primes return 2^(bits-1) + small and 2^bits - small, whose
+    middle words are all zeros or all ones; these are the moduli in between."""
+    rng = random.Random(seed)
+    out, step = [], 2 * n
+    while len(out) < count:
+        k = rng.getrandbits(bits) | (1 << (bits - 1))
+        q = (k // step) * step + 1
+        if q.bit_length() == bits and has_generic_words(q) and q not in out and is_prime(q):
+            out.append(q)
+    return out
+
+
+GENERIC_BITS = (65, 100, 127, 128, 129, 192, 193, 250, 255)     # see full_width_moduli
+_FULL_WIDTH_SETS = {}
+
+
+def full_width_moduli(name, n):
+    """The moduli sets of the full-width class tests (FHE_WIDTH_256), cached per (name, n).
+      'g<bits>'  two generic primes of that width.  65 is the first width above the word-sized classes; 127 the top of the two-limb
+                 transforms and 128 the bottom of the four-limb ones; 128 / 129 and 192 / 193 put q's top bit at the top of a 64-bit limb
+                 or at the bottom of the next; 250 and 255 are the lazy and the canonical tops.
+      't<bits>'  the two largest primes below 2^bits (127, 128, 255): sums at the container limit.
+      'g85x3'    three generic 85-bit primes whose product has 255 bits, the largest a CRT result may have (the first seed from 85 that gives one).
+      'mixed-a'  generic 250-bit + generic 100-bit + the smallest 60-bit prime: a full-width basis that also holds a limb below 2^64.
+      'mixed-b'  generic 127-bit + generic 122-bit: a two-limb basis that is not lazy (the widest modulus decides)."""
+    key = (name, n)
+    if key not in _FULL_WIDTH_SETS:
+        if name == "mixed-a":
+            qs = generic_ntt_primes(250, n, 1, 250) + generic_ntt_primes(100, n, 1, 100) + ntt_primes(60, n, 1)
+        elif name == "mixed-b":
+            qs = generic_ntt_primes(127, n, 1, 127) + generic_ntt_primes(122, n, 1, 122)
+        elif name == "g85x3":
+            seed = 85
+            while True:
+                qs = generic_ntt_primes(85, n, 3, seed)
+                if (qs[0] * qs[1] * qs[2]).bit_length() == 255:
+                    break
+                seed += 1
+        elif name[0] == "g":
+            qs = generic_ntt_primes(int(name[1:]), n, 2, int(name[1:]))
+        else:
+            assert name[0] == "t", name
+            qs = largest_ntt_primes(int(name[1:]), n, 2)
+            assert all(q.bit_length() == int(name[1:]) for q in qs)
+        _FULL_WIDTH_SETS[key] = qs
+    return list(_FULL_WIDTH_SETS[key])
+
+
+def base_conversion_case(case, n):
+    """(source moduli, target moduli) of the fast base conversions that involve a full-width basis."""
+    if case == "g250->g127+p60":
+        return full_width_moduli("g250", n), full_width_moduli("g127", n)[:1] + ntt_primes(60, n, 1)
+    if case == "g127x2->g255":
+        return full_width_moduli("g127", n), full_width_moduli("g255", n)
+    assert case == "p60x3->g250", case
+    return ntt_primes(60, n, 3), full_width_moduli("g250", n)
+
+
 def find_psi(n, q):
     """Same rule as the engine and the oracle: first x^((q-1)/2n), x = 2,3,..., of order exactly 2n."""
     e = (q - 1) // (2 * n)

@@ -610,3 +610,175 @@ def test_oracle_relinearize_at_the_top_primes_matches_big_integers(oracle, bits,
                     want0[i] = [(u + v) % q for u, v in zip(want0[i], pb)]
                     want1[i] = [(u + v) % q for u, v in zip(want1[i], pa)]
         assert g0[bi] == want0 and g1[bi] == want1, bi
+
+
+# ---------------------------------------------------------------------------------- full-width class: generic moduli
+# The GPU tests of tests/test_full_width_moduli.py compare the full-width kernels with this oracle on moduli whose 32-bit words are all
+# generic (ntt_math.generic_ntt_primes); here the oracle itself is checked on such moduli against Python integers, at n = 64.
+FULL_WIDTH_SETS = ("g127", "g128", "g255", "mixed-a")
+
+
+@pytest.mark.parametrize("bits", nm.GENERIC_BITS + (85, 122))
+def test_generic_ntt_primes_have_generic_words(bits):
+    n = 2048
+    qs = nm.generic_ntt_primes(bits, n, 3, bits)
+    assert qs == nm.generic_ntt_primes(bits, n, 3, bits) and len(set(qs)) == 3                # deterministic for a seed, distinct
+    assert qs != nm.generic_ntt_primes(bits, n, 3, bits + 1)
+    for q in qs:
+        assert q.bit_length() == bits and q % (2 * n) == 1 and nm.is_prime(q)
+        words = [(q >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+        top = (bits - 1) // 32
+        assert all(w == 0 for w in words[top + 1:]) and words[top] != 0
+        assert all(w not in (0, 0xFFFFFFFF) for w in words[:top]), hex(q)
+    # the searches used everywhere else give the patterns this one excludes
+    assert not nm.has_generic_words(nm.ntt_primes(250, n, 1)[0]) and not nm.has_generic_words(nm.largest_ntt_primes(255, n, 1)[0])
+
+
+def _full_width_patterns(moduli, n, seed):
+    """[5][L][n] residues as Python integers: random, every coefficient q - 1, q - 1 / 0 alternating, q - 1 / 1 alternating, and a random
+    low part under q's own top 32-bit word (a comparison with q is decided below the top word)."""
+    rng = random.Random(seed)
+    low = []
+    for q in moduli:
+        sh = 32 * ((q.bit_length() - 1) // 32)
+        low.append([(q >> sh << sh) + rng.randrange(q & ((1 << sh) - 1)) for _ in range(n)])
+    return [[[rng.randrange(q) for _ in range(n)] for q in moduli],
+            [[q - 1] * n for q in moduli],
+            [[(q - 1) if i % 2 == 0 else 0 for i in range(n)] for q in moduli],
+            [[(q - 1) if i % 2 == 0 else 1 for i in range(n)] for q in moduli],
+            low]
+
+
+@pytest.mark.parametrize("name", FULL_WIDTH_SETS)
+def test_oracle_transforms_and_products_on_generic_full_width_moduli(oracle, name):
+    n = 64
+    moduli = nm.full_width_moduli(name, n)
+    rp = oracle.RnsPlan(n, moduli)
+    pats = _full_width_patterns(moduli, n, 1)
+    x = _pack(oracle, pats)
+    f = rp.forward(x, threads=2)
+    got = _unpack(oracle, f)
+    for bi in range(len(pats)):
+        for l, q in enumerate(moduli):
+            assert got[bi][l] == nm.negacyclic_ntt_direct(pats[bi][l], q, nm.find_psi(n, q)), (bi, q)
+    assert np.array_equal(rp.inverse(f, threads=2), x)
+    others = _full_width_patterns(moduli, n, 2)
+    others = [pats[1], others[1], others[3], others[0], others[4]]      # random x all q - 1; all q - 1 squared; alt0 x alt1; alt1 x random; low x low
+    prod = _unpack(oracle, rp.polymul(x, _pack(oracle, others), threads=2))
+    for bi in range(len(pats)):
+        for l, q in enumerate(moduli):
+            assert prod[bi][l] == nm.negacyclic_mul_direct(pats[bi][l], others[bi][l], q), (bi, q)
+
+
+@pytest.mark.parametrize("w", [61, 64])
+@pytest.mark.parametrize("name", FULL_WIDTH_SETS)
+def test_oracle_relinearize_on_generic_full_width_moduli_matches_big_integers(oracle, name, w):
+    """The formula of test_oracle_relinearize_at_the_top_primes_matches_big_integers.  w = 61: digits straddle the 64-bit limbs; w = 64: a
+    digit is a whole limb.  On mixed-a the digits of the wide limbs exceed the 60-bit modulus: d % q is a real reduction there."""
+    n = 64
+    moduli = nm.full_width_moduli(name, n); L = len(moduli)
+    rp = oracle.RnsPlan(n, moduli)
+    K = (max(q.bit_length() for q in moduli) + w - 1) // w
+    assert rp.num_digits(w) == K
+    rng = random.Random(len(name) * 100 + w)
+    kb = [[[rng.randrange(q) for _ in range(n)] for q in moduli] for _ in range(L * K)]
+    ka = [[[rng.randrange(q) for _ in range(n)] for q in moduli] for _ in range(L * K)]
+    c2 = _full_width_patterns(moduli, n, 7)[:3]              # random, all q - 1 (the largest digits), alternating
+    c0 = _full_width_patterns(moduli, n, 8)[:3]; c1 = _full_width_patterns(moduli, n, 9)[:3]
+    c0[2], c1[2] = c0[1], c1[1]                              # accumulators at q - 1 in two slots
+    o0, o1 = rp.relinearize(w, _pack(oracle, c0), _pack(oracle, c1), _pack(oracle, c2), [_pack(oracle, [k])[0] for k in kb], [_pack(oracle, [k])[0] for k in ka], threads=2)
+    g0, g1 = _unpack(oracle, o0), _unpack(oracle, o1)
+    reduced = False
+    for bi in range(3):
+        want0 = [list(r) for r in c0[bi]]; want1 = [list(r) for r in c1[bi]]
+        for j in range(L):
+            for k in range(K):
+                D = [(v >> (k * w)) & ((1 << w) - 1) for v in c2[bi][j]]
+                for i, q in enumerate(moduli):
+                    Dq = [d % q for d in D]
+                    reduced |= Dq != D
+                    pb = nm.negacyclic_mul_direct(Dq, kb[j * K + k][i], q); pa = nm.negacyclic_mul_direct(Dq, ka[j * K + k][i], q)
+                    want0[i] = [(u + v) % q for u, v in zip(want0[i], pb)]
+                    want1[i] = [(u + v) % q for u, v in zip(want1[i], pa)]
+        assert g0[bi] == want0 and g1[bi] == want1, bi
+    assert reduced == (name == "mixed-a")
+
+
+def _product(moduli):
+    Q = 1
+    for q in moduli:
+        Q *= q
+    return Q
+
+
+@pytest.mark.parametrize("name", FULL_WIDTH_SETS + ("g85x3", "t127"))
+def test_oracle_rns_entry_and_exit_on_generic_full_width_moduli(oracle, name):
+    """to_rns of any 256-bit value == Python %, from_rns == Python CRT where Q fits below 2^255 (the other bases are rejected)."""
+    n = 64
+    moduli = nm.full_width_moduli(name, n)
+    L = len(moduli); Q = _product(moduli)
+    rp = oracle.RnsPlan(n, moduli)
+    rng = random.Random(len(name))
+    edge = [0, 1 << 255, (1 << 256) - 1]
+    for q in moduli:
+        edge += [q, q - 1, (1 << 256) - q]
+    vals = edge + [rng.getrandbits(256) | (1 << 255) for _ in range(n - len(edge))]
+    R = rp.to_rns(oracle.to_limbs(vals).reshape(1, n, 4))
+    for l, q in enumerate(moduli):
+        assert oracle.from_limbs(R[0, l]) == [v % q for v in vals], q
+    if Q >= 1 << 255:
+        with pytest.raises(ValueError):
+            rp.from_rns(R)
+        return
+    if name in ("g85x3", "t127"):
+        assert Q.bit_length() == (255 if name == "g85x3" else 254)
+    vals = [0, 1, Q - 1, Q - 2] + [Q // q for q in moduli] + [Q - Q // q for q in moduli]
+    vals += [rng.randrange(Q) for _ in range(n - len(vals))]
+    V = oracle.to_limbs(vals).reshape(1, n, 4)
+    R = rp.to_rns(V)
+    assert [oracle.from_limbs(R[0, l, 2:3])[0] for l in range(L)] == [q - 1 for q in moduli]           # Q - 1: every residue q_l - 1
+    assert np.array_equal(rp.from_rns(R), V)
+    # an independent CRT from residues
+    res = [oracle.from_limbs(R[0, l]) for l in range(L)]
+    for i in range(n):
+        x = sum(res[l][i] * pow(Q // q, -1, q) % q * (Q // q) for l, q in enumerate(moduli)) % Q
+        assert x == vals[i]
+
+
+@pytest.mark.parametrize("order", ["widest-last", "narrowest-last", "g127", "g128", "g255"])
+def test_oracle_rescale_drop_last_on_generic_full_width_moduli(oracle, order):
+    """round(C / q_last) limb-wise from RESIDUES (C need not fit a container): with r the centred residue modulo q_last,
+    out_l = (c_l - r) * q_last^-1 mod q_l.  The last limb holds floor(q_last / 2), floor(q_last / 2) + 1, 0 and q_last - 1 among random values."""
+    n = 64
+    moduli = nm.full_width_moduli("mixed-a" if order.endswith("last") else order, n)
+    if order == "widest-last":
+        moduli = moduli[::-1]                                 # 60-bit, 100-bit, 250-bit
+    L = len(moduli); ql = moduli[-1]
+    rp = oracle.RnsPlan(n, moduli)
+    pats = _full_width_patterns(moduli, n, 11)
+    for bi in range(len(pats)):
+        pats[bi][L - 1][:4] = [ql // 2, ql // 2 + 1, 0, ql - 1]
+    out = _unpack(oracle, rp.rescale_drop_last(_pack(oracle, pats)))
+    for bi in range(len(pats)):
+        for i in range(n):
+            r = pats[bi][L - 1][i]
+            if r > ql // 2:
+                r -= ql
+            for l, q in enumerate(moduli[:-1]):
+                assert out[bi][l][i] == (pats[bi][l][i] - r) * pow(ql, -1, q) % q, (bi, i, l)
+
+
+@pytest.mark.parametrize("case", ["g250->g127+p60", "g127x2->g255", "p60x3->g250"])
+def test_oracle_fast_base_conversion_on_generic_full_width_moduli(oracle, case):
+    """y_j = sum_i [x_i (Q/q_i)^-1]_{q_i} (Q/q_i) mod p_j, from residues with Python integers."""
+    n = 64
+    src, dst = nm.base_conversion_case(case, n)
+    Q = _product(src)
+    S, D = oracle.RnsPlan(n, src), oracle.RnsPlan(n, dst)
+    pats = _full_width_patterns(src, n, 13)
+    Y = _unpack(oracle, S.fast_base_convert(D, _pack(oracle, pats)))
+    for bi in range(len(pats)):
+        for i in range(n):
+            full = sum(pats[bi][l][i] * pow(Q // q, -1, q) % q * (Q // q) for l, q in enumerate(src))
+            for j, p in enumerate(dst):
+                assert Y[bi][j][i] == full % p, (bi, i, j)
