@@ -106,6 +106,10 @@ def lib():
         "fhe_galois_element": ([u32, ctypes.c_int32, P(u32)], ci),
         "fhe_rns_automorphism": ([vp, vp, vp, u32, u32], ci),
         "fhe_ct_apply_galois": ([vp, vp, u32, vp, vp, vp, vp, u32], ci),
+        "fhe_ct_hoist": ([vp, u32, vp, u32], ci),
+        "fhe_ct_apply_galois_hoisted": ([vp, vp, u32, vp, vp, vp, u32], ci),
+        "fhe_rns_ntt_reserve_hoist": ([vp, u32, u32], ci),
+        "fhe_rns_ntt_hoist_bytes": ([vp, ctypes.POINTER(ctypes.c_uint64)], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -435,6 +439,24 @@ class RnsNttEngine:
         """(d_out0, d_out1) = sigma_g applied to the ciphertext (d_c0, d_c1) and key-switched back with the Galois keys gk of g
         (imported with import_relin_keys: rows (b, a) with b = -a*s + e + g_jk * sigma_g(s))."""
         _check(lib().fhe_ct_apply_galois(self.h, gk.h, galois_elt, _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), _ptr(d_c1), batch))
+
+    def hoist(self, decomp_bits, d_c1, batch=1):
+        """Decompose and transform c1 once; the engine keeps the result for apply_galois_hoisted until the next hoist."""
+        _check(lib().fhe_ct_hoist(self.h, decomp_bits, _ptr(d_c1), batch))
+
+    def apply_galois_hoisted(self, gk, galois_elt, d_out0, d_out1, d_c0, batch=1):
+        """One rotation of the hoisted ciphertext: d_c0 is the c0 that belongs to the hoisted c1, gk the Galois keys of g."""
+        _check(lib().fhe_ct_apply_galois_hoisted(self.h, gk.h, galois_elt, _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), batch))
+
+    def reserve_hoist(self, decomp_bits, batch):
+        """Pre-size the hoist workspace (and what the two calls need of the others) so that neither allocates afterwards."""
+        _check(lib().fhe_rns_ntt_reserve_hoist(self.h, decomp_bits, batch))
+
+    def hoist_bytes(self):
+        """Device bytes of the hoist workspace (not counted by workspace_bytes)."""
+        out = ctypes.c_uint64(0)
+        _check(lib().fhe_rns_ntt_hoist_bytes(self.h, ctypes.byref(out)))
+        return out.value
 
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))

@@ -67,7 +67,7 @@ struct EngineEnv {
     int force_width = 0;
     bool no_wide_lazy = false, no_wide_tiles = false;
     bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
-         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false,
+         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false,
          split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
     uint32_t small_batch_polys = 256, coop_polys = 64, split_pairs_polys = 128, overlap_chunks = 4;
     int ct_form_force = 0;
@@ -92,6 +92,9 @@ struct fhe_rns_ntt {
     void *d_ws = nullptr; size_t ws_bytes = 0;
     void *d_ws2 = nullptr; size_t ws2_bytes = 0;   // c2 of the fused multiply + relinearise (compact or containers); separate from d_ws, which the general paths use
     void *d_ws3 = nullptr; size_t ws3_bytes = 0;   // compact polynomials between the two launches of a two-pass transform (sub_top != 0)
+    // Hoisted rotations: the transformed digit polynomials of the c1 of the last fhe_ct_hoist, a fourth allocation that no other entry point touches
+    void *d_hoist = nullptr; size_t hoist_bytes = 0;
+    struct { bool valid = false, fused = false; uint32_t w = 0, K = 0, batch = 0; } hoist;   // what d_hoist holds: digit width, digits per limb, ciphertexts
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
@@ -185,6 +188,7 @@ LdsPlan plan_ct_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands,
 bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys);
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone);
 LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
+bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys);   // hoisted rotations on the LDS kernels of hoist.hip.h (else the composed path)
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
 WsNeed need_multiply(const fhe_rns_ntt *h, uint32_t batch);

@@ -12,6 +12,7 @@ void destroy_impl(fhe_rns_ntt *h) {
     if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->d_ws2) (void)hipFree(h->d_ws2);
     if (h->d_ws3) (void)hipFree(h->d_ws3);
+    if (h->d_hoist) (void)hipFree(h->d_hoist);
     if (h->d_cdt) (void)hipFree(h->d_cdt);
     if (h->d_flag) (void)hipFree(h->d_flag);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
@@ -197,6 +198,7 @@ static EngineEnv read_env() {
     e.no_compact_blind_rotate = set("FHE_HIP_NO_COMPACT_BLIND_ROTATE");
     e.no_two_launch_ct = set("FHE_HIP_NO_TWO_LAUNCH_CT");
     e.no_fused_galois = set("FHE_HIP_NO_FUSED_GALOIS");                                // fhe_ct_apply_galois on the composed path everywhere (cross-check)
+    e.no_fused_hoist = set("FHE_HIP_NO_FUSED_HOIST");                                  // hoisted rotations on the composed path everywhere (cross-check); key import is unchanged
     e.split_keyswitch = set("FHE_HIP_SPLIT_KEYSWITCH");
     e.small_batch_polys = num("FHE_HIP_SMALL_BATCH_POLYS", 256, 0, LONG_MAX);       // fused multiply of at most this many limb polynomials runs the 16-per-thread latency kernel (0 = never)
     e.coop_polys = num("FHE_HIP_COOP_POLYS", 64, 0, 64);                               // ... (N = 2^13 / 2^14, 4-byte residues) spreads each over four workgroups in three launches (0 = never)

@@ -43,6 +43,31 @@ static int pack_relin_keys_t(fhe_rns_ntt *h, fhe_relin_keys *rk) {
     return post_launch(h->stream, "pack_keys_kernel");
 }
 
+// Whether a key set of K digits of decomp_bits bits gets packed tables, i.e. runs the fused kernels (fhe_ct_hoist asks before any key set is seen)
+static bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K) {
+    const size_t num_keys = (size_t)h->L * K;
+    // The fused kernels feed a digit of limb j (< min(2^w, q_j)) straight into limb i's lazy forward transform, whose
+    // integer butterflies accept inputs below 4*q_i; bases mixing very different prime sizes go through the general
+    // composition, which reduces every digit modulo q_i first.
+    bool digits_fit = true;
+    if (h->width == FHE_WIDTH_32 || h->width == FHE_WIDTH_64 || h->width == FHE_WIDTH_64X) {
+        fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
+        for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
+        const fhe_host::u128 digit_bound = decomp_bits < 64 ? std::min((fhe_host::u128)1 << decomp_bits, q_max) : q_max;
+        // the full-range field's butterflies are canonical: there a digit must be a residue of q_i as it stands
+        digits_fit = digit_bound <= (h->width == FHE_WIDTH_64X ? q_min : 4 * q_min);
+    } else if (h->width == FHE_WIDTH_52) {
+        // floating-point field: the fused kernels add the L*K digit-times-key products of a limb as doubles and reduce the sum once
+        // (F52::regroup, stated for |x| < 2^49).  A product is below 0.76 q in magnitude, and the external product adds the second
+        // component's L*K products to the reduced sum of the first: (L*K + 1) * 0.76 * 2^43 < 2^49 holds up to L*K = 83 (DESIGN.md
+        // section 4.3).  More digits than that take the general composition, which reduces after every product.
+        digits_fit = (uint64_t)h->L * K <= 83;
+    }
+    // the fused kernels address a packed table through a buffer descriptor with 32-bit offsets (fhe_dev::TableBuf): a table of 4 GiB or
+    // more (L*K*L*n residues: not reached by any parameter set of the reference) stays on the general composition
+    const bool table_fits = (size_t)num_keys * h->L * h->n * (h->width == FHE_WIDTH_32 ? 4 : 8) < ((size_t)1 << 32);
+    return h->width != FHE_WIDTH_256 && !h->sub_top && digits_fit && table_fits && !h->env.no_fused_keyswitch;
+}
 extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, uint32_t decomp_bits,
                                      const void *const *d_keys_b, const void *const *d_keys_a, uint32_t num_keys) {
     if (!h || !out || !d_keys_b || !d_keys_a) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null argument");
@@ -73,27 +98,7 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
     }
     int rc = do_forward(h, rk->d_kb, num_keys);
     if (!rc) rc = do_forward(h, rk->d_ka, num_keys);
-    // The fused kernels feed a digit of limb j (< min(2^w, q_j)) straight into limb i's lazy forward transform, whose
-    // integer butterflies accept inputs below 4*q_i; bases mixing very different prime sizes go through the general
-    // composition, which reduces every digit modulo q_i first.
-    bool digits_fit = true;
-    if (h->width == FHE_WIDTH_32 || h->width == FHE_WIDTH_64 || h->width == FHE_WIDTH_64X) {
-        fhe_host::u128 q_min = ~(fhe_host::u128)0, q_max = 0;
-        for (const U256 &q : h->moduli) { fhe_host::u128 v = q.w[0]; q_min = v < q_min ? v : q_min; q_max = v > q_max ? v : q_max; }
-        const fhe_host::u128 digit_bound = decomp_bits < 64 ? std::min((fhe_host::u128)1 << decomp_bits, q_max) : q_max;
-        // the full-range field's butterflies are canonical: there a digit must be a residue of q_i as it stands
-        digits_fit = digit_bound <= (h->width == FHE_WIDTH_64X ? q_min : 4 * q_min);
-    } else if (h->width == FHE_WIDTH_52) {
-        // floating-point field: the fused kernels add the L*K digit-times-key products of a limb as doubles and reduce the sum once
-        // (F52::regroup, stated for |x| < 2^49).  A product is below 0.76 q in magnitude, and the external product adds the second
-        // component's L*K products to the reduced sum of the first: (L*K + 1) * 0.76 * 2^43 < 2^49 holds up to L*K = 83 (DESIGN.md
-        // section 4.3).  More digits than that take the general composition, which reduces after every product.
-        digits_fit = (uint64_t)h->L * K <= 83;
-    }
-    // the fused kernels address a packed table through a buffer descriptor with 32-bit offsets (fhe_dev::TableBuf): a table of 4 GiB or
-    // more (L*K*L*n residues: not reached by any parameter set of the reference) stays on the general composition
-    const bool table_fits = (size_t)rk->num_keys * h->L * h->n * (h->width == FHE_WIDTH_32 ? 4 : 8) < ((size_t)1 << 32);
-    if (!rc && h->width != FHE_WIDTH_256 && !h->sub_top && digits_fit && table_fits && !h->env.no_fused_keyswitch) {
+    if (!rc && keys_get_packed(h, decomp_bits, K)) {
         rc = with_word_field(h, [&](auto f) { return pack_relin_keys_t<decltype(f)>(h, rk); });
         if (!rc) {   // the fused kernels read only the packed tables (n * sizeof(E) bytes per key polynomial instead of n * 32): drop the
                      // container copy, so that a bootstrapping key of several hundred RGSW ciphertexts fits (hipFree waits for the packing)
@@ -107,30 +112,32 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
     return FHE_OK;
 }
 
+// D[jk][b][i] = digit jk of src[b] embedded in limb i, as containers (K digits of w bits per limb)
+static int embed_digits(fhe_rns_ntt *h, char *D, const void *src, uint32_t K, uint32_t w, uint32_t chunk) {
+    const size_t total = (size_t)h->L * K * chunk * h->L * h->n;
+    if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) {
+        using F = decltype(f); using V = typename F::V16;
+        hipLaunchKernelGGL((fhe_dev::digit_embed_kernel<F>), dim3(ew_grid(total * 2)), dim3(256), 0, h->stream, (V *)D, (const V *)src,
+                           (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, K, w, chunk);
+        return post_launch(h->stream, "digit_embed_kernel");
+    });
+    hipLaunchKernelGGL(fhe_dev::digit_embed256_kernel, dim3(ew_grid(total)), dim3(256), 0, h->stream, (fhe_dev::u256 *)D, (const fhe_dev::u256 *)src,
+                       (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, K, w, chunk);
+    return post_launch(h->stream, "digit_embed256_kernel");
+}
 template <class F>
 static int relin_embed_mac_lds(fhe_rns_ntt *h, const fhe_relin_keys *rk, char *D, char *acc0, char *acc1, const void *c2, uint32_t chunk, int phase) {
     using V = typename F::V16;
     const uint32_t LK = h->L * rk->K;
-    if (phase == 0) {
-        size_t total = (size_t)LK * chunk * h->L * h->n * 2;
-        hipLaunchKernelGGL((fhe_dev::digit_embed_kernel<F>), dim3(ew_grid(total)), dim3(256), 0, h->stream, (V *)D, (const V *)c2,
-                           (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->K, rk->decomp_bits, chunk);
-        return post_launch(h->stream, "digit_embed_kernel");
-    }
     size_t halves = (size_t)chunk * h->L * h->n * 2;
     hipLaunchKernelGGL((fhe_dev::relin_mac_kernel<F>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)D,
                        (const V *)rk->d_kb, (const V *)rk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, chunk);
     return post_launch(h->stream, "relin_mac_kernel");
 }
 static int relin_embed_mac(fhe_rns_ntt *h, const fhe_relin_keys *rk, char *D, char *acc0, char *acc1, const void *c2, uint32_t chunk, int phase) {
+    if (phase == 0) return embed_digits(h, D, c2, rk->K, rk->decomp_bits, chunk);
     if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return relin_embed_mac_lds<decltype(f)>(h, rk, D, acc0, acc1, c2, chunk, phase); });
     const uint32_t LK = h->L * rk->K;
-    if (phase == 0) {
-        size_t total = (size_t)LK * chunk * h->L * h->n;
-        hipLaunchKernelGGL(fhe_dev::digit_embed256_kernel, dim3(ew_grid(total)), dim3(256), 0, h->stream, (fhe_dev::u256 *)D, (const fhe_dev::u256 *)c2,
-                           (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, rk->K, rk->decomp_bits, chunk);
-        return post_launch(h->stream, "digit_embed256_kernel");
-    }
     size_t count = (size_t)chunk * h->L * h->n;
     hipLaunchKernelGGL(fhe_dev::relin_mac256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)acc0, (fhe_dev::u256 *)acc1,
                        (const fhe_dev::u256 *)D, (const fhe_dev::u256 *)rk->d_kb, (const fhe_dev::u256 *)rk->d_ka,
@@ -393,6 +400,115 @@ extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk,
     }
     if ((rc = do_galois(h, d_out0, h->d_ws2, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
     return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->d_ws2, batch);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Hoisted rotations (Halevi-Shoup): fhe_ct_hoist decomposes and transforms c1 once, every fhe_ct_apply_galois_hoisted is a permuted
+// multiply-accumulate with the key rows, two inverse transforms and sigma_g(c0)   (semantics and pi_g: include/fhe_hip.h)
+// ------------------------------------------------------------------------------------------------------
+// Fused path (plan_fused_hoist; kernels: hoist.hip.h): c1 compacted into d_ws2, ntt_hoist_kernel writes the L K L kept polynomials as
+// residues; a rotation is the one-component automorphism of c0 into d_ws2 (compact) and ntt_hoist_apply_kernel.  Composed path: the
+// digit polynomials as containers [jk][b][i] (digit_embed + forward transform); a rotation is relin_mac_perm (first sum into d_ws, second
+// into out1), two inverse transforms, sigma_g(c0) into out0 and an addition.  A key set that kept only its packed tables (N = 2^15,
+// FHE_HIP_NO_FUSED_HOIST=1) is read from those (relin_mac_perm_packed_kernel): key import is the same with and without hoisting.
+static bool hoist_fused(const fhe_rns_ntt *h, uint32_t w, uint32_t K) { return plan_fused_hoist(h, keys_get_packed(h, w, K)); }
+static size_t hoist_size(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool fused) {
+    return (size_t)batch * h->L * K * h->L * h->n * (fused ? residue_bytes(h) : 32);
+}
+static WsNeed need_hoist(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool fused) {   // of fhe_ct_hoist and fhe_ct_apply_galois_hoisted together
+    const size_t polys = (size_t)batch * h->L;
+    if (fused) return {0, polys * h->n * residue_bytes(h), 0};                 // compact c1, then compact sigma_g(c0)
+    return WsNeed{polys * h->n * 32, 0, 0} | need_transform(h, polys * h->L * K) | need_transform(h, polys);
+}
+static int ensure_hoist(fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool fused) {
+    int rc = ensure_need(h, need_hoist(h, batch, K, fused)); if (rc) return rc;
+    const size_t bytes = hoist_size(h, batch, K, fused);
+    if (h->hoist_bytes < bytes) h->hoist.valid = false;                       // growing drops what was kept
+    return grow_ws(h, &h->d_hoist, &h->hoist_bytes, bytes);
+}
+static int check_hoist_call(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t batch, const char *what) {
+    int rc = check_call(h, batch, what); if (rc) return rc;
+    if (decomp_bits < 1 || decomp_bits > 64) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": decomp_bits must be in [1, 64]");
+    if ((uint64_t)batch * h->L * h->L > 0x7fffffffull) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": batch * num_primes^2 too large");
+    return FHE_OK;
+}
+extern "C" int fhe_rns_ntt_reserve_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t batch) {
+    int rc = check_hoist_call(h, decomp_bits, batch, "reserve_hoist"); if (rc) return rc;
+    const uint32_t K = relin_digits(h, decomp_bits);
+    return ensure_hoist(h, batch, K, hoist_fused(h, decomp_bits, K));
+}
+extern "C" int fhe_rns_ntt_hoist_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {
+    if (!h || !bytes) return fail(FHE_ERR_INVALID_ARG, "hoist_bytes: null argument");
+    *bytes = (uint64_t)h->hoist_bytes;
+    return FHE_OK;
+}
+extern "C" int fhe_ct_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, const void *d_c1, uint32_t batch) {
+    int rc = check_hoist_call(h, decomp_bits, batch, "ct_hoist"); if (rc) return rc;
+    if (!d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_hoist: null argument");
+    if ((rc = check_aligned({d_c1}, "ct_hoist"))) return rc;
+    if ((rc = check_inputs(h, {d_c1}, batch))) return rc;
+    const uint32_t K = relin_digits(h, decomp_bits);
+    const bool fused = hoist_fused(h, decomp_bits, K);
+    h->hoist.valid = false;
+    if ((rc = ensure_hoist(h, batch, K, fused))) return rc;
+    if (fused) {
+        if ((rc = compact_poly(h, h->d_ws2, d_c1, (size_t)batch * h->L * h->n))) return rc;
+        fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST, {}, batch * h->L * h->L);
+        A.r0 = h->d_hoist; A.c2 = h->d_ws2; A.in_compact = true; A.K = K; A.w = decomp_bits;
+        if ((rc = lds_launch(h, A, "ntt_hoist_kernel"))) return rc;
+    } else {
+        if ((rc = embed_digits(h, (char *)h->d_hoist, d_c1, K, decomp_bits, batch))) return rc;
+        if ((rc = do_forward(h, h->d_hoist, h->L * K * batch))) return rc;
+    }
+    h->hoist.valid = true; h->hoist.fused = fused; h->hoist.w = decomp_bits; h->hoist.K = K; h->hoist.batch = batch;
+    return FHE_OK;
+}
+static int relin_mac_perm(fhe_rns_ntt *h, const fhe_relin_keys *gk, void *acc0, void *acc1, uint32_t g, uint32_t batch) {
+    const uint32_t LK = h->L * gk->K;
+    const size_t count = (size_t)batch * h->L * h->n;
+    if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) {
+        using F = decltype(f); using V = typename F::V16;
+        if (!gk->d_kb) {
+            hipLaunchKernelGGL((fhe_dev::relin_mac_perm_packed_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->d_hoist,
+                               (const typename F::E *)gk->d_pkb, (const typename F::E *)gk->d_pka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, batch, g);
+            return post_launch(h->stream, "relin_mac_perm_packed_kernel");
+        }
+        hipLaunchKernelGGL((fhe_dev::relin_mac_perm_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->d_hoist,
+                           (const V *)gk->d_kb, (const V *)gk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, batch, g);
+        return post_launch(h->stream, "relin_mac_perm_kernel");
+    });
+    hipLaunchKernelGGL(fhe_dev::relin_mac_perm256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)acc0, (fhe_dev::u256 *)acc1,
+                       (const fhe_dev::u256 *)h->d_hoist, (const fhe_dev::u256 *)gk->d_kb, (const fhe_dev::u256 *)gk->d_ka,
+                       (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, LK, batch, g);
+    return post_launch(h->stream, "relin_mac_perm256_kernel");
+}
+extern "C" int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1,
+                                           const void *d_c0, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_apply_galois_hoisted"); if (rc) return rc;
+    if (!gk || !d_out0 || !d_out1 || !d_c0) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: null argument");
+    if ((rc = check_aligned({d_out0, d_out1, d_c0}, "ct_apply_galois_hoisted"))) return rc;
+    if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: keys were imported for a different engine");
+    if (d_out0 == d_out1 || d_out0 == d_c0 || d_out1 == d_c0) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: outputs must be distinct from each other and from c0");
+    if ((rc = check_galois_element(h, galois_elt, "ct_apply_galois_hoisted"))) return rc;
+    if (!h->hoist.valid) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: no fhe_ct_hoist on this engine yet (or its workspace was re-sized since)");
+    if (batch != h->hoist.batch) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: batch differs from the hoisted one");
+    if (gk->decomp_bits != h->hoist.w) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: the keys' decomp_bits differ from the hoisted ones");
+    if (h->hoist.fused ? !gk->d_pkb : (!gk->d_kb && !gk->d_pkb)) return fail(FHE_ERR_INVALID_ARG, "ct_apply_galois_hoisted: the key set does not have the tables this engine's hoist path reads");
+    if ((rc = check_inputs(h, {d_c0}, batch))) return rc;
+    if ((rc = ensure_hoist(h, batch, gk->K, h->hoist.fused))) return rc;       // (no-op after fhe_ct_hoist: the workspaces only ever grow)
+    const size_t polys = (size_t)batch * h->L;
+    if (h->hoist.fused) {
+        if ((rc = do_galois(h, h->d_ws2, nullptr, nullptr, d_c0, nullptr, galois_elt, polys, true))) return rc;
+        fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST_APPLY, {}, (uint32_t)polys);
+        A.r0 = d_out0; A.r1 = d_out1; A.c2 = h->d_hoist; A.add0 = h->d_ws2; A.in_compact = A.add_compact = true;
+        A.kb = gk->d_pkb; A.ka = gk->d_pka; A.K = gk->K; A.galois = galois_elt;
+        return lds_launch(h, A, "ntt_hoist_apply_kernel");
+    }
+    if ((rc = relin_mac_perm(h, gk, h->d_ws, d_out1, galois_elt, batch))) return rc;
+    if ((rc = do_inverse(h, h->d_ws, batch))) return rc;
+    if ((rc = do_inverse(h, d_out1, batch))) return rc;
+    if ((rc = do_galois(h, d_out0, nullptr, nullptr, d_c0, nullptr, galois_elt, polys, false))) return rc;
+    return do_ew<1>(h, d_out0, d_out0, h->d_ws, batch, "hoisted rotation add");
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "lds_launch.h"
+#include "hoist.hip.h"
 #include "ntt_lds.hip.h"
 #include "ntt_lds_small.hip.h"
 
@@ -69,6 +70,21 @@ static bool launch(const LdsArgs &A) {
     if (A.op == LDS_INVERSE) {
         hipLaunchKernelGGL((ntt_inverse_kernel<F, LOGN>), grid, block, 0, A.stream, (char *)A.r0, limbs, A.L);
         return true;
+    }
+    // Hoisted rotations: compact c1 in, kept polynomials out; kept polynomials and a compact addend in, containers out
+    if (A.op == LDS_HOIST || A.op == LDS_HOIST_APPLY) {
+        if constexpr (lds_hoist(EB, LOGN)) {
+            if (A.op == LDS_HOIST) {
+                if (!in || out) return false;
+                hipLaunchKernelGGL((ntt_hoist_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (E *)A.r0, (const char *)A.c2, limbs, A.L, A.K, A.w);
+            } else {
+                if (!in || !ac || out || !A.add0) return false;
+                hipLaunchKernelGGL((ntt_hoist_apply_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const E *)A.c2, (const char *)A.add0,
+                                   (const E *)A.kb, (const E *)A.ka, limbs, A.L, A.K, A.galois);
+            }
+            return true;
+        }
+        return false;
     }
     // What no form has a kernel for.  Multiply: containers in and out.  Tensor product: containers in.  Key switch: r0, r1 containers; the addends
     // are given, compact and beside a compact digit source (the fused multiply + relinearise), or not given: r0, r1 are accumulated in place.

@@ -8,10 +8,11 @@
 namespace fhe_dev {
 
 // One list per enum: the enumerators and the names that the "no LDS kernel for ..." error prints come out of the same lines.
+// LDS_HOIST / LDS_HOIST_APPLY: hoisted rotations (hoist.hip.h), one form each.
 // The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
 // over the top stages and the sub-transforms of the 2^top blocks
 #define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
-    X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") \
+    X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") X(LDS_HOIST, "hoist") X(LDS_HOIST_APPLY, "hoisted rotation") \
     X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
 #define LDS_ENUMERATOR(id, name) id,
 #define LDS_NAME_CASE(id, name) case id: return name;
@@ -55,6 +56,10 @@ constexpr bool lds_small_multiply(int elem_bytes, int log_n) { return elem_bytes
 // ... and for a handful of polynomials one polynomial over four workgroups (LDS_COOP4: ntt_multiply4_* / ntt_ct4_* kernels)
 constexpr bool lds_coop4_multiply(int elem_bytes, int log_n) { return elem_bytes == 4 && (log_n == 13 || log_n == 14); }
 
+// hoisted rotations (ntt_hoist_kernel / ntt_hoist_apply_kernel: two and three live arrays): every LDS-resident size but N = 2^15, whose
+// 1024-thread workgroups cap a thread at 128 VGPRs (the apply kernel parks 84 bytes per lane in scratch there): that size takes the composed path
+constexpr bool lds_hoist(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
+
 // The kernel form of LDS_MULTIPLY / LDS_CT_MULTIPLY / LDS_KEYSWITCH / LDS_EXTPROD (the other ops have one form each).
 #define LDS_FORMS(X) /* LDS_MULTIPLY, LDS_CT_MULTIPLY */ \
     X(LDS_ONE_LAUNCH, "one-launch")              /* one workgroup per limb polynomial, one launch */ \
@@ -96,6 +101,9 @@ struct LdsArgs {
     bool out_compact = false;            // every output r0, r1, r2
     void *ws = nullptr;                  // the form's workspace (LdsForm)
     const void *kb = nullptr, *ka = nullptr, *kb1 = nullptr, *ka1 = nullptr;   // packed key tables / RGSW rows
+    // LDS_HOIST: r0 = the hoist workspace, c2 = c1 (compact).  LDS_HOIST_APPLY: (r0, r1) = (add0, 0) + the kept polynomials of c2 = the hoist
+    // workspace, read at pi_galois, times kb / ka; add0 = sigma_galois(c0), compact
+    uint32_t galois = 0;
     const uint32_t *shifts = nullptr;    // LDS_EXTPROD: device array of per-ciphertext monomial exponents
     uint32_t K = 0, w = 0;
     uint32_t b_polys = 0;                // LDS_MULTIPLY: polynomials behind b0 (0 = as many as the batch; L = one RNS polynomial broadcast over the batch)

@@ -52,6 +52,36 @@ relin_mac256_kernel(u256 *__restrict__ acc0, u256 *__restrict__ acc1, const u256
     }
 }
 
+// relin_mac256_kernel with the digit polynomials read at pi_g (hoisted rotation, composed path; pi_g: include/fhe_hip.h, Galois section)
+__global__ void __launch_bounds__(256)
+relin_mac_perm256_kernel(u256 *__restrict__ acc0, u256 *__restrict__ acc1, const u256 *__restrict__ D, const u256 *__restrict__ KB,
+                         const u256 *__restrict__ KA, const Limb256 *__restrict__ limbs, uint32_t L, uint32_t log_n, uint32_t LK,
+                         uint32_t batch, uint32_t galois) {
+    const size_t per_poly = (size_t)1 << log_n, per_ct = per_poly * L, per_digit = per_ct * batch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < per_digit; g += stride) {
+        const size_t kidx = g % per_ct;
+        const Limb256 &P = limbs[(uint32_t)(kidx >> log_n)];
+        const uint32_t x = (uint32_t)(g & (per_poly - 1));
+        uint32_t xs = 0;
+        if (log_n) {
+            const uint32_t e = __brev(x) >> (32 - log_n);
+            xs = __brev(((galois * (2 * e + 1)) & ((2u << log_n) - 1)) >> 1) >> (32 - log_n);
+        }
+        const size_t src = g - x + xs;
+        u256 s0, s1;
+        s0.l[0] = s0.l[1] = s0.l[2] = s0.l[3] = 0; s1 = s0;
+        for (uint32_t jk = 0; jk < LK; jk++) {
+            const uint32_t qi = (uint32_t)P.inv0;
+            const u256 d = mont_mul_fips(load_u256(D + (size_t)jk * per_digit + src), P.r2, P.q, qi);      // d * R
+            s0 = add_mod(s0, mont_mul_fips(d, load_u256(KB + (size_t)jk * per_ct + kidx), P.q, qi), P.q);
+            s1 = add_mod(s1, mont_mul_fips(d, load_u256(KA + (size_t)jk * per_ct + kidx), P.q, qi), P.q);
+        }
+        store_u256(acc0 + g, s0);
+        store_u256(acc1 + g, s1);
+    }
+}
+
 // (X^shift[b] - 1) * p on full-width containers (see monomial_mul_sub_kernel in ntt_lds.hip.h)
 __global__ void __launch_bounds__(256)
 monomial_mul_sub256_kernel(u256 *__restrict__ out, const u256 *__restrict__ in, const uint32_t *__restrict__ shifts,

@@ -147,6 +147,71 @@ relin_mac_kernel(typename F::V16 *__restrict__ acc0, typename F::V16 *__restrict
     }
 }
 
+// Position of NTT(a) that position x of NTT(sigma_g a) equals (include/fhe_hip.h, Galois section): position x holds a(psi^(2 bitrev(x) + 1))
+__device__ __forceinline__ uint32_t galois_ntt_src(uint32_t x, uint32_t g, uint32_t log_n) {
+    if (!log_n) return 0;
+    const uint32_t e = __brev(x) >> (32 - log_n);
+    return __brev(((g * (2 * e + 1)) & ((2u << log_n) - 1)) >> 1) >> (32 - log_n);
+}
+// relin_mac_kernel with the digit polynomials read at pi_g: the accumulators of one hoisted rotation (composed path)
+template <class F>
+__global__ void __launch_bounds__(256)
+relin_mac_perm_kernel(typename F::V16 *__restrict__ acc0, typename F::V16 *__restrict__ acc1, const typename F::V16 *__restrict__ D,
+                      const typename F::V16 *__restrict__ KB, const typename F::V16 *__restrict__ KA, const Limb<F> *__restrict__ limbs,
+                      uint32_t L, uint32_t log_n, uint32_t LK, uint32_t batch, uint32_t galois) {
+    using E = typename F::E;
+    const size_t per_poly = (size_t)2 << log_n, per_ct = per_poly * L, per_digit = per_ct * batch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < per_digit; g += stride) {
+        E s0 = 0, s1 = 0;
+        if (!(g & 1)) {
+            const size_t kidx = g % per_ct;
+            const Limb<F> &P = limbs[(uint32_t)(kidx >> (log_n + 1))];
+            const uint32_t x = (uint32_t)((g & (per_poly - 1)) >> 1);
+            const size_t src = g - 2 * (size_t)x + 2 * (size_t)galois_ntt_src(x, galois, log_n);
+            for (uint32_t jk = 0; jk < LK; jk++) {
+                const E d = F::load_low(D + (size_t)jk * per_digit + src);
+                s0 = F::ew_add(s0, F::ew_mul(d, F::load_low(KB + (size_t)jk * per_ct + kidx), P), P.q);
+                s1 = F::ew_add(s1, F::ew_mul(d, F::load_low(KA + (size_t)jk * per_ct + kidx), P), P.q);
+            }
+        }
+        __builtin_nontemporal_store(F::pack(s0), acc0 + g);
+        __builtin_nontemporal_store(F::pack(s1), acc1 + g);
+    }
+}
+
+// The same from the PACKED key tables (pack_keys_kernel: entry (c, tid, e) of row jk, limb i is KEY_ntt[i][tid*32 + c*VPL + e] * 2^W), for key sets
+// that dropped their container copy: canon(pw_mul(operand, d)) is the plain product key * d mod q (mul_const below)
+template <class F>
+__global__ void __launch_bounds__(256)
+relin_mac_perm_packed_kernel(typename F::V16 *__restrict__ acc0, typename F::V16 *__restrict__ acc1, const typename F::V16 *__restrict__ D,
+                             const typename F::E *__restrict__ PB, const typename F::E *__restrict__ PA, const Limb<F> *__restrict__ limbs,
+                             uint32_t L, uint32_t log_n, uint32_t LK, uint32_t batch, uint32_t galois) {
+    using E = typename F::E;
+    constexpr uint32_t VPL = 16 / sizeof(E);
+    const size_t per_poly = (size_t)2 << log_n, per_ct = per_poly * L, per_digit = per_ct * batch, n = (size_t)1 << log_n;
+    const uint32_t T = (uint32_t)(n >> 5);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < per_digit; g += stride) {
+        E s0 = 0, s1 = 0;
+        if (!(g & 1)) {
+            const uint32_t i = (uint32_t)((g % per_ct) >> (log_n + 1));
+            const Limb<F> &P = limbs[i];
+            const uint32_t x = (uint32_t)((g & (per_poly - 1)) >> 1), r = x & 31;
+            const size_t src = g - 2 * (size_t)x + 2 * (size_t)galois_ntt_src(x, galois, log_n);
+            const size_t slot = ((size_t)(r / VPL) * T + (x >> 5)) * VPL + r % VPL;
+            for (uint32_t jk = 0; jk < LK; jk++) {
+                const E d = F::load_low(D + (size_t)jk * per_digit + src);
+                const size_t k = ((size_t)jk * L + i) * n + slot;
+                s0 = F::ew_add(s0, F::canon_inv(F::pw_mul(PB[k], d, P.q, P.qinv), P.q), P.q);
+                s1 = F::ew_add(s1, F::canon_inv(F::pw_mul(PA[k], d, P.q, P.qinv), P.q), P.q);
+            }
+        }
+        __builtin_nontemporal_store(F::pack(s0), acc0 + g);
+        __builtin_nontemporal_store(F::pack(s1), acc1 + g);
+    }
+}
+
 // ---- RNS conversions on word-sized residues (row N2): rounded drop of the last prime, Bajard fast base conversion -----------
 // The container-level kernels in ntt256.hip.h do these through 256-bit Montgomery products for every width class; for word-sized
 // classes the same arithmetic fits the field type and the kernels are streaming kernels.  Constants are "pw operands"

@@ -187,6 +187,10 @@ static bool use_joint3(const fhe_rns_ntt *h, bool extprod, bool compact) {
 bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys) {
     return packed_keys && h->width != FHE_WIDTH_256 && !h->sub_top && !h->env.single_transforms && !h->env.no_fused_ct_relin;
 }
+// Hoisted rotations as the two LDS ops of hoist.hip.h: where the fused multiply + relinearise runs and the instance has the kernels
+bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys) {
+    return plan_fused_ct_relin(h, packed_keys) && fhe_dev::lds_hoist((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_hoist;
+}
 // Key switch of `polys` limb polynomials with K digits (KsSource: engine.h).  alone: no other chunk of the call runs beside it (the
 // few-ciphertext parts take d_ws).
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone) {

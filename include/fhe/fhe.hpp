@@ -349,6 +349,34 @@ public:
         apply_galois(result, ct, path[0], gal_keys);
         for (size_t i = 1; i < path.size(); i++) apply_galois(result, result, path[i], gal_keys);
     }
+    // Hoisted rotations: ct is decomposed and transformed once (fhe_ct_hoist), every step is then one fhe_ct_apply_galois_hoisted with the key of
+    // 3^step.  UNLIKE rotate_rows, a missing step is not composed from power-of-two keys: each step needs its own key in the set (a composed
+    // rotation is not a rotation of the hoisted ciphertext; generate keys with galoiskey_gen(gal_keys, sk, steps, ...)), else it throws; step 0
+    // is a copy.  The results decrypt like rotate_rows' but are not bit-identical to them.
+    std::vector<Ciphertext> rotate_rows_hoisted(const Ciphertext &ct, const std::vector<int> &steps, const GaloisKeys &gal_keys) {
+        if (ct.components.size() != 2) throw std::runtime_error("FHEContext::rotate_rows_hoisted: 2-component ciphertext expected (relinearize first)");
+        const uint32_t half = params_.n / 2;
+        std::vector<uint32_t> elts;
+        for (int st : steps) {
+            const uint32_t r = (uint32_t)(((long long)st % half + half) % half), g = galois_element((int)r);
+            if (r && galois_key_index(gal_keys, g) == (size_t)-1) throw std::runtime_error("FHEContext::rotate_rows_hoisted: no Galois key for a step");
+            elts.push_back(r ? g : 1);
+        }
+        import_galois_keys(gal_keys);
+        std::vector<Ciphertext> out(steps.size());
+        if (!elts.empty())
+            check(fhe_ct_hoist(params_.rns_ntt->handle(), gal_keys.decomp_bits, ct.components[1]->coeffs, 1), "FHEContext::rotate_rows_hoisted: hoist");
+        for (size_t s = 0; s < elts.size(); s++) {
+            ensure_components(out[s], 2);
+            if (elts[s] == 1) copy_ciphertext(out[s], ct);
+            else check(fhe_ct_apply_galois_hoisted(params_.rns_ntt->handle(), gal_keys.imported[galois_key_index(gal_keys, elts[s])], elts[s],
+                                                   out[s].components[0]->coeffs, out[s].components[1]->coeffs, ct.components[0]->coeffs, 1),
+                       "FHEContext::rotate_rows_hoisted");
+            out[s].noise_budget = ct.noise_budget; out[s].level = ct.level; out[s].is_ntt_form = false;
+        }
+        device_synchronize();
+        return out;
+    }
     // FHEContext::rotate_columns (include/fhe.cuh:114-115): swaps the two rows (g = 2n - 1).
     void rotate_columns(Ciphertext &result, const Ciphertext &ct, const GaloisKeys &gal_keys) { apply_galois(result, ct, column_element(), gal_keys); }
 

@@ -251,7 +251,12 @@ int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_
  *     2 pi_g(i) + 1 = g (2i + 1) (mod 2n).  rotate_rows(steps) uses g = 3^steps mod 2n (steps taken mod n/2, negative steps the inverse
  *     power); rotate_columns uses g = 2n - 1.  With the slots of row 0 ordered by 2i+1 = 3^k and those of row 1 by 2i+1 = -3^k (mod 2n),
  *     rotate_rows(r) is a cyclic left shift by r of both rows, as in SEAL, and rotate_columns swaps the rows.  The natural slot order of
- *     the encoding is a permutation of this one. */
+ *     the encoding is a permutation of this one.
+ *   NTT-domain order.  Position x of a forward-transformed limb holds a(psi^(2 bitrev(x) + 1)), bitrev over log2 n bits (fhe_ntt_forward:
+ *     "X[k] sits at position bitrev(k)"; in the LDS kernels thread tid, register r holds position tid * 32 + r).  An automorphism is
+ *     therefore a pure permutation of the transformed values, with no negation: NTT(sigma_g a)[x] = NTT(a)[pi_g(x)] with
+ *         pi_g(x) = bitrev( ((g * (2 * bitrev(x) + 1)) mod 2n - 1) / 2 ).
+ *     Every size and width class leaves this order (two-pass sizes and the full-width tile kernels included); hoisted rotations rest on it. */
 /* Host only: *elt = 3^(steps mod n/2) mod 2n, the row-rotation element.  n a power of two, 8 <= n <= 2^30. */
 int fhe_galois_element(uint32_t n, int32_t steps, uint32_t *elt);
 /* d_out[b][l] = sigma_g(d_in[b][l]) on [batch][L][n]; out of place (d_out != d_in).  FHE_ERR_INVALID_ARG for an even g or g >= 2n. */
@@ -262,6 +267,38 @@ int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32
  * key switch of fhe_ct_multiply_relin); elsewhere the automorphism followed by fhe_ct_relinearize. */
 int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1, const void *d_c0,
                         const void *d_c1, uint32_t batch);
+
+/* ---- hoisted rotations: decompose a ciphertext once, rotate it many times (Halevi and Shoup) ------------------------------------
+ * sigma_g is a ring automorphism, so it can be applied to the digit polynomials instead of to c1.  With D_{j,k}(c1) the base-2^w digit
+ * polynomials of c1 mod q_j (the digits fhe_ct_relinearize takes of c2, same level order j*K + k), each embedded in every limb i as a
+ * residue of q_i:
+ *     out0 = sigma_g(c0) + sum_{j,k} sigma_g(D_{j,k}(c1)) * b_{j,k}
+ *     out1 =               sum_{j,k} sigma_g(D_{j,k}(c1)) * a_{j,k}          in Z_{q_i}[x]/(x^n + 1), every limb i
+ * sigma_g acts on a digit polynomial as on any element of R_{q_i} (a negated digit d becomes q_i - d).  sum sigma_g(D_{j,k}) g_{j,k} =
+ * sigma_g(c1) and sigma_g(D) has the coefficient magnitudes of D, so the result decrypts under s to sigma_g(m) with the noise bound of
+ * fhe_ct_apply_galois, from the same Galois keys.  It is NOT bit-identical to fhe_ct_apply_galois for g != 1 (the digits of sigma(c1) are
+ * not sigma of the digits of c1); for g = 1 it is.  Equivalently, with sigma_{g^-1} applied to every key row:
+ *     hoisted(c0, c1; kb, ka, g) = sigma_g( relinearize(c0, 0, c1; sigma_{g^-1}(kb), sigma_{g^-1}(ka)) ).
+ * The result depends only on (c0, c1, keys, g, w): never on how many elements are applied, on the kernel path or on the batch.
+ *
+ * fhe_ct_hoist decomposes c1 ([batch][L][n], read only) into its L*K digit polynomials for decomp_bits, transforms each under every limb
+ * and keeps them in the engine's hoist workspace until the next fhe_ct_hoist or fhe_rns_ntt_destroy.  The hoist workspace is a fourth
+ * allocation of its own: no other entry point touches it, and fhe_rns_ntt_reserve / fhe_rns_ntt_workspace_bytes neither size nor count
+ * it.  Its size is batch * L*K * L * n * sizeof(residue) bytes (4 or 8) on the LDS-resident word-sized sizes up to N = 2^14 whose key
+ * sets get packed tables, and batch * L*K * L * n * 32 bytes elsewhere (full-width class, N >= 2^15, FHE_HIP_NO_FUSED_HOIST=1).  A failed
+ * allocation is FHE_ERR_HIP with nothing launched. */
+int fhe_ct_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, const void *d_c1, uint32_t batch);
+/* One rotation from the kept decomposition.  gk: Galois keys of galois_elt, imported with fhe_relin_keys_create.  d_c0 is the c0 that
+ * belongs to the hoisted c1 (read only); outputs distinct from each other and from d_c0.  FHE_ERR_INVALID_ARG, with nothing launched, when
+ * there is no prior fhe_ct_hoist on this engine, batch or gk's decomp_bits differ from the hoist's, the keys belong to another engine, g is
+ * even or >= 2n, or a pointer is null, misaligned or aliased. */
+int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, uint32_t galois_elt, void *d_out0, void *d_out1,
+                                const void *d_c0, uint32_t batch);
+/* Pre-sizes the hoist workspace (and what fhe_ct_hoist / fhe_ct_apply_galois_hoisted need of the three other workspaces) for `batch`
+ * ciphertexts at decomp_bits, so that neither call allocates afterwards; growing the hoist workspace drops a kept decomposition.
+ * fhe_rns_ntt_hoist_bytes reports the hoist workspace's size in bytes (0 until the first hoist or reserve_hoist). */
+int fhe_rns_ntt_reserve_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t batch);
+int fhe_rns_ntt_hoist_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes);
 
 /* ---- blind-rotation inner loop ------------------------------------------------------ */
 /* FHEContext::blind_rotate is only declared in the reference (include/fhe.cuh:139; pipeline prose README.md:146-159).  Its
