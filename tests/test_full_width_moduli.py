@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 
 import ntt_math as nm
+from test_galois import sigma_np
+from test_hoisted import _expected
 from workload import rns_poly
 
 pytestmark = pytest.mark.gpu
@@ -375,6 +377,44 @@ def test_apply_galois_on_generic_moduli(eng, oracle, name):
         assert np.array_equal(o0.download(c0.shape), w0) and np.array_equal(o1.download(c0.shape), w1), x
         e.check_canonical(o0, BATCH); e.check_canonical(o1, BATCH)
     assert np.array_equal(d0.download(c0.shape), c0) and np.array_equal(d1.download(c0.shape), c1)
+
+
+@pytest.mark.parametrize("name", KEYSWITCH_SETS)
+def test_apply_galois_hoisted_on_generic_moduli(eng, oracle, name):
+    """fhe_ct_hoist + fhe_ct_apply_galois_hoisted: digit_embed256_kernel, full-width transforms and relin_mac_perm256_kernel (mont_mul_fips on every
+    digit x key product, the digits read at pi_g), on two-limb (mixed-b, g127) and four-limb residues.  w = 64: a digit is a whole limb.  Against
+    the identity of tests/test_hoisted.py (pinned to the header's definition by test_hoisted_identity_equals_the_header_definition); its sigma and the
+    one written out above are two implementations and must agree.  The full-width class keeps containers: 32 bytes per kept value."""
+    n, w, elements = N, 64, (1, 3, 2 * N - 1)
+
+    def make():
+        moduli = _moduli(name); L = len(moduli)
+        rp = oracle.RnsPlan(n, moduli); K = rp.num_digits(w)
+        kb = _keys(moduli, n, L * K, 700); ka = _keys(moduli, n, L * K, 1300)
+        c0, c1 = _mixed(81, moduli, n, A_SLOTS), _mixed(82, moduli, n, B_SLOTS)
+        for g in elements[1:]:
+            assert np.array_equal(sigma_np(c1, moduli, g), _sigma(c1, moduli, g)), g
+        return moduli, K, kb, ka, c0, c1, [_expected(oracle, n, moduli, w, c0, c1, kb, ka, g) for g in elements]
+    moduli, K, kb, ka, c0, c1, want = _cached(("hoisted", name), make)
+    L = len(moduli)
+    e = _engine(eng, n, moduli)
+    assert e.relin_num_digits(w) == K
+    gk = e.import_relin_keys(w, [_up(eng, k) for k in kb], [_up(eng, k) for k in ka])
+    shape = (BATCH,) + c0.shape[1:]
+    for s, (a0, a1) in enumerate(zip(_groups(c0), _groups(c1))):
+        sl = slice(s * BATCH, (s + 1) * BATCH)
+        d0, d1 = _up(eng, a0), _up(eng, a1)
+        o0, o1 = eng.DeviceBuffer(a0.nbytes), eng.DeviceBuffer(a0.nbytes)
+        e.hoist(w, d1, BATCH)
+        assert e.hoist_bytes() == BATCH * L * K * L * n * 32
+        for g, (w0, w1) in zip(elements, want):
+            e.apply_galois_hoisted(gk, g, o0, o1, d0, BATCH)
+            assert np.array_equal(o0.download(shape), w0[sl]) and np.array_equal(o1.download(shape), w1[sl]), (g, s)
+            e.check_canonical(o0, BATCH); e.check_canonical(o1, BATCH)
+        p0, p1 = eng.DeviceBuffer(a0.nbytes), eng.DeviceBuffer(a0.nbytes)         # sigma_1 is the identity: the plain key switch, bit for bit
+        e.apply_galois(gk, 1, p0, p1, d0, d1, BATCH)
+        assert np.array_equal(p0.download(shape), want[0][0][sl]) and np.array_equal(p1.download(shape), want[0][1][sl]), s
+        assert np.array_equal(d0.download(shape), a0) and np.array_equal(d1.download(shape), a1)
 
 
 @pytest.mark.parametrize("name", KEYSWITCH_SETS)
