@@ -98,6 +98,7 @@ def lib():
         "fhe_poly_mod_switch": ([vp, vp, U64x4, U64x4, sz, vp], ci),
         "fhe_negacyclic_reduce": ([vp, U64x4, sz, vp], ci),
         "fhe_rns_rescale_drop_last": ([vp, vp, vp, u32], ci),
+        "fhe_ct_mod_switch_drop_last": ([vp, u64, P(vp), P(vp), u32, u32], ci),
         "fhe_relin_num_digits": ([vp, u32, P(u32)], ci),
         "fhe_relin_keys_create": ([vp, P(vp), u32, P(vp), P(vp), u32], ci),
         "fhe_relin_keys_destroy": ([vp], ci),
@@ -402,6 +403,14 @@ class RnsNttEngine:
 
     def rescale_drop_last(self, d_out, d_in, batch=1):
         _check(lib().fhe_rns_rescale_drop_last(self.h, _ptr(d_out), _ptr(d_in), batch))
+
+    def ct_mod_switch(self, t, outs, ins, batch=1):
+        """BGV modulus switch: drops the last prime from the components `ins` ([batch][L][n] each) into `outs` ([batch][L-1][n]), one launch;
+        the plaintext modulo t is kept up to the factor q_last^-1 mod t."""
+        k = len(ins)
+        arr = lambda xs: (ctypes.c_void_p * max(len(xs), 1))(*[None if x is None else _ptr(x) for x in xs])   # None: a null pointer (rejected)
+        po, pi = arr(outs), arr(ins)
+        _check(lib().fhe_ct_mod_switch_drop_last(self.h, t, po, pi, k, batch))
 
     def relin_num_digits(self, decomp_bits):
         k = ctypes.c_uint32(0); _check(lib().fhe_relin_num_digits(self.h, decomp_bits, ctypes.byref(k))); return k.value

@@ -9,7 +9,7 @@
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
 //   keyswitch.hip   key import, relinearisation, multiply + relinearise, Galois, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
 //                   key / digit / monomial kernels of ntt_word.hip.h)
-//   rns.hip         CRT tables, to / from RNS, rescale, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
+//   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once
 #include "../../include/fhe_hip.h"
@@ -23,6 +23,7 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "host_math.hpp"
@@ -105,6 +106,9 @@ struct fhe_rns_ntt {
     void *d_bconv_w_minv = nullptr, *d_bconv_w_mat = nullptr;   // word-sized classes: base-conversion operands for bconv_w_target
     const void *bconv_w_target = nullptr;
     std::vector<U256> bconv_moduli, bconv_w_moduli;   // the target bases the cached matrices were built for (a handle address can be re-used)
+    // fhe_ct_mod_switch_drop_last: the constant tables depend on t; one entry per t seen (ModSwitchLimb[L], or E[2L - 1] on the word-sized
+    // kernels; owned by d_tables).  A call with a t that has an entry allocates nothing.
+    std::vector<std::pair<uint64_t, void *>> mod_switch_tables;
     void *d_from_rns_w_minv = nullptr, *d_from_rns_w_M = nullptr;   // integer word classes: CRT operands and Q / q_l (owned by d_tables)
     void *d_to_rns_w = nullptr;          // integer word classes: 2^(W k) mod q_l as pw operands, E[L][256 / W] (owned by d_tables)
     fhe_dev::CrtBig crt_big;

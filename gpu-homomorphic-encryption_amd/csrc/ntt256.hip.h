@@ -34,5 +34,11 @@ struct CrtLimb {
 };
 struct CrtBig { u256 Q; uint64_t inv0, _pad; };
 struct RescaleLimb { u256 qlast_inv_m; };   // (q_last^-1 mod q_l) * R mod q_l
+// BGV modulus switch (fhe_ct_mod_switch_drop_last): entry l < L-1 holds the constants of output limb l, entry L-1 (qlast_inv_m only) -t^-1 mod q_last
+struct ModSwitchLimb {
+    u256 qlast_inv_m;    // (q_last^-1 mod q_l) * R mod q_l          entry L-1: (-t^-1 mod q_last) * R mod q_last
+    u256 t_qlast_inv;    // t * q_last^-1 mod q_l, PLAIN: multiplied into a value that already carries R
+};
+struct ModSwitchPtrs { const void *in[3]; void *out[3]; };   // the components of one call, by value in the kernel arguments
 
 }  // namespace fhe_dev

@@ -68,6 +68,41 @@ rescale_drop_last_kernel(u256 *__restrict__ out, const u256 *__restrict__ in, co
     }
 }
 
+// BGV modulus switch (FHEContext::mod_switch_to_next, include/fhe.cuh:109, undefined in the reference): the rescale above with a rounding term
+// that is a multiple of t.  u = [-r t^-1]_{q_last} centred, out[b][l][x] = (c[b][l][x] + t u) * q_last^-1 mod q_l, for up to three components in
+// one launch.  No CRT constant is read (only q, r2, inv0 of CrtLimb), so the product of the primes may exceed a container.  The magnitude of u
+// may exceed q_l (a wider last prime): mont(mag, R^2) is its residue times R for ANY 256-bit value (to_rns_kernel), and the second product with the
+// PLAIN constant t q_last^-1 takes the R out again.  One lane per (component, b, x).
+__global__ void __launch_bounds__(256)
+mod_switch_drop_last_kernel(ModSwitchPtrs ptrs, const CrtLimb *__restrict__ limbs, const ModSwitchLimb *__restrict__ ms, uint32_t L, uint32_t log_n,
+                            size_t per_comp /* batch * n */, size_t count /* components * batch * n */) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, n = (size_t)1 << log_n;
+    const u256 ql = limbs[L - 1].q;
+    const uint64_t ql_inv0 = limbs[L - 1].inv0;
+    const u256 u_m = ms[L - 1].qlast_inv_m;
+    u256 half;                                                       // floor(q_last / 2)
+#pragma unroll
+    for (int i = 0; i < 4; i++) half.l[i] = (ql.l[i] >> 1) | (i < 3 ? ql.l[i + 1] << 63 : 0);
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < count; g += stride) {
+        const uint32_t c = g >= 2 * per_comp ? 2 : g >= per_comp ? 1 : 0;
+        const size_t r = g - c * per_comp, b = r >> log_n, x = r & (n - 1);
+        const u256 *__restrict__ in = (const u256 *)(c == 0 ? ptrs.in[0] : c == 1 ? ptrs.in[1] : ptrs.in[2]);
+        u256 *__restrict__ out = (u256 *)(c == 0 ? ptrs.out[0] : c == 1 ? ptrs.out[1] : ptrs.out[2]);
+        const u256 u = mont_mul(load_u256(in + (b * L + (L - 1)) * n + x), u_m, ql, ql_inv0);
+        bool neg = false;
+#pragma unroll
+        for (int i = 3; i >= 0; i--) { if (u.l[i] != half.l[i]) { neg = u.l[i] > half.l[i]; break; } }
+        u256 mag;
+        if (neg) sub256(mag, ql, u); else mag = u;
+        for (uint32_t l = 0; l + 1 < L; l++) {
+            const CrtLimb &P = limbs[l];
+            const u256 a = mont_mul(load_u256(in + (b * L + l) * n + x), ms[l].qlast_inv_m, P.q, P.inv0);
+            const u256 m = mont_mul(mont_mul(mag, P.r2, P.q, P.inv0), ms[l].t_qlast_inv, P.q, P.inv0);
+            store_u256(out + (b * (L - 1) + l) * n + x, neg ? sub_mod(a, m, P.q) : add_mod(a, m, P.q));
+        }
+    }
+}
+
 // Fast base conversion (Bajard et al.; fast_base_conversion_kernel, include/rns.cuh:116-125, undefined in the reference):
 // out[b][j][x] = sum_i [x_i * (Q/q_i)^-1]_{q_i} * (Q/q_i) mod p_j.  `mat` holds ((Q/q_i) mod p_j) * R_j, row-major [L][Lp].
 // One lane per (b, x): the L scaled residues t_i are formed once and reused for every target prime.

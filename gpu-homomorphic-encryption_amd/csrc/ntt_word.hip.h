@@ -2,6 +2,7 @@
 // canonical-input scan, key-table packing, the general-path relinearisation pieces, RNS conversions (row N2) and the monomial
 // multiply of the blind-rotation general path.  Each kernel is instantiated by the one host source that launches it (engine.h); the LDS-resident transform kernels are in ntt_lds.hip.h.
 #pragma once
+#include "ntt256.hip.h"
 #include "ntt_field.hip.h"
 
 namespace fhe_dev {
@@ -243,6 +244,40 @@ rescale_word_kernel(typename F::V16 *__restrict__ out, const typename F::V16 *__
             const E a = mul_const<F>(inv_ops[l], xl, P), m = mul_const<F>(inv_ops[l], mag, P);
             const E o = neg ? F::ew_add(a, m, P.q) : F::ew_sub(a, m, P.q);
             typename F::V16 *dst = out + (((b * (L - 1) + l) << log_n) + x) * 2;
+            __builtin_nontemporal_store(F::pack(o), dst);
+            __builtin_nontemporal_store(F::pack((E)0), dst + 1);
+        }
+    }
+}
+
+// BGV modulus switch (FHEContext::mod_switch_to_next, include/fhe.cuh:109, declared only): the rescale above with the rounding term made a
+// multiple of t.  u = [-r t^-1]_{q_last} centred (r the last-limb residue), out[b][l][x] = (in[b][l][x] + t u) q_last^-1 mod q_l, for up to three
+// ciphertext components in one launch.  ops[0] is the pw operand of -t^-1 mod q_last (a constant of the LAST limb); ops[1 + 2l], ops[2 + 2l] those
+// of q_last^-1 and (t mod q_l) q_last^-1 modulo q_l.  (x_l + t u) inv = x_l inv +- mag (t inv) with u = +-mag, mag <= (q_last - 1) / 2: like `mag` of
+// the rescale a residue of another prime of the class, a valid second operand as it stands (F32: any 32-bit word; F64 / F64X: any 64-bit word;
+// F52: pw_mul takes a in [0, q), |b| < 2^48, and mag < 2^42).  One lane per (component, b, x), whole containers stored, as the rescale.
+template <class F>
+__global__ void __launch_bounds__(256)
+mod_switch_word_kernel(ModSwitchPtrs ptrs, const Limb<F> *__restrict__ limbs, const typename F::E *__restrict__ ops, uint32_t L, uint32_t log_n,
+                       size_t per_comp /* batch * n */, size_t count /* components * batch * n */) {
+    using E = typename F::E; using V = typename F::V16;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, n = (size_t)1 << log_n;
+    const Limb<F> &PL = limbs[L - 1];
+    const E q_last = PL.q, half = (E)(((uint64_t)q_last - 1) >> 1), u_op = ops[0];
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < count; g += stride) {
+        const uint32_t c = g >= 2 * per_comp ? 2 : g >= per_comp ? 1 : 0;
+        const size_t r = g - c * per_comp, b = r >> log_n, x = r & (n - 1);
+        const V *__restrict__ in = (const V *)(c == 0 ? ptrs.in[0] : c == 1 ? ptrs.in[1] : ptrs.in[2]);
+        V *__restrict__ out = (V *)(c == 0 ? ptrs.out[0] : c == 1 ? ptrs.out[1] : ptrs.out[2]);
+        const E u = mul_const<F>(u_op, F::load_low(in + (((b * L + (L - 1)) << log_n) + x) * 2), PL);
+        const bool neg = u > half;
+        const E mag = neg ? q_last - u : u;
+        for (uint32_t l = 0; l + 1 < L; l++) {
+            const Limb<F> &P = limbs[l];
+            const E xl = F::load_low(in + (((b * L + l) << log_n) + x) * 2);
+            const E a = mul_const<F>(ops[1 + 2 * l], xl, P), m = mul_const<F>(ops[2 + 2 * l], mag, P);
+            const E o = neg ? F::ew_sub(a, m, P.q) : F::ew_add(a, m, P.q);
+            V *dst = out + (((b * (L - 1) + l) << log_n) + x) * 2;
             __builtin_nontemporal_store(F::pack(o), dst);
             __builtin_nontemporal_store(F::pack((E)0), dst + 1);
         }

@@ -1,4 +1,4 @@
-// rns.hip -- RNS entry / exit: CRT tables, to / from RNS, rescale, fast base conversion.
+// rns.hip -- RNS entry / exit: CRT tables, to / from RNS, rescale, BGV modulus switch, fast base conversion.
 #include "engine.h"
 
 #include <type_traits>
@@ -209,6 +209,86 @@ extern "C" int fhe_rns_rescale_drop_last(fhe_rns_ntt_t *h, void *d_out, const vo
     return post_launch(h->stream, "rescale_drop_last_kernel");
 }
 
+
+// ---- BGV modulus switch ---------------------------------------------------------------------------------------------------------
+static void *find_mod_switch_table(const fhe_rns_ntt *h, uint64_t t) {
+    for (const auto &e : h->mod_switch_tables) if (e.first == t) return e.second;
+    return nullptr;
+}
+template <class F>
+static int mod_switch_word(fhe_rns_ntt *h, uint64_t t, const fhe_dev::ModSwitchPtrs &ptrs, uint32_t comps, uint32_t batch) {
+    using E = typename F::E;
+    void *d_ops = find_mod_switch_table(h, t);
+    if (!d_ops) {
+        const uint32_t L = h->L;
+        std::vector<E> ops(2 * (size_t)L - 1);
+        const uint64_t ql = h->moduli[L - 1].w[0];
+        ops[0] = word_operand<F>(ql - inv_mod_u64(t % ql, ql), ql);                          // -t^-1 mod q_last (t != 0 mod q_last: checked by the caller)
+        for (uint32_t l = 0; l + 1 < L; l++) {
+            const uint64_t q = h->moduli[l].w[0], inv = inv_mod_u64(ql % q, q);
+            ops[1 + 2 * l] = word_operand<F>(inv, q);
+            ops[2 + 2 * l] = word_operand<F>((uint64_t)((fhe_host::u128)(t % q) * inv % q), q);   // t reduced here: it may exceed q_l
+        }
+        int rc = upload(h, ops, &d_ops); if (rc) return rc;
+        h->mod_switch_tables.emplace_back(t, d_ops);
+    }
+    const size_t per_comp = (size_t)batch * h->n, count = per_comp * comps;
+    hipLaunchKernelGGL((fhe_dev::mod_switch_word_kernel<F>), dim3(ew_grid(count)), dim3(256), 0, h->stream, ptrs, (const fhe_dev::Limb<F> *)h->d_limbs,
+                       (const E *)d_ops, h->L, h->log_n, per_comp, count);
+    return post_launch(h->stream, "mod_switch_word_kernel");
+}
+extern "C" int fhe_ct_mod_switch_drop_last(fhe_rns_ntt_t *h, uint64_t t, void *const *d_out, const void *const *d_in, uint32_t num_components,
+                                           uint32_t batch) {
+    int rc = check_call(h, batch, "ct_mod_switch_drop_last"); if (rc) return rc;
+    if (num_components < 1 || num_components > 3) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: 1 to 3 components");
+    if (!d_out || !d_in) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: null argument");
+    fhe_dev::ModSwitchPtrs ptrs = {};
+    for (uint32_t c = 0; c < num_components; c++) {
+        if (!d_out[c] || !d_in[c]) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: null component pointer");
+        if ((rc = check_aligned({d_out[c], d_in[c]}, "ct_mod_switch_drop_last"))) return rc;
+        ptrs.in[c] = d_in[c]; ptrs.out[c] = d_out[c];
+    }
+    for (uint32_t c = 0; c < num_components; c++) {
+        for (uint32_t k = 0; k < num_components; k++)
+            if (d_out[c] == d_in[k]) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: an output aliases an input");
+        for (uint32_t k = c + 1; k < num_components; k++)
+            if (d_out[c] == d_out[k]) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: two outputs are the same buffer");
+    }
+    if (h->L < 2) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: needs at least two primes");
+    if (t < 2) return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: t must be >= 2");
+    const U256 &ql = h->moduli[h->L - 1];
+    if (!(ql.w[1] | ql.w[2] | ql.w[3]) && t % ql.w[0] == 0)                                   // a wider q_last exceeds any 64-bit t
+        return fail(FHE_ERR_INVALID_ARG, "ct_mod_switch_drop_last: t must be invertible modulo the last prime");
+    if (h->width != FHE_WIDTH_256 && !h->env.no_word_conversions)       // word-sized classes: a streaming kernel on the field type
+        return with_word_field(h, [&](auto f) { return mod_switch_word<decltype(f)>(h, t, ptrs, num_components, batch); });
+    if ((rc = ensure_crt(h))) return rc;
+    void *d_ms = find_mod_switch_table(h, t);
+    if (!d_ms) {
+        const uint32_t L = h->L;
+        std::vector<fhe_dev::ModSwitchLimb> ms(L);
+        std::memset(ms.data(), 0, L * sizeof(fhe_dev::ModSwitchLimb));
+        {
+            fhe_host::Mod M(ql);
+            U256 qm2; fhe_host::sub_to(qm2, M.q, U256(2));
+            const U256 tinv_m = M.pow_m(M.to_mont(M.reduce(U256(t))), qm2);                  // (t^-1 mod q_last) * R
+            const U256 neg_m = M.sub(U256(), tinv_m);
+            std::memcpy(ms[L - 1].qlast_inv_m.l, neg_m.w, 32);
+        }
+        for (uint32_t l = 0; l + 1 < L; l++) {
+            fhe_host::Mod M(h->moduli[l]);
+            U256 qm2; fhe_host::sub_to(qm2, M.q, U256(2));
+            const U256 inv_m = M.pow_m(M.to_mont(M.reduce(ql)), qm2);                        // (q_last^-1 mod q_l) * R
+            const U256 t_inv = M.mont(M.reduce(U256(t)), inv_m);                             // t * q_last^-1 mod q_l, plain
+            std::memcpy(ms[l].qlast_inv_m.l, inv_m.w, 32); std::memcpy(ms[l].t_qlast_inv.l, t_inv.w, 32);
+        }
+        if ((rc = upload(h, ms, &d_ms))) return rc;
+        h->mod_switch_tables.emplace_back(t, d_ms);
+    }
+    const size_t per_comp = (size_t)batch * h->n, count = per_comp * num_components;
+    hipLaunchKernelGGL(fhe_dev::mod_switch_drop_last_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, ptrs, (const fhe_dev::CrtLimb *)h->d_crt,
+                       (const fhe_dev::ModSwitchLimb *)d_ms, h->L, h->log_n, per_comp, count);
+    return post_launch(h->stream, "mod_switch_drop_last_kernel");
+}
 
 extern "C" int fhe_rns_fast_base_convert(fhe_rns_ntt_t *h, fhe_rns_ntt_t *target, void *d_out, const void *d_in, uint32_t batch) {
     int rc = check_call(h, batch, "fast_base_convert"); if (rc) return rc;

@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <stdexcept>
+#include <string>
 #include <memory>
 #include <random>
 #include <vector>
@@ -29,10 +30,13 @@ struct RelinKeys {                                            // include/fhe.cuh
     // engine-side copy (NTT domain, packed for the fused key-switch kernel); built on first use
     mutable fhe_relin_keys_t *imported = nullptr;
     mutable const void *imported_for = nullptr;
+    // the same rows imported on the engines of lower levels (index = level, entry 0 unused): derived by slicing, never regenerated
+    mutable std::vector<fhe_relin_keys_t *> imported_levels;
     RelinKeys() = default;
     RelinKeys(const RelinKeys &) = delete;
     RelinKeys &operator=(const RelinKeys &) = delete;
-    ~RelinKeys() { fhe_relin_keys_destroy(imported); for (PublicKey *k : rlk_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } } }
+    void drop_levels() const { for (fhe_relin_keys_t *k : imported_levels) fhe_relin_keys_destroy(k); imported_levels.clear(); }
+    ~RelinKeys() { drop_levels(); fhe_relin_keys_destroy(imported); for (PublicKey *k : rlk_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } } }
 };
 
 struct GaloisKeys {                                           // include/fhe.cuh:58-61
@@ -43,10 +47,13 @@ struct GaloisKeys {                                           // include/fhe.cuh
     // engine-side copies (one imported key set per element, NTT domain, packed for the fused key switch); built on first use
     mutable std::vector<fhe_relin_keys_t *> imported;
     mutable const void *imported_for = nullptr;
+    mutable std::vector<std::vector<fhe_relin_keys_t *>> imported_levels;   // [level][element], entry 0 unused: sliced from the same rows
     GaloisKeys() = default;
     GaloisKeys(const GaloisKeys &) = delete;
     GaloisKeys &operator=(const GaloisKeys &) = delete;
+    void drop_levels() const { for (auto &lv : imported_levels) for (fhe_relin_keys_t *k : lv) fhe_relin_keys_destroy(k); imported_levels.clear(); }
     ~GaloisKeys() {
+        drop_levels();
         for (fhe_relin_keys_t *k : imported) fhe_relin_keys_destroy(k);
         for (PublicKey *k : gal_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } }
     }
@@ -57,9 +64,13 @@ struct Plaintext {                                            // include/fhe.cuh
     bool is_ntt_form = false;
 };
 
+// Levels.  Level l means the first L - l primes of the basis: a ciphertext at level l has components of L - l limbs and lives on the
+// context's engine for those primes.  mod_switch_to_next moves it one level down and divides its noise by the dropped prime; the
+// plaintext picks up the factor q_last^-1 mod t, which `correction` keeps: the ciphertext decrypts to correction * m mod t.
 struct Ciphertext {                                           // include/fhe.cuh:63-69
     std::vector<Polynomial *> components;
     uint32_t level = 0;
+    uint64_t correction = 1;
     float noise_budget = 0.f;
     bool is_ntt_form = false;
 };
@@ -91,41 +102,81 @@ public:
     FHEContext(const FHEContext &) = delete;
     FHEContext &operator=(const FHEContext &) = delete;
 
-    Polynomial *new_polynomial() const { return new Polynomial(params_.n, params_.rns_moduli[0], (uint32_t)params_.rns_moduli.size()); }
+    // a zeroed polynomial of level `level`: L - level limbs
+    Polynomial *new_polynomial(uint32_t level = 0) const {
+        return new Polynomial(params_.n, params_.rns_moduli[0], (uint32_t)params_.rns_moduli.size() - level);
+    }
+    uint32_t num_levels() const { return (uint32_t)params_.rns_moduli.size(); }               // levels 0 .. L - 1
+    // the engine of a level (the first L - level primes), created on first use; level 0 is params().rns_ntt
+    RNS_NTTEngine &engine(uint32_t level) {
+        if (level >= num_levels()) throw std::runtime_error("FHEContext: no such level");
+        if (!level) return *params_.rns_ntt;
+        if (level_engines_.size() < num_levels()) level_engines_.resize(num_levels());
+        if (!level_engines_[level])
+            level_engines_[level].reset(new RNS_NTTEngine(params_.n, params_.rns_moduli.data(), num_levels() - level));
+        return *level_engines_[level];
+    }
 
     // src/fhe.cu:187-197
+    // Operands must be at the same level (no automatic alignment).  With unequal corrections both operands are first brought to correction 1
+    // on a copy (normalized()), which costs up to log2(t / 2) bits of noise; equal corrections are kept.
     void add(Ciphertext &result, const Ciphertext &a, const Ciphertext &b) {
+        same_level(a, b, "FHEContext::add");
+        if (a.correction != b.correction) {
+            Ciphertext na, nb;
+            const Ciphertext &x = normalized(na, a), &y = normalized(nb, b);
+            add(result, x, y);
+            device_synchronize();
+            free_components(na); free_components(nb);
+            return;
+        }
+        RNS_NTTEngine &E = engine(a.level);
         size_t num = std::max(a.components.size(), b.components.size());
-        ensure_components(result, num);
+        ensure_components(result, num, a.level);
         for (size_t i = 0; i < num; i++) {
             if (i < a.components.size() && i < b.components.size())
-                params_.rns_ntt->add_rns(result.components[i]->coeffs, a.components[i]->coeffs, b.components[i]->coeffs);
+                E.add_rns(result.components[i]->coeffs, a.components[i]->coeffs, b.components[i]->coeffs);
             else {
                 const Polynomial *src = i < a.components.size() ? a.components[i] : b.components[i];
-                check(fhe_hip_memcpy_d2d(result.components[i]->coeffs, src->coeffs, src->count() * sizeof(uint256_t)), "add copy");
+                if (src != result.components[i])
+                    check(fhe_hip_memcpy_d2d(result.components[i]->coeffs, src->coeffs, src->count() * sizeof(uint256_t)), "add copy");
             }
         }
         result.noise_budget = std::min(a.noise_budget, b.noise_budget);
-        result.level = std::max(a.level, b.level);
+        result.level = a.level; result.correction = a.correction;
     }
     // sub / add_plain / sub_plain / multiply_plain (include/fhe.cuh:98-104, declared only in the reference).  Plaintexts are the
     // encode()d polynomials (reduced mod t in every limb); with the mirror's BGV-style encryption c0 + c1*s = m + t*e they act
     // on the message directly: component-wise subtraction, +-pt on c0, every component times pt.
     void sub(Ciphertext &result, const Ciphertext &a, const Ciphertext &b) {
         if (a.components.size() != b.components.size()) throw std::runtime_error("FHEContext::sub: ciphertexts of different size");
-        ensure_components(result, a.components.size());
+        same_level(a, b, "FHEContext::sub");
+        if (a.correction != b.correction) {
+            Ciphertext na, nb;
+            const Ciphertext &x = normalized(na, a), &y = normalized(nb, b);
+            sub(result, x, y);
+            device_synchronize();
+            free_components(na); free_components(nb);
+            return;
+        }
+        RNS_NTTEngine &E = engine(a.level);
+        ensure_components(result, a.components.size(), a.level);
         for (size_t i = 0; i < a.components.size(); i++)
-            params_.rns_ntt->sub_rns(result.components[i]->coeffs, a.components[i]->coeffs, b.components[i]->coeffs);
+            E.sub_rns(result.components[i]->coeffs, a.components[i]->coeffs, b.components[i]->coeffs);
         result.noise_budget = std::min(a.noise_budget, b.noise_budget);
-        result.level = std::max(a.level, b.level);
+        result.level = a.level; result.correction = a.correction;
     }
     void add_plain(Ciphertext &result, const Ciphertext &ct, const Plaintext &pt) { plain_addsub(result, ct, pt, true); }
     void sub_plain(Ciphertext &result, const Ciphertext &ct, const Plaintext &pt) { plain_addsub(result, ct, pt, false); }
+    // A level-l plaintext is the first L - l limbs of the encoded one: a contiguous prefix of its [L][n] buffer, used in place.  The product
+    // keeps the correction of ct (correction * m * p); add_plain / sub_plain need correction 1 and normalise a copy of ct first (up to
+    // log2(t / 2) bits of noise).
     void multiply_plain(Ciphertext &result, const Ciphertext &ct, const Plaintext &pt) {
-        ensure_components(result, ct.components.size());
+        RNS_NTTEngine &E = engine(ct.level);
+        ensure_components(result, ct.components.size(), ct.level);
         for (size_t i = 0; i < ct.components.size(); i++)
-            params_.rns_ntt->multiply_rns(result.components[i]->coeffs, ct.components[i]->coeffs, pt.poly->coeffs);
-        result.noise_budget = ct.noise_budget; result.level = ct.level;
+            E.multiply_rns(result.components[i]->coeffs, ct.components[i]->coeffs, pt.poly->coeffs);
+        result.noise_budget = ct.noise_budget; result.level = ct.level; result.correction = ct.correction;
     }
 
     // src/fhe.cu:199-224: tensor product (4 forward + 3 inverse transforms instead of the reference's 8 + 4), then relinearisation.
@@ -133,21 +184,26 @@ public:
     // RelinKeys the result keeps its three components, as relinearize() does.
     void multiply(Ciphertext &result, const Ciphertext &a, const Ciphertext &b, const RelinKeys &rlk) {
         if (a.components.size() != 2 || b.components.size() != 2) throw std::runtime_error("FHEContext::multiply: 2-component ciphertexts expected");
+        same_level(a, b, "FHEContext::multiply");
+        const uint32_t level = a.level;
+        const uint64_t corr = mul_mod_t(a.correction, b.correction);
+        const float nb = a.noise_budget + b.noise_budget + 10;        // the reference's rough estimate (src/fhe.cu:222)
+        RNS_NTTEngine &E = engine(level);
         if (rlk.rlk_keys.empty()) {
-            ensure_components(result, 3);
-            params_.rns_ntt->tensor_multiply(result.components[0]->coeffs, result.components[1]->coeffs, result.components[2]->coeffs,
-                                             a.components[0]->coeffs, a.components[1]->coeffs, b.components[0]->coeffs, b.components[1]->coeffs);
+            ensure_components(result, 3, level);
+            E.tensor_multiply(result.components[0]->coeffs, result.components[1]->coeffs, result.components[2]->coeffs,
+                              a.components[0]->coeffs, a.components[1]->coeffs, b.components[0]->coeffs, b.components[1]->coeffs);
+            device_synchronize();
         } else {
-            import_relin_keys(rlk);
-            ensure_components(result, 2);
+            fhe_relin_keys_t *keys = relin_keys_at(rlk, level);
+            ensure_components(result, 2, level);
             while (result.components.size() > 2) { delete result.components.back(); result.components.pop_back(); }
-            check(fhe_ct_multiply_relin(params_.rns_ntt->handle(), rlk.imported, result.components[0]->coeffs, result.components[1]->coeffs,
+            check(fhe_ct_multiply_relin(E.handle(), keys, result.components[0]->coeffs, result.components[1]->coeffs,
                                         a.components[0]->coeffs, a.components[1]->coeffs, b.components[0]->coeffs, b.components[1]->coeffs, 1),
                   "FHEContext::multiply");
             device_synchronize();
         }
-        result.noise_budget = a.noise_budget + b.noise_budget + 10;   // the reference's rough estimate (src/fhe.cu:222)
-        result.level = std::max(a.level, b.level);
+        result.noise_budget = nb; result.level = level; result.correction = corr;
     }
 
     // src/fhe.cu:226-235 is a stub that drops c2 (which breaks decryption); docs/ARCHITECTURE.md:319-326 gives the
@@ -157,8 +213,7 @@ public:
         if (ct.components.size() <= 2) return;                                              // src/fhe.cu:227
         if (rlk.rlk_keys.empty()) return;
         if (ct.components.size() != 3) throw std::runtime_error("FHEContext::relinearize: 3-component ciphertext expected");
-        import_relin_keys(rlk);
-        check(fhe_ct_relinearize(params_.rns_ntt->handle(), rlk.imported, ct.components[0]->coeffs, ct.components[1]->coeffs,
+        check(fhe_ct_relinearize(engine(ct.level).handle(), relin_keys_at(rlk, ct.level), ct.components[0]->coeffs, ct.components[1]->coeffs,
                                  ct.components[2]->coeffs, 1), "FHEContext::relinearize");
         device_synchronize();
         delete ct.components[2];
@@ -168,12 +223,26 @@ public:
     // hands the key polynomials to the engine once (transformed and packed inside the library), cached in the RelinKeys object
     void import_relin_keys(const RelinKeys &rlk) {
         if (rlk.imported && rlk.imported_for == params_.rns_ntt) return;
-        fhe_relin_keys_destroy(rlk.imported); rlk.imported = nullptr;
+        fhe_relin_keys_destroy(rlk.imported); rlk.imported = nullptr; rlk.drop_levels();
         std::vector<const void *> kb, ka;
         for (const PublicKey *k : rlk.rlk_keys) { kb.push_back(k->pk0->coeffs); ka.push_back(k->pk1->coeffs); }
         check(fhe_relin_keys_create(params_.rns_ntt->handle(), &rlk.imported, rlk.decomp_bits, kb.data(), ka.data(), (uint32_t)kb.size()),
               "FHEContext: relinearisation key import");
         rlk.imported_for = params_.rns_ntt;
+    }
+
+    // The imported key set for ciphertexts at `level`.  Level 0 is import_relin_keys.  Lower levels are DERIVED from the same rows: top-level
+    // row j*K + k is (b, a) with the gadget 2^(kw) in limb j only, and the first L' = L - level limbs of a row are the level's row, so the
+    // level's key set is rows j*K + k for j < L', k < K' (K' = digits per limb of the level's engine, K' <= K) through the same device pointers.
+    fhe_relin_keys_t *relin_keys_at(const RelinKeys &rlk, uint32_t level) {
+        import_relin_keys(rlk);
+        if (!level) return rlk.imported;
+        if (rlk.imported_levels.size() < num_levels()) rlk.imported_levels.resize(num_levels(), nullptr);
+        if (!rlk.imported_levels[level]) {
+            std::vector<const PublicKey *> rows(rlk.rlk_keys.begin(), rlk.rlk_keys.end());
+            rlk.imported_levels[level] = import_sliced(rows.data(), rows.size(), rlk.decomp_bits, level);
+        }
+        return rlk.imported_levels[level];
     }
 
     // number of key levels relinkey_gen must produce for this context: L limbs x ceil(bits(q_max) / decomp_bits) digits
@@ -310,18 +379,18 @@ public:
         if (ct.components.size() != 2) throw std::runtime_error("FHEContext::apply_galois: 2-component ciphertext expected (relinearize first)");
         const size_t idx = galois_key_index(gal_keys, galois_elt);
         if (idx == (size_t)-1) throw std::runtime_error("FHEContext::apply_galois: no Galois key for this element");
-        import_galois_keys(gal_keys);
-        std::unique_ptr<Polynomial> o0(new_polynomial()), o1(new_polynomial());     // the ABI call is out of place
-        check(fhe_ct_apply_galois(params_.rns_ntt->handle(), gal_keys.imported[idx], galois_elt, o0->coeffs, o1->coeffs, ct.components[0]->coeffs,
+        const float nb = ct.noise_budget; const uint32_t lv = ct.level; const uint64_t corr = ct.correction;   // sigma_g(correction * m) = correction * sigma_g(m)
+        const std::vector<fhe_relin_keys_t *> &keys = galois_keys_at(gal_keys, lv);
+        std::unique_ptr<Polynomial> o0(new_polynomial(lv)), o1(new_polynomial(lv));     // the ABI call is out of place
+        check(fhe_ct_apply_galois(engine(lv).handle(), keys[idx], galois_elt, o0->coeffs, o1->coeffs, ct.components[0]->coeffs,
                                   ct.components[1]->coeffs, 1), "FHEContext::apply_galois");
-        const float nb = ct.noise_budget; const uint32_t lv = ct.level;
-        ensure_components(result, 2);
+        ensure_components(result, 2, lv);
         while (result.components.size() > 2) { delete result.components.back(); result.components.pop_back(); }
         const size_t bytes = o0->count() * sizeof(uint256_t);
         check(fhe_hip_memcpy_d2d(result.components[0]->coeffs, o0->coeffs, bytes), "apply_galois copy");
         check(fhe_hip_memcpy_d2d(result.components[1]->coeffs, o1->coeffs, bytes), "apply_galois copy");
         device_synchronize();
-        result.noise_budget = nb; result.level = lv; result.is_ntt_form = false;
+        result.noise_budget = nb; result.level = lv; result.correction = corr; result.is_ntt_form = false;
     }
     // FHEContext::rotate_rows (include/fhe.cuh:112-113): cyclic left shift by `steps` of both rows.  One call when the key set holds 3^steps,
     // else a composition of the power-of-two steps it holds (either direction); throws when the step cannot be reached.
@@ -343,7 +412,7 @@ public:
         std::vector<uint32_t> path;
         if (!compose(1, path) && !compose(-1, path)) throw std::runtime_error("FHEContext::rotate_rows: no composition of the Galois keys reaches this step");
         if (path.empty()) {                                         // r = 0: the identity
-            if (&result != &ct) { ensure_components(result, ct.components.size()); copy_ciphertext(result, ct); }
+            if (&result != &ct) { ensure_components(result, ct.components.size(), ct.level); copy_ciphertext(result, ct); }
             return;
         }
         apply_galois(result, ct, path[0], gal_keys);
@@ -362,17 +431,18 @@ public:
             if (r && galois_key_index(gal_keys, g) == (size_t)-1) throw std::runtime_error("FHEContext::rotate_rows_hoisted: no Galois key for a step");
             elts.push_back(r ? g : 1);
         }
-        import_galois_keys(gal_keys);
+        const std::vector<fhe_relin_keys_t *> &keys = galois_keys_at(gal_keys, ct.level);
+        fhe_rns_ntt_t *h = engine(ct.level).handle();
         std::vector<Ciphertext> out(steps.size());
         if (!elts.empty())
-            check(fhe_ct_hoist(params_.rns_ntt->handle(), gal_keys.decomp_bits, ct.components[1]->coeffs, 1), "FHEContext::rotate_rows_hoisted: hoist");
+            check(fhe_ct_hoist(h, gal_keys.decomp_bits, ct.components[1]->coeffs, 1), "FHEContext::rotate_rows_hoisted: hoist");
         for (size_t s = 0; s < elts.size(); s++) {
-            ensure_components(out[s], 2);
+            ensure_components(out[s], 2, ct.level);
             if (elts[s] == 1) copy_ciphertext(out[s], ct);
-            else check(fhe_ct_apply_galois_hoisted(params_.rns_ntt->handle(), gal_keys.imported[galois_key_index(gal_keys, elts[s])], elts[s],
+            else check(fhe_ct_apply_galois_hoisted(h, keys[galois_key_index(gal_keys, elts[s])], elts[s],
                                                    out[s].components[0]->coeffs, out[s].components[1]->coeffs, ct.components[0]->coeffs, 1),
                        "FHEContext::rotate_rows_hoisted");
-            out[s].noise_budget = ct.noise_budget; out[s].level = ct.level; out[s].is_ntt_form = false;
+            out[s].noise_budget = ct.noise_budget; out[s].level = ct.level; out[s].correction = ct.correction; out[s].is_ntt_form = false;
         }
         device_synchronize();
         return out;
@@ -384,7 +454,7 @@ public:
     void import_galois_keys(const GaloisKeys &gk) {
         if (gk.imported_for == params_.rns_ntt && gk.imported.size() == gk.elements.size()) return;
         for (fhe_relin_keys_t *k : gk.imported) fhe_relin_keys_destroy(k);
-        gk.imported.clear();
+        gk.imported.clear(); gk.drop_levels();
         const uint32_t levels = relin_levels(gk.decomp_bits);
         if (gk.gal_keys.size() != (size_t)levels * gk.elements.size()) throw std::runtime_error("FHEContext: Galois key set of the wrong size");
         for (size_t e = 0; e < gk.elements.size(); e++) {
@@ -395,6 +465,61 @@ public:
             gk.imported.push_back(h);
         }
         gk.imported_for = params_.rns_ntt;
+    }
+
+    // every element's key set for ciphertexts at `level`: level 0 is import_galois_keys, lower levels are sliced from the same rows (relin_keys_at)
+    const std::vector<fhe_relin_keys_t *> &galois_keys_at(const GaloisKeys &gk, uint32_t level) {
+        import_galois_keys(gk);
+        if (!level) return gk.imported;
+        if (gk.imported_levels.size() < num_levels()) gk.imported_levels.resize(num_levels());
+        std::vector<fhe_relin_keys_t *> &sets = gk.imported_levels[level];
+        if (sets.size() != gk.elements.size()) {
+            for (fhe_relin_keys_t *k : sets) fhe_relin_keys_destroy(k);
+            sets.clear();
+            const size_t rows = gk.gal_keys.size() / gk.elements.size();
+            for (size_t e = 0; e < gk.elements.size(); e++) sets.push_back(import_sliced(gk.gal_keys.data() + e * rows, rows, gk.decomp_bits, level));
+        }
+        return sets;
+    }
+
+    // ---- levels: BGV modulus switching down the prime chain (include/fhe.cuh:109-110, 122; declared only in the reference) -------------------
+    // Drops the last prime of ct's level from all its components (2 or 3) in one fhe_ct_mod_switch_drop_last call: the noise shrinks by about
+    // the dropped prime (plus a rounding term of the size of a fresh ciphertext's noise), the plaintext picks up q_last^-1 mod t (correction).
+    void mod_switch_to_next(Ciphertext &ct) {
+        const uint32_t L = num_levels(), k = (uint32_t)ct.components.size();
+        if (ct.level + 1 >= L) throw std::runtime_error("FHEContext::mod_switch_to_next: the ciphertext is at the last level");
+        if (k < 1 || k > 3) throw std::runtime_error("FHEContext::mod_switch_to_next: 1 to 3 components expected");
+        const uint256_t &q_last = params_.rns_moduli[L - 1 - ct.level];
+        const uint64_t t = params_.t;
+        std::vector<Polynomial *> outs;
+        std::vector<uint256_t *> d_out; std::vector<const uint256_t *> d_in;
+        for (uint32_t i = 0; i < k; i++) { outs.push_back(new_polynomial(ct.level + 1)); d_out.push_back(outs[i]->coeffs); d_in.push_back(ct.components[i]->coeffs); }
+        engine(ct.level).mod_switch_drop_last(t, d_out.data(), d_in.data(), k);
+        device_synchronize();
+        for (uint32_t i = 0; i < k; i++) { delete ct.components[i]; ct.components[i] = outs[i]; }
+        ct.level += 1;
+        ct.correction = mul_mod_t(ct.correction, inv_mod_t(mod_small(q_last.limbs, t)));
+    }
+    void mod_switch_to_level(Ciphertext &ct, uint32_t target) {
+        if (target < ct.level) throw std::runtime_error("FHEContext::mod_switch_to_level: the target is above the ciphertext's level");
+        if (target >= num_levels()) throw std::runtime_error("FHEContext::mod_switch_to_level: no such level");
+        while (ct.level < target) mod_switch_to_next(ct);
+    }
+    // floor(log2(Q_l / 2)) - ceil(log2(max_i |v_i|)), clipped at 0: v the centred value of c0 + c1 s (+ c2 s^2) modulo Q_l, i.e. the bits left
+    // before the noise wraps around Q_l and decryption fails.
+    float estimate_noise_budget(const Ciphertext &ct, const SecretKey &sk) {
+        uint64_t Q[4], half[4];
+        const std::vector<uint256_t> v = decrypt_values(ct, sk, Q, half);
+        uint64_t mx[4] = {0, 0, 0, 0};
+        for (const uint256_t &x : v) {
+            uint64_t a[4];
+            if (greater(x.limbs, half)) sub4(a, Q, x.limbs); else std::copy(x.limbs, x.limbs + 4, a);
+            if (greater(a, mx)) std::copy(a, a + 4, mx);
+        }
+        const int qb = bit_length(Q), mb = bit_length(mx);
+        const bool pow2 = __builtin_popcountll(mx[0]) + __builtin_popcountll(mx[1]) + __builtin_popcountll(mx[2]) + __builtin_popcountll(mx[3]) == 1;
+        const int budget = (qb - 2) - (pow2 ? mb - 1 : mb);             // floor(log2(Q / 2)) - ceil(log2 max); max = 0 counts as 1
+        return (float)std::max(0, budget);
     }
 
     // SIMD-slot encoding (the reference's encode scales by delta, src/fhe.cu:113-136, and its BatchEncoder is a passthrough,
@@ -420,7 +545,7 @@ public:
     }
 
     void encrypt(Ciphertext &ct, const Plaintext &pt, const PublicKey &pk) {               // src/fhe.cu:138-169
-        ensure_components(ct, 2);
+        ensure_components(ct, 2, 0);
         RNS_NTTEngine &E = *params_.rns_ntt;
         std::unique_ptr<Polynomial> u(new_polynomial()), e(new_polynomial());
         draw_ternary(*u);
@@ -433,34 +558,21 @@ public:
         draw_scaled_error(*e);
         E.add_rns(ct.components[1]->coeffs, ct.components[1]->coeffs, e->coeffs);            // + t*e2 (:166)
         device_synchronize();
-        ct.level = 0; ct.noise_budget = 0; ct.is_ntt_form = false;
+        ct.level = 0; ct.correction = 1; ct.noise_budget = 0; ct.is_ntt_form = false;
     }
 
-    // c0 + c1*s (+ c2*s^2), CRT to the centred integer through fhe_rns_from_rns, reduced mod t  (src/fhe.cu:171-185)
+    // c0 + c1*s (+ c2*s^2) on the engine of ct's level, CRT to the centred integer modulo Q_l through fhe_rns_from_rns, reduced mod t and divided
+    // by ct.correction  (src/fhe.cu:171-185).  The secret key of a level is the first L - level limbs of sk, used in place.
     void decrypt(Plaintext &pt, const Ciphertext &ct, const SecretKey &sk) {
-        const uint32_t n = params_.n, L = (uint32_t)params_.rns_moduli.size();
-        RNS_NTTEngine &E = *params_.rns_ntt;
-        std::unique_ptr<Polynomial> acc(new_polynomial()), sp(new_polynomial()), tmp(new_polynomial());
-        check(fhe_hip_memcpy_d2d(acc->coeffs, ct.components[0]->coeffs, acc->count() * sizeof(uint256_t)), "decrypt copy");
-        check(fhe_hip_memcpy_d2d(sp->coeffs, sk.sk->coeffs, sp->count() * sizeof(uint256_t)), "decrypt copy");
-        for (size_t k = 1; k < ct.components.size(); k++) {
-            E.multiply_rns(tmp->coeffs, ct.components[k]->coeffs, sp->coeffs);
-            E.add_rns(acc->coeffs, acc->coeffs, tmp->coeffs);
-            if (k + 1 < ct.components.size()) E.multiply_rns(sp->coeffs, sp->coeffs, sk.sk->coeffs);   // s^(k+1), in place
-        }
-        uint256_t *d_int = device_alloc(n);
-        E.from_rns(d_int, acc->coeffs);
-        std::vector<uint256_t> v(n);
-        device_synchronize(); copy_to_host(v.data(), d_int, n); device_free(d_int);
-        // Q and Q/2 as 256-bit integers
-        uint64_t Q[4] = {1, 0, 0, 0};
-        for (uint32_t l = 0; l < L; l++) mul_small(Q, params_.rns_moduli[l].limbs[0]);
-        uint64_t half[4]; for (int i = 0; i < 4; i++) half[i] = (Q[i] >> 1) | (i < 3 ? Q[i + 1] << 63 : 0);
-        const uint64_t t = params_.t, q_mod_t = mod_small(Q, t);
+        const uint32_t n = params_.n;
+        uint64_t Q[4], half[4];
+        const std::vector<uint256_t> v = decrypt_values(ct, sk, Q, half);
+        const uint64_t t = params_.t, q_mod_t = mod_small(Q, t), cinv = inv_mod_t(ct.correction % t);
         std::vector<long long> m(n);
         for (uint32_t i = 0; i < n; i++) {
             const uint64_t r = mod_small(v[i].limbs, t);
-            m[i] = (long long)(greater(v[i].limbs, half) ? (r + t - q_mod_t) % t : r);         // value - Q when above Q/2
+            const uint64_t c = greater(v[i].limbs, half) ? (r + t - q_mod_t) % t : r;           // value - Q when above Q/2
+            m[i] = (long long)(cinv == 1 ? c : mul_mod_t(c, cinv));
         }
         if (!pt.poly) pt.poly = new_polynomial();
         upload_signed(*pt.poly, m);
@@ -473,16 +585,94 @@ private:
     SchemeParams params_;
     std::mt19937_64 rng_{0x5EED0000ull};
     bool device_sampling_ = false;
+    std::vector<std::unique_ptr<RNS_NTTEngine>> level_engines_;   // index = level; entry 0 unused (params_.rns_ntt)
 
-    void plain_addsub(Ciphertext &result, const Ciphertext &ct, const Plaintext &pt, bool add_it) {
-        ensure_components(result, ct.components.size());
-        RNS_NTTEngine &E = *params_.rns_ntt;
+    // c0 + c1*s (+ c2*s^2) of a ciphertext at its level as integers in [0, Q_l); Q = Q_l and half = floor(Q_l / 2) as 256-bit integers
+    std::vector<uint256_t> decrypt_values(const Ciphertext &ct, const SecretKey &sk, uint64_t Q[4], uint64_t half[4]) {
+        const uint32_t n = params_.n, Ll = num_levels() - ct.level, lv = ct.level;
+        RNS_NTTEngine &E = engine(lv);
+        for (const Polynomial *c : ct.components)
+            if (c->num_limbs != Ll) throw std::runtime_error("FHEContext: ciphertext components do not have the limbs of its level");
+        std::unique_ptr<Polynomial> acc(new_polynomial(lv)), sp(new_polynomial(lv)), tmp(new_polynomial(lv));
+        check(fhe_hip_memcpy_d2d(acc->coeffs, ct.components[0]->coeffs, acc->count() * sizeof(uint256_t)), "decrypt copy");
+        check(fhe_hip_memcpy_d2d(sp->coeffs, sk.sk->coeffs, sp->count() * sizeof(uint256_t)), "decrypt copy");
+        for (size_t k = 1; k < ct.components.size(); k++) {
+            E.multiply_rns(tmp->coeffs, ct.components[k]->coeffs, sp->coeffs);
+            E.add_rns(acc->coeffs, acc->coeffs, tmp->coeffs);
+            if (k + 1 < ct.components.size()) E.multiply_rns(sp->coeffs, sp->coeffs, sk.sk->coeffs);   // s^(k+1), in place
+        }
+        uint256_t *d_int = device_alloc(n);
+        E.from_rns(d_int, acc->coeffs);
+        std::vector<uint256_t> v(n);
+        device_synchronize(); copy_to_host(v.data(), d_int, n); device_free(d_int);
+        Q[0] = 1; Q[1] = Q[2] = Q[3] = 0;
+        for (uint32_t l = 0; l < Ll; l++) mul_small(Q, params_.rns_moduli[l].limbs[0]);
+        for (int i = 0; i < 4; i++) half[i] = (Q[i] >> 1) | (i < 3 ? Q[i + 1] << 63 : 0);
+        return v;
+    }
+    static void same_level(const Ciphertext &a, const Ciphertext &b, const char *what) {
+        if (a.level != b.level) throw std::runtime_error(std::string(what) + ": operands at different levels (mod_switch_to_level first)");
+    }
+    uint64_t mul_mod_t(uint64_t a, uint64_t b) const { return (uint64_t)((unsigned __int128)(a % params_.t) * (b % params_.t) % params_.t); }
+    uint64_t inv_mod_t(uint64_t a) const {                           // extended Euclid: t need not be prime, a must be a unit
+        __int128 r0 = params_.t, r1 = a % params_.t, s0 = 0, s1 = 1;
+        while (r1) { const __int128 q = r0 / r1, r2 = r0 - q * r1, s2 = s0 - q * s1; r0 = r1; r1 = r2; s0 = s1; s1 = s2; }
+        if (r0 != 1) throw std::runtime_error("FHEContext: not invertible modulo t");
+        return (uint64_t)(s0 < 0 ? s0 + params_.t : s0);
+    }
+    // `ct` itself when its correction is 1, else `tmp` = a copy of ct times the centred representative of correction^-1 mod t (a constant
+    // polynomial through fhe_rns_ntt_multiply_bcast): the same plaintext with correction 1, at up to log2(t / 2) more bits of noise.
+    const Ciphertext &normalized(Ciphertext &tmp, const Ciphertext &ct) {
+        if (ct.correction == 1) return ct;
+        const uint64_t t = params_.t, c = inv_mod_t(ct.correction);
+        std::vector<long long> cpoly(params_.n, 0);
+        cpoly[0] = c > t / 2 ? -(long long)(t - c) : (long long)c;
+        std::unique_ptr<Polynomial> cp(new_polynomial());            // [L][n]: its first L - level limbs are the level's constant
+        upload_signed(*cp, cpoly);
+        ensure_components(tmp, ct.components.size(), ct.level);
+        for (size_t i = 0; i < ct.components.size(); i++)
+            engine(ct.level).multiply_rns_bcast(tmp.components[i]->coeffs, ct.components[i]->coeffs, cp->coeffs, 1);
+        device_synchronize();
+        tmp.level = ct.level; tmp.correction = 1; tmp.noise_budget = ct.noise_budget; tmp.is_ntt_form = false;
+        return tmp;
+    }
+    static void free_components(Ciphertext &ct) { for (Polynomial *p : ct.components) delete p; ct.components.clear(); }
+    // rows j*K + k (j < L', k < K') of a top-level key-switch key, imported on the engine of `level` through the same device pointers
+    fhe_relin_keys_t *import_sliced(const PublicKey *const *rows, size_t num_rows, uint32_t decomp_bits, uint32_t level) {
+        const uint32_t L = num_levels(), Ll = L - level;
+        if (num_rows % L) throw std::runtime_error("FHEContext: key set of the wrong size");
+        const uint32_t K = (uint32_t)(num_rows / L);
+        uint32_t Kl = 0;
+        check(fhe_relin_num_digits(engine(level).handle(), decomp_bits, &Kl), "FHEContext: digits of a level");
+        if (Kl > K) throw std::runtime_error("FHEContext: a level needs more digits than the key set has");
+        std::vector<const void *> kb, ka;
+        for (uint32_t j = 0; j < Ll; j++)
+            for (uint32_t k = 0; k < Kl; k++) { const PublicKey *r = rows[(size_t)j * K + k]; kb.push_back(r->pk0->coeffs); ka.push_back(r->pk1->coeffs); }
+        fhe_relin_keys_t *h = nullptr;
+        check(fhe_relin_keys_create(engine(level).handle(), &h, decomp_bits, kb.data(), ka.data(), (uint32_t)kb.size()), "FHEContext: key import at a level");
+        return h;
+    }
+    static void sub4(uint64_t r[4], const uint64_t a[4], const uint64_t b[4]) {
+        unsigned __int128 br = 0;
+        for (int i = 0; i < 4; i++) { const unsigned __int128 d = (unsigned __int128)a[i] - b[i] - br; r[i] = (uint64_t)d; br = (d >> 64) & 1; }
+    }
+    static int bit_length(const uint64_t a[4]) {
+        for (int i = 3; i >= 0; i--) if (a[i]) return 64 * i + 64 - __builtin_clzll(a[i]);
+        return 0;
+    }
+
+    void plain_addsub(Ciphertext &result, const Ciphertext &ct_in, const Plaintext &pt, bool add_it) {
+        Ciphertext norm;
+        const Ciphertext &ct = normalized(norm, ct_in);
+        ensure_components(result, ct.components.size(), ct.level);
+        RNS_NTTEngine &E = engine(ct.level);
         if (add_it) E.add_rns(result.components[0]->coeffs, ct.components[0]->coeffs, pt.poly->coeffs);
         else E.sub_rns(result.components[0]->coeffs, ct.components[0]->coeffs, pt.poly->coeffs);
         for (size_t i = 1; i < ct.components.size(); i++)
             if (result.components[i] != ct.components[i])
                 check(fhe_hip_memcpy_d2d(result.components[i]->coeffs, ct.components[i]->coeffs, ct.components[i]->count() * sizeof(uint256_t)), "plain op copy");
-        result.noise_budget = ct.noise_budget; result.level = ct.level;
+        result.noise_budget = ct.noise_budget; result.level = ct.level; result.correction = 1;
+        if (!norm.components.empty()) { device_synchronize(); free_components(norm); }
     }
 
     // ---- where keygen / encrypt get their random polynomials: host generator (default) or the device samplers --------------
@@ -587,10 +777,13 @@ private:
     void copy_ciphertext(Ciphertext &dst, const Ciphertext &src) {
         for (size_t i = 0; i < src.components.size(); i++)
             check(fhe_hip_memcpy_d2d(dst.components[i]->coeffs, src.components[i]->coeffs, src.components[i]->count() * sizeof(uint256_t)), "ciphertext copy");
-        dst.noise_budget = src.noise_budget; dst.level = src.level;
+        dst.noise_budget = src.noise_budget; dst.level = src.level; dst.correction = src.correction;
     }
-    void ensure_components(Ciphertext &ct, size_t num) {
-        while (ct.components.size() < num) ct.components.push_back(new_polynomial());   // the reference `new`s and never frees (src/fhe.cu:202-205)
+    // at least `num` components of the limbs of `level` (a component left over from another level is replaced)
+    void ensure_components(Ciphertext &ct, size_t num, uint32_t level) {
+        const uint32_t limbs = num_levels() - level;
+        for (Polynomial *&p : ct.components) if (p->num_limbs != limbs) { delete p; p = new_polynomial(level); }
+        while (ct.components.size() < num) ct.components.push_back(new_polynomial(level));   // the reference `new`s and never frees (src/fhe.cu:202-205)
     }
 };
 

@@ -71,6 +71,12 @@ public:
     }
     // RNSContext::mod_switch_rns (include/rns.cuh:44): drop the last prime with rounding; d_out is [batch][L-1][n]
     void rescale_drop_last(uint256_t *d_out, const uint256_t *d_in, uint32_t batch = 1) { check(fhe_rns_rescale_drop_last(h_, d_out, d_in, batch), "rescale_drop_last"); }
+    // FHEContext::mod_switch_to_next (include/fhe.cuh:109): BGV modulus switch of up to three ciphertext components in one launch; d_in / d_out are
+    // HOST arrays of num_components device pointers, [batch][L][n] in and [batch][L-1][n] out; the plaintext keeps the factor q_last^-1 mod t
+    void mod_switch_drop_last(uint64_t t, uint256_t *const *d_out, const uint256_t *const *d_in, uint32_t num_components, uint32_t batch = 1) {
+        check(fhe_ct_mod_switch_drop_last(h_, t, reinterpret_cast<void *const *>(d_out), reinterpret_cast<const void *const *>(d_in), num_components, batch),
+              "mod_switch_drop_last");
+    }
     void pointwise_rns(uint256_t *d_result, const uint256_t *d_a, const uint256_t *d_b, uint32_t batch = 1) {
         check(fhe_rns_ntt_pointwise(h_, d_result, d_a, d_b, batch), "pointwise_rns");
     }

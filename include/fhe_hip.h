@@ -156,7 +156,7 @@ int fhe_rns_ntt_create(fhe_rns_ntt_t **out, uint32_t n, const uint64_t (*moduli)
 /* RNSContext::RNSContext(primes) (include/rns.cuh:27-66, src/rns.cu:6-29): an RNS base WITHOUT a ring.  The handle is an engine of
  * degree n = 1: its buffers [batch][L][1] are exactly RNSContext's interleaved [count][num_primes] layout (src/rns.cu:103-104),
  * `batch` is the reference's `count`, and every container-level entry point (fhe_rns_to_rns, fhe_rns_from_rns, fhe_rns_poly_add /
- * sub, fhe_rns_ntt_pointwise, fhe_rns_mul_mont_literal, fhe_rns_rescale_drop_last, fhe_rns_fast_base_convert, the samplers) works on
+ * sub, fhe_rns_ntt_pointwise, fhe_rns_mul_mont_literal, fhe_rns_rescale_drop_last, fhe_ct_mod_switch_drop_last, fhe_rns_fast_base_convert, the samplers) works on
  * it.  Primes: pairwise distinct odd primes < 2^255 (no congruence condition). */
 int fhe_rns_base_create(fhe_rns_ntt_t **out, const uint64_t (*primes)[4], uint32_t num_primes);
 int fhe_rns_ntt_destroy(fhe_rns_ntt_t *h);                                    /* src/ntt.cu:147-156 */
@@ -200,11 +200,29 @@ int fhe_rns_to_rns(fhe_rns_ntt_t *h, void *d_rns, const void *d_values, uint32_t
  * reconstruction into [0, Q), Q = prod q_l.  Needs Q < 2^255 (FHE_ERR_UNSUPPORTED otherwise). */
 int fhe_rns_from_rns(fhe_rns_ntt_t *h, void *d_values, const void *d_rns, uint32_t batch);
 
-/* RNSContext::mod_switch_rns / rns_mod_switch_kernel (include/rns.cuh:44,128-136), FHEContext::mod_switch_to_next
- * (include/fhe.cuh:109), poly_mod_switch_kernel (include/polynomial.cuh:96-103) -- all undefined in the reference:
- * drop the last prime with rounding, d_out[b][l][x] = round(C / q_last) mod q_l for l < L-1.  d_in is [batch][L][n],
- * d_out is [batch][L-1][n] (the layout of an engine built on the first L-1 primes).  Needs L >= 2. */
+/* RNSContext::mod_switch_rns / rns_mod_switch_kernel (include/rns.cuh:44,128-136), poly_mod_switch_kernel
+ * (include/polynomial.cuh:96-103) -- undefined in the reference: drop the last prime with rounding,
+ * d_out[b][l][x] = round(C / q_last) mod q_l for l < L-1.  d_in is [batch][L][n], d_out is [batch][L-1][n] (the layout of an
+ * engine built on the first L-1 primes).  Needs L >= 2.  The rounding term is arbitrary modulo a plaintext modulus t: this is NOT the
+ * modulus switch of a BGV ciphertext (FHEContext::mod_switch_to_next), which is fhe_ct_mod_switch_drop_last below. */
 int fhe_rns_rescale_drop_last(fhe_rns_ntt_t *h, void *d_out, const void *d_in, uint32_t batch);
+
+/* FHEContext::mod_switch_to_next / mod_switch_to_level (include/fhe.cuh:109-110, declared only): BGV modulus switch.  Drops the last
+ * prime of the basis from up to three ciphertext components in ONE launch, keeping the plaintext modulo t up to the known factor
+ * q_last^-1 mod t.  d_in and d_out are HOST arrays of num_components (1..3) device pointers; inputs are [batch][L][n], outputs
+ * [batch][L-1][n] (the layout of an engine on the first L-1 primes).  For every component, b and x, with r = in[b][L-1][x]:
+ *     u   = (-r * t^-1) mod q_last,   u_c = u if u <= (q_last - 1) / 2, else u - q_last       (q_last is odd: no tie)
+ *     out[b][l][x] = (in[b][l][x] + t * u_c) * q_last^-1 mod q_l,  canonical,  l < L-1
+ * i.e. C' = (C + t * u_c) / q_last exactly: the added term is 0 modulo t, cancels C modulo q_last and is at most t * q_last / 2 in
+ * magnitude.  If (c0, c1) decrypts to m + t*e under s modulo Q, the outputs decrypt modulo Q / q_last to q_last^-1 * (m + t*e) + small,
+ * which is q_last^-1 * m modulo t: the caller keeps that factor (Ciphertext::correction in include/fhe/fhe.hpp).
+ * FHE_ERR_INVALID_ARG, with nothing launched, unless L >= 2, t >= 2, t != 0 (mod q_last), num_components in 1..3, every pointer is
+ * non-null and 16-byte aligned, and the outputs are distinct from each other and from every input.  No condition on Q = prod q_l: no
+ * CRT is involved (two 250-bit primes work).  The constant tables depend on t: they are built and uploaded on the first call with a
+ * given t and kept, one set per t, until fhe_rns_ntt_destroy.  After that first call a call with the same t allocates nothing and can
+ * be captured into a hipGraph. */
+int fhe_ct_mod_switch_drop_last(fhe_rns_ntt_t *h, uint64_t t, void *const *d_out, const void *const *d_in, uint32_t num_components,
+                                uint32_t batch);
 
 /* Fast base conversion (Bajard et al.) -- RNSContext::base_extend / fast_base_conversion_kernel (include/rns.cuh:47-48,
  * 116-125, undefined in the reference): d_out[b][j][x] = sum_i [x_i (Q/q_i)^-1]_{q_i} (Q/q_i) mod p_j for the primes p_j of
