@@ -111,6 +111,10 @@ def lib():
         "fhe_ct_apply_galois_hoisted": ([vp, vp, u32, vp, vp, vp, u32], ci),
         "fhe_rns_ntt_reserve_hoist": ([vp, u32, u32], ci),
         "fhe_rns_ntt_hoist_bytes": ([vp, ctypes.POINTER(ctypes.c_uint64)], ci),
+        "fhe_linear_transform_create": ([vp, P(vp), u32, P(u32), P(vp), P(vp), u32], ci),
+        "fhe_linear_transform_destroy": ([vp], ci),
+        "fhe_linear_transform_reserve": ([vp, vp, u32], ci),
+        "fhe_ct_linear_transform_hoisted": ([vp, vp, vp, vp, vp, vp, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -467,6 +471,26 @@ class RnsNttEngine:
         _check(lib().fhe_rns_ntt_hoist_bytes(self.h, ctypes.byref(out)))
         return out.value
 
+    def linear_transform_create(self, decomp_bits, galois_elts, keys, plains):
+        """sum_t plains[t] * rotation by galois_elts[t]: keys[t] the Galois keys of that element (None with element 1: no key switch),
+        plains[t] one [L][n] polynomial in coefficient form on the device.  The key sets are referenced and must outlive the object."""
+        G = len(galois_elts); assert len(keys) == G and len(plains) == G
+        m = max(G, 1)
+        elts = (ctypes.c_uint32 * m)(*galois_elts)
+        pk = (ctypes.c_void_p * m)(*[None if k is None else k.h for k in keys])
+        pp = (ctypes.c_void_p * m)(*[None if p is None else _ptr(p) for p in plains])
+        out = ctypes.c_void_p()
+        _check(lib().fhe_linear_transform_create(self.h, ctypes.byref(out), decomp_bits, elts, pk, pp, G))
+        return LinearTransform(out, list(keys))
+
+    def linear_transform_reserve(self, lt, batch):
+        """Pre-size what linear_transform_hoisted (and the hoist before it) needs for `batch` ciphertexts: reserve, then hoist."""
+        _check(lib().fhe_linear_transform_reserve(self.h, lt.h, batch))
+
+    def linear_transform_hoisted(self, lt, d_out0, d_out1, d_c0, d_c1=None, batch=1):
+        """(d_out0, d_out1) = sum_t p_t * rotation_t of the hoisted ciphertext; d_c1 is needed only when lt has a keyless term."""
+        _check(lib().fhe_ct_linear_transform_hoisted(self.h, lt.h, _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), None if d_c1 is None else _ptr(d_c1), batch))
+
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))
 
@@ -490,6 +514,23 @@ class RelinKeys:
     def close(self):
         if self.h:
             lib().fhe_relin_keys_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LinearTransform:
+    """A hoisted linear transform built on an engine (plaintexts owned by the library; holds its key sets alive)."""
+
+    def __init__(self, h, keys=()):
+        self.h, self.keys = h, keys
+
+    def close(self):
+        if self.h:
+            lib().fhe_linear_transform_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

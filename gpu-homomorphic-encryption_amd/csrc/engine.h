@@ -96,6 +96,9 @@ struct fhe_rns_ntt {
     // Hoisted rotations: the transformed digit polynomials of the c1 of the last fhe_ct_hoist, a fourth allocation that no other entry point touches
     void *d_hoist = nullptr; size_t hoist_bytes = 0;
     struct { bool valid = false, fused = false; uint32_t w = 0, K = 0, batch = 0; } hoist;   // what d_hoist holds: digit width, digits per limb, ciphertexts
+    // Hoisted linear transform: a fifth allocation.  Fused path: c0^ (and c1^) of the call in the hoist layout; composed path: the two components
+    // of one weighted rotation before they are added to the outputs
+    void *d_lin = nullptr; size_t lin_bytes = 0;
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
@@ -193,6 +196,7 @@ bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys);
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone);
 LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
 bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys);   // hoisted rotations on the LDS kernels of hoist.hip.h (else the composed path)
+bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys); // hoisted linear transform on the LDS kernels of hoist_lincomb.hip.h (else the composed path)
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
 WsNeed need_multiply(const fhe_rns_ntt *h, uint32_t batch);

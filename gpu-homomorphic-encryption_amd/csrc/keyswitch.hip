@@ -512,6 +512,140 @@ extern "C" int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_key
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Hoisted linear transform: out = sum_t p_t * hoisted_rotation(ct, g_t) from one kept decomposition   (semantics: include/fhe_hip.h)
+// ------------------------------------------------------------------------------------------------------
+// Fused path (plan_fused_lincomb, every keyed term with packed tables; kernels: hoist_lincomb.hip.h): the plaintexts are kept transformed and
+// packed like key rows, the terms sit in a device table, and a call is two launches whatever G is: c0 (and c1, where a term has no key)
+// forward into d_lin in the hoist layout, then ntt_hoist_lincomb_kernel.  Composed path: the plaintexts are kept as given, and every term is
+// fhe_ct_apply_galois_hoisted into d_lin (the first term: into the outputs), fhe_rns_ntt_multiply_bcast and fhe_rns_poly_add.
+struct fhe_linear_transform {
+    fhe_rns_ntt *owner = nullptr;
+    uint32_t decomp_bits = 0, K = 0;
+    bool fused = false, keyless = false;            // fused: the LDS kernels run it; keyless: some term has no key (the call needs c1)
+    std::vector<uint32_t> g;
+    std::vector<const fhe_relin_keys *> gk;         // referenced, not owned
+    void *d_plain = nullptr;                        // fused: [G][L][n] residues, transformed and packed; composed: [G][L][n] containers, coefficient form
+    void *d_terms = nullptr;                        // fused: LincombTerm[G]
+};
+extern "C" int fhe_linear_transform_destroy(fhe_linear_transform_t *lt) {
+    if (lt) {
+        for (void *p : {lt->d_plain, lt->d_terms}) if (p) (void)hipFree(p);
+        delete lt;
+    }
+    return FHE_OK;
+}
+extern "C" int fhe_linear_transform_create(fhe_rns_ntt_t *h, fhe_linear_transform_t **out, uint32_t decomp_bits, const uint32_t *galois_elts,
+                                           const fhe_relin_keys_t *const *gks, const void *const *d_plain, uint32_t num_terms) {
+    if (!h || !out || !galois_elts || !gks || !d_plain) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: null argument");
+    int rc = check_hoist_call(h, decomp_bits, 1, "linear_transform_create"); if (rc) return rc;
+    if (num_terms < 1 || num_terms > FHE_LINEAR_TRANSFORM_MAX_TERMS) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: num_terms must be in [1, FHE_LINEAR_TRANSFORM_MAX_TERMS]");
+    const uint32_t K = relin_digits(h, decomp_bits);
+    bool fused = plan_fused_lincomb(h, keys_get_packed(h, decomp_bits, K)), keyless = false;
+    for (uint32_t t = 0; t < num_terms; t++) {
+        if ((rc = check_galois_element(h, galois_elts[t], "linear_transform_create"))) return rc;
+        if (!d_plain[t]) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: null plaintext pointer");
+        if ((rc = check_aligned({d_plain[t]}, "linear_transform_create"))) return rc;
+        const fhe_relin_keys *gk = gks[t];
+        if (!gk) {
+            if (galois_elts[t] != 1) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: a term without a key set must have Galois element 1");
+            keyless = true;
+            continue;
+        }
+        if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: keys were imported for a different engine");
+        if (gk->decomp_bits != decomp_bits) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: a key set's decomp_bits differ from the transform's");
+        fused = fused && gk->d_pkb;
+        if (!gk->d_pkb && !gk->d_kb) return fail(FHE_ERR_INVALID_ARG, "linear_transform_create: a key set has no tables");
+    }
+    fhe_linear_transform *lt = new (std::nothrow) fhe_linear_transform();
+    if (!lt) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
+    lt->owner = h; lt->decomp_bits = decomp_bits; lt->K = K; lt->fused = fused; lt->keyless = keyless;
+    lt->g.assign(galois_elts, galois_elts + num_terms); lt->gk.assign(gks, gks + num_terms);
+    const size_t S = (size_t)h->L * h->n * 32;
+    void *d_copy = nullptr;                          // the plaintexts as containers
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_copy, S * num_terms));
+        for (uint32_t t = 0; t < num_terms; t++) HIP_TRY(hipMemcpyAsync((char *)d_copy + t * S, d_plain[t], S, hipMemcpyDeviceToDevice, h->stream));
+        if (!fused) { lt->d_plain = d_copy; d_copy = nullptr; return post_launch(h->stream, "linear_transform_create copy"); }
+        if (int r = do_forward(h, d_copy, num_terms)) return r;
+        std::vector<fhe_dev::LincombTerm> terms(num_terms);
+        const size_t eb = residue_bytes(h);
+        HIP_TRY(hipMalloc(&lt->d_plain, (size_t)num_terms * h->L * h->n * eb));
+        HIP_TRY(hipMalloc(&lt->d_terms, num_terms * sizeof(fhe_dev::LincombTerm)));
+        if (int r = with_word_field(h, [&](auto f) {
+                using F = decltype(f);
+                hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid((size_t)num_terms * h->L * h->n)), dim3(256), 0, h->stream, (typename F::E *)lt->d_plain,
+                                   (const typename F::V16 *)d_copy, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, num_terms);
+                return post_launch(h->stream, "pack_keys_kernel (plaintexts)");
+            })) return r;
+        for (uint32_t t = 0; t < num_terms; t++)
+            terms[t] = {gks[t] ? gks[t]->d_pkb : nullptr, gks[t] ? gks[t]->d_pka : nullptr, (const char *)lt->d_plain + (size_t)t * h->L * h->n * eb, galois_elts[t], 0};
+        HIP_TRY(hipMemcpyAsync(lt->d_terms, terms.data(), num_terms * sizeof(fhe_dev::LincombTerm), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));     // `terms` leaves scope; hipFree of the copy waits anyway
+        return FHE_OK;
+    };
+    rc = body();
+    if (d_copy) (void)hipFree(d_copy);
+    if (rc) { fhe_linear_transform_destroy(lt); return rc; }
+    *out = lt;
+    return FHE_OK;
+}
+// bytes of d_lin for `batch` ciphertexts: c0^ and c1^ as residues, or two container components
+static size_t lincomb_scratch(const fhe_rns_ntt *h, const fhe_linear_transform *lt, uint32_t batch) {
+    return (size_t)batch * h->L * h->n * (lt->fused ? (lt->keyless ? 2 : 1) * residue_bytes(h) : 2 * 32);
+}
+static int ensure_lincomb(fhe_rns_ntt *h, const fhe_linear_transform *lt, uint32_t batch) {
+    int rc = ensure_hoist(h, batch, lt->K, hoist_fused(h, lt->decomp_bits, lt->K)); if (rc) return rc;
+    if (!lt->fused && (rc = ensure_need(h, need_multiply(h, batch)))) return rc;
+    return grow_ws(h, &h->d_lin, &h->lin_bytes, lincomb_scratch(h, lt, batch));
+}
+extern "C" int fhe_linear_transform_reserve(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, uint32_t batch) {
+    if (!h || !lt) return fail(FHE_ERR_INVALID_ARG, "linear_transform_reserve: null argument");
+    int rc = check_hoist_call(h, lt->decomp_bits, batch, "linear_transform_reserve"); if (rc) return rc;
+    if (lt->owner != h) return fail(FHE_ERR_INVALID_ARG, "linear_transform_reserve: the transform was created for a different engine");
+    return ensure_lincomb(h, lt, batch);
+}
+extern "C" int fhe_ct_linear_transform_hoisted(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, void *d_out0, void *d_out1, const void *d_c0,
+                                               const void *d_c1, uint32_t batch) {
+    int rc = check_call(h, batch, "ct_linear_transform_hoisted"); if (rc) return rc;
+    if (!lt || !d_out0 || !d_out1 || !d_c0) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: null argument");
+    if (lt->owner != h) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: the transform was created for a different engine");
+    if (lt->keyless && !d_c1) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: a term without a key set needs c1");
+    if ((rc = check_aligned({d_out0, d_out1, d_c0, d_c1}, "ct_linear_transform_hoisted"))) return rc;
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: outputs must be distinct");
+    for (const void *i : {d_c0, d_c1}) if (d_out0 == i || d_out1 == i) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: outputs must not alias inputs");
+    if (!h->hoist.valid) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: no fhe_ct_hoist on this engine yet (or its workspace was re-sized since)");
+    if (batch != h->hoist.batch) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: batch differs from the hoisted one");
+    if (lt->decomp_bits != h->hoist.w) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: the transform's decomp_bits differ from the hoisted ones");
+    if (lt->fused && !h->hoist.fused) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: the kept decomposition is not in the layout this transform reads");
+    if ((rc = check_inputs(h, {d_c0}, batch)) || (lt->keyless && (rc = check_inputs(h, {d_c1}, batch)))) return rc;
+    if ((rc = ensure_lincomb(h, lt, batch))) return rc;                       // (no-op after fhe_linear_transform_reserve)
+    if (!h->hoist.valid) return fail(FHE_ERR_INVALID_ARG, "ct_linear_transform_hoisted: the hoist workspace had to grow, which drops the kept decomposition: hoist again");
+    const uint32_t polys = batch * h->L, G = (uint32_t)lt->g.size();
+    if (lt->fused) {
+        fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST_FWD, {}, polys);
+        A.r0 = h->d_lin; A.a0 = d_c0; A.a1 = lt->keyless ? d_c1 : nullptr; A.out_compact = true;
+        if ((rc = lds_launch(h, A, "ntt_hoist_fwd_kernel"))) return rc;
+        fhe_dev::LdsArgs B = lds_args(h, fhe_dev::LDS_HOIST_LINCOMB, {}, polys);
+        B.r0 = d_out0; B.r1 = d_out1; B.c2 = h->d_hoist; B.add0 = h->d_lin; B.in_compact = B.add_compact = true;
+        B.add1 = lt->keyless ? (const char *)h->d_lin + (size_t)polys * h->n * residue_bytes(h) : nullptr;
+        B.terms = lt->d_terms; B.num_terms = G; B.K = lt->K;
+        return lds_launch(h, B, "ntt_hoist_lincomb_kernel");
+    }
+    const size_t S = (size_t)h->L * h->n * 32;
+    char *s0 = (char *)h->d_lin, *s1 = s0 + (size_t)batch * S;
+    for (uint32_t t = 0; t < G; t++) {
+        void *t0 = t ? (void *)s0 : d_out0, *t1 = t ? (void *)s1 : d_out1;    // the first term goes straight to the outputs
+        const void *pt = (const char *)lt->d_plain + (size_t)t * S;
+        if (lt->gk[t]) {
+            if ((rc = fhe_ct_apply_galois_hoisted(h, lt->gk[t], lt->g[t], t0, t1, d_c0, batch))) return rc;
+            if ((rc = fhe_rns_ntt_multiply_bcast(h, t0, t0, pt, batch)) || (rc = fhe_rns_ntt_multiply_bcast(h, t1, t1, pt, batch))) return rc;
+        } else if ((rc = fhe_rns_ntt_multiply_bcast(h, t0, d_c0, pt, batch)) || (rc = fhe_rns_ntt_multiply_bcast(h, t1, d_c1, pt, batch))) return rc;
+        if (t && ((rc = fhe_rns_poly_add(h, d_out0, d_out0, s0, batch)) || (rc = fhe_rns_poly_add(h, d_out1, d_out1, s1, batch)))) return rc;
+    }
+    return FHE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
 // blind-rotation inner loop
 // ------------------------------------------------------------------------------------------------------
 static int monomial_compact(fhe_rns_ntt *h, void *out, const void *in, const uint32_t *shifts, size_t count) {   // (X^shift - 1) * p on compact polynomials

@@ -4,6 +4,7 @@
 #include <type_traits>
 #include "lds_launch.h"
 #include "hoist.hip.h"
+#include "hoist_lincomb.hip.h"
 #include "ntt_lds.hip.h"
 #include "ntt_lds_small.hip.h"
 
@@ -81,6 +82,22 @@ static bool launch(const LdsArgs &A) {
                 if (!in || !ac || out || !A.add0) return false;
                 hipLaunchKernelGGL((ntt_hoist_apply_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const E *)A.c2, (const char *)A.add0,
                                    (const E *)A.kb, (const E *)A.ka, limbs, A.L, A.K, A.galois);
+            }
+            return true;
+        }
+        return false;
+    }
+    // Hoisted linear transform: containers in, canonical hoist-layout residues out; those, the kept polynomials and the term table in, containers out
+    if (A.op == LDS_HOIST_FWD || A.op == LDS_HOIST_LINCOMB) {
+        if constexpr (lds_hoist_lincomb(EB, LOGN)) {
+            if (A.op == LDS_HOIST_FWD) {
+                if (in || !out || !A.a0) return false;
+                hipLaunchKernelGGL((ntt_hoist_fwd_kernel<F, LOGN, 2>), dim3(A.polys, A.a1 ? 2 : 1), block, 0, A.stream, (E *)A.r0, (const char *)A.a0, (const char *)A.a1, limbs, A.L);
+            } else {
+                constexpr bool split = lds_hoist_lincomb_split(EB);
+                if (!in || !ac || out || !A.add0 || !A.terms || !A.num_terms) return false;
+                hipLaunchKernelGGL((ntt_hoist_lincomb_kernel<F, LOGN, 2, split>), dim3(A.polys * (split ? 2 : 1)), block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const E *)A.c2,
+                                   (const E *)A.add0, (const E *)A.add1, (const LincombTerm *)A.terms, A.num_terms, limbs, A.L, A.K);
             }
             return true;
         }

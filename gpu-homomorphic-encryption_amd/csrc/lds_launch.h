@@ -8,11 +8,13 @@
 namespace fhe_dev {
 
 // One list per enum: the enumerators and the names that the "no LDS kernel for ..." error prints come out of the same lines.
-// LDS_HOIST / LDS_HOIST_APPLY: hoisted rotations (hoist.hip.h), one form each.
+// LDS_HOIST / LDS_HOIST_APPLY: hoisted rotations (hoist.hip.h), one form each.  LDS_HOIST_FWD / LDS_HOIST_LINCOMB: the two launches of the
+// hoisted linear transform (hoist_lincomb.hip.h), one form each.
 // The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
 // over the top stages and the sub-transforms of the 2^top blocks
 #define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
     X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") X(LDS_HOIST, "hoist") X(LDS_HOIST_APPLY, "hoisted rotation") \
+    X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") \
     X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
 #define LDS_ENUMERATOR(id, name) id,
 #define LDS_NAME_CASE(id, name) case id: return name;
@@ -59,6 +61,11 @@ constexpr bool lds_coop4_multiply(int elem_bytes, int log_n) { return elem_bytes
 // hoisted rotations (ntt_hoist_kernel / ntt_hoist_apply_kernel: two and three live arrays): every LDS-resident size but N = 2^15, whose
 // 1024-thread workgroups cap a thread at 128 VGPRs (the apply kernel parks 84 bytes per lane in scratch there): that size takes the composed path
 constexpr bool lds_hoist(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
+// hoisted linear transform (ntt_hoist_fwd_kernel / ntt_hoist_lincomb_kernel): 4-byte residues one workgroup per (ciphertext, limb) with five live
+// arrays, 8-byte residues one per (ciphertext, limb, output component) with three; wherever the hoist kernels exist and the instance keeps
+// the budget of its field (tests/test_linear_transform.py compiles every LDS-resident instance and pins it)
+constexpr bool lds_hoist_lincomb(int elem_bytes, int log_n) { return lds_hoist(elem_bytes, log_n); }
+constexpr bool lds_hoist_lincomb_split(int elem_bytes) { return elem_bytes == 8; }
 
 // The kernel form of LDS_MULTIPLY / LDS_CT_MULTIPLY / LDS_KEYSWITCH / LDS_EXTPROD (the other ops have one form each).
 #define LDS_FORMS(X) /* LDS_MULTIPLY, LDS_CT_MULTIPLY */ \
@@ -78,6 +85,14 @@ constexpr bool lds_hoist(int elem_bytes, int log_n) { (void)elem_bytes; return l
     X(LDS_PART_PAIRS, "per-digit-pair parts")    /* one workgroup per digit PAIR (paired transforms) + a combining launch, ws = partial sums */
 enum LdsForm { LDS_FORMS(LDS_ENUMERATOR) };
 constexpr const char *lds_form_name(int form) { switch (form) { LDS_FORMS(LDS_NAME_CASE) } return "unknown"; }
+
+// One term of a hoisted linear transform (device table owned by the fhe_linear_transform object, read by ntt_hoist_lincomb_kernel).
+// kb == nullptr: no key switch, the term is p * (c0, c1)
+struct LincombTerm {
+    const void *kb, *ka;                 // packed key tables of the term's key set (pack_keys_kernel)
+    const void *pt;                      // the term's plaintext, transformed and packed like one key row: [L][n] residues
+    uint32_t g, _pad;                    // Galois element (1 for a keyless term)
+};
 
 // One launch request.  The host fills the members that are operands of ITS op, by name (lds_args of engine.h sets the common ones from the
 // engine and the plan); everything else keeps its default.
@@ -104,6 +119,11 @@ struct LdsArgs {
     // LDS_HOIST: r0 = the hoist workspace, c2 = c1 (compact).  LDS_HOIST_APPLY: (r0, r1) = (add0, 0) + the kept polynomials of c2 = the hoist
     // workspace, read at pi_galois, times kb / ka; add0 = sigma_galois(c0), compact
     uint32_t galois = 0;
+    // LDS_HOIST_FWD: r0 = [a1 ? 2 : 1][polys][n] residues = the forward transforms of a0 (and a1), containers in, canonical, hoist layout.
+    // LDS_HOIST_LINCOMB: (r0, r1) = sum over the num_terms entries of `terms` (device array of LincombTerm) of plaintext * rotation; c2 = the
+    // hoist workspace, add0 / add1 = the two halves LDS_HOIST_FWD wrote (add1 only where a term has no key); polys = ciphertexts x limbs
+    const void *terms = nullptr;
+    uint32_t num_terms = 0;
     const uint32_t *shifts = nullptr;    // LDS_EXTPROD: device array of per-ciphertext monomial exponents
     uint32_t K = 0, w = 0;
     uint32_t b_polys = 0;                // LDS_MULTIPLY: polynomials behind b0 (0 = as many as the batch; L = one RNS polynomial broadcast over the batch)

@@ -191,6 +191,9 @@ bool plan_fused_ct_relin(const fhe_rns_ntt *h, bool packed_keys) {
 bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys) {
     return plan_fused_ct_relin(h, packed_keys) && fhe_dev::lds_hoist((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_hoist;
 }
+bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys) {
+    return plan_fused_hoist(h, packed_keys) && fhe_dev::lds_hoist_lincomb((int)residue_bytes(h), (int)h->log_n);
+}
 // Key switch of `polys` limb polynomials with K digits (KsSource: engine.h).  alone: no other chunk of the call runs beside it (the
 // few-ciphertext parts take d_ws).
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone) {

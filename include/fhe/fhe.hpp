@@ -447,6 +447,44 @@ public:
         device_synchronize();
         return out;
     }
+    // Hoisted linear transform (plaintext matrix-vector product by diagonals): sum_s diagonals[s] * rotate_rows(ct, steps[s]) from ONE hoist and
+    // ONE fhe_ct_linear_transform_hoisted at the ciphertext's level.  Step 0 is the keyless term; every other step needs its own key in the
+    // set, else it throws (as rotate_rows_hoisted).  A level-l plaintext is the prefix of its buffer (as multiply_plain); correction and level
+    // are carried from ct.  The ring elements are those of rotate_rows_hoisted + multiply_plain + add.
+    Ciphertext linear_transform_hoisted(const Ciphertext &ct, const std::vector<int> &steps, const std::vector<const Plaintext *> &diagonals,
+                                        const GaloisKeys &gal_keys) {
+        if (ct.components.size() != 2) throw std::runtime_error("FHEContext::linear_transform_hoisted: 2-component ciphertext expected (relinearize first)");
+        if (steps.empty() || steps.size() != diagonals.size()) throw std::runtime_error("FHEContext::linear_transform_hoisted: one diagonal per step, at least one");
+        const uint32_t half = params_.n / 2;
+        std::vector<uint32_t> elts;
+        for (int st : steps) {
+            const uint32_t r = (uint32_t)(((long long)st % half + half) % half), g = galois_element((int)r);
+            if (r && galois_key_index(gal_keys, g) == (size_t)-1) throw std::runtime_error("FHEContext::linear_transform_hoisted: no Galois key for a step");
+            elts.push_back(r ? g : 1);
+        }
+        const std::vector<fhe_relin_keys_t *> &keys = galois_keys_at(gal_keys, ct.level);
+        fhe_rns_ntt_t *h = engine(ct.level).handle();
+        std::vector<const fhe_relin_keys_t *> gks;
+        std::vector<const void *> plains;
+        for (size_t s = 0; s < elts.size(); s++) {
+            if (!diagonals[s] || !diagonals[s]->poly) throw std::runtime_error("FHEContext::linear_transform_hoisted: null diagonal");
+            gks.push_back(elts[s] == 1 ? nullptr : keys[galois_key_index(gal_keys, elts[s])]);
+            plains.push_back(diagonals[s]->poly->coeffs);
+        }
+        fhe_linear_transform_t *lt = nullptr;
+        check(fhe_linear_transform_create(h, &lt, gal_keys.decomp_bits, elts.data(), gks.data(), plains.data(), (uint32_t)elts.size()),
+              "FHEContext::linear_transform_hoisted: create");
+        Ciphertext out;
+        ensure_components(out, 2, ct.level);
+        int rc = fhe_ct_hoist(h, gal_keys.decomp_bits, ct.components[1]->coeffs, 1);
+        if (!rc) rc = fhe_ct_linear_transform_hoisted(h, lt, out.components[0]->coeffs, out.components[1]->coeffs, ct.components[0]->coeffs,
+                                                      ct.components[1]->coeffs, 1);
+        if (!rc) device_synchronize();
+        fhe_linear_transform_destroy(lt);
+        check(rc, "FHEContext::linear_transform_hoisted");
+        out.noise_budget = ct.noise_budget; out.level = ct.level; out.correction = ct.correction; out.is_ntt_form = false;
+        return out;
+    }
     // FHEContext::rotate_columns (include/fhe.cuh:114-115): swaps the two rows (g = 2n - 1).
     void rotate_columns(Ciphertext &result, const Ciphertext &ct, const GaloisKeys &gal_keys) { apply_galois(result, ct, column_element(), gal_keys); }
 

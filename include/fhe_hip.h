@@ -318,6 +318,45 @@ int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk, ui
 int fhe_rns_ntt_reserve_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t batch);
 int fhe_rns_ntt_hoist_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes);
 
+/* ---- hoisted linear transform: a sum of plaintext-weighted rotations in one call ("double hoisting") -------------------------------
+ * The plaintext matrix-vector product over slots (Halevi and Shoup, diagonal method):  out = sum_t p_t * rotate(ct, step_t), t = 0 .. G-1.
+ * Term t has a Galois element g_t (odd, below 2n), the Galois keys of g_t (imported with fhe_relin_keys_create on h for decomp_bits) and a
+ * plaintext p_t: ONE [L][n] polynomial in coefficient form, canonical, shared by the whole batch.  gks[t] == NULL is allowed only with
+ * galois_elts[t] == 1 and means "no key switch": the term is p_t * (c0, c1).  Elements may repeat.  From the decomposition kept by the last
+ * fhe_ct_hoist on h (same decomp_bits, same batch), with D_{j,k}(c1) and the level order of the hoisted rotation above:
+ *     out0 = sum_t p_t * ( sigma_{g_t}(c0) + sum_{j,k} sigma_{g_t}(D_{j,k}(c1)) * b_{t,j,k} )
+ *     out1 = sum_t p_t * (                   sum_{j,k} sigma_{g_t}(D_{j,k}(c1)) * a_{t,j,k} )      in Z_{q_i}[x]/(x^n + 1), every limb i, canonical
+ * and for a keyless term  p_t * c0  and  p_t * c1.  All arithmetic is exact modular arithmetic: the result is bit-identical to
+ *     sum_t fhe_rns_ntt_multiply_bcast( fhe_ct_apply_galois_hoisted(gk_t, g_t), p_t )   folded with fhe_rns_poly_add
+ * on every path, and depends only on the inputs: never on the batch, the kernel path or the order of the terms.  It decrypts under s to
+ * sum_t p_t * sigma_{g_t}(m); in slots, sum_t d_t (.) rot(v, step_t) with the row ordering of the Galois section above when p_t encodes d_t.
+ *
+ * On the LDS-resident word-sized sizes up to N = 2^14 whose key sets have packed tables a call is two launches whatever G is: c0 (and c1,
+ * if a term has no key) forward-transformed once, then one kernel that runs every term's permuted multiply-accumulate, multiplies by the
+ * transformed plaintext and adds in the NTT domain: two inverse transforms and two container stores per ciphertext limb in all, instead
+ * of 6 G of each for the composition.  Elsewhere (full-width class, N >= 2^15, FHE_HIP_NO_FUSED_HOIST=1) the library runs that composition
+ * itself, per term, through a scratch pair of its own.
+ *
+ * fhe_linear_transform_create copies the plaintexts (and, for the fused path, transforms them once and keeps them in the order the kernel
+ * reads, as key rows are kept); the key sets are referenced, not copied, and must outlive the object.  FHE_ERR_INVALID_ARG, with nothing
+ * launched and *out untouched: a null argument, plaintext or (with g != 1) key set; num_terms == 0 or above
+ * FHE_LINEAR_TRANSFORM_MAX_TERMS; an even element or one >= 2n; keys of another engine or of another decomp_bits; a misaligned plaintext. */
+#define FHE_LINEAR_TRANSFORM_MAX_TERMS 4096u
+typedef struct fhe_linear_transform fhe_linear_transform_t;
+int fhe_linear_transform_create(fhe_rns_ntt_t *h, fhe_linear_transform_t **out, uint32_t decomp_bits, const uint32_t *galois_elts,
+                                const fhe_relin_keys_t *const *gks, const void *const *d_plain, uint32_t num_terms);
+int fhe_linear_transform_destroy(fhe_linear_transform_t *lt);
+/* Sizes whatever fhe_ct_linear_transform_hoisted (and the fhe_ct_hoist before it) needs for `batch` ciphertexts, so that neither allocates
+ * afterwards (hipGraph capture).  The call's scratch is a fifth allocation of the engine, counted by fhe_rns_ntt_workspace_bytes; like
+ * fhe_rns_ntt_reserve_hoist, growing the hoist workspace drops a kept decomposition, so reserve before hoisting. */
+int fhe_linear_transform_reserve(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, uint32_t batch);
+/* (d_out0, d_out1) = the sum above, [batch][L][n] each.  d_c0 is the c0 that belongs to the hoisted c1; d_c1 is required (and must be the
+ * hoisted c1) iff lt has a keyless term, else may be NULL.  Inputs are read only.  FHE_ERR_INVALID_ARG, with nothing launched and nothing
+ * written: a null handle, object or output; an object created for another engine; no valid fhe_ct_hoist on h, or a batch or decomp_bits
+ * that differs from the hoist's; d_c1 missing when a term has no key; a misaligned pointer; outputs aliasing each other or an input. */
+int fhe_ct_linear_transform_hoisted(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, void *d_out0, void *d_out1,
+                                    const void *d_c0, const void *d_c1, uint32_t batch);
+
 /* ---- blind-rotation inner loop ------------------------------------------------------ */
 /* FHEContext::blind_rotate is only declared in the reference (include/fhe.cuh:139; pipeline prose README.md:146-159).  Its
  * inner loop is  acc <- acc + ExternalProduct((X^a - 1) * acc, RGSW(s)),  and the external product of an RLWE pair (d0, d1)
