@@ -115,6 +115,10 @@ def lib():
         "fhe_linear_transform_destroy": ([vp], ci),
         "fhe_linear_transform_reserve": ([vp, vp, u32], ci),
         "fhe_ct_linear_transform_hoisted": ([vp, vp, vp, vp, vp, vp, u32], ci),
+        "fhe_public_key_create": ([vp, P(vp), vp, vp], ci),
+        "fhe_public_key_destroy": ([vp], ci),
+        "fhe_ct_encrypt_reserve": ([vp, ctypes.c_double, u32], ci),
+        "fhe_ct_encrypt": ([vp, vp, u64, ctypes.c_double, P(u64), vp, vp, vp, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -491,6 +495,22 @@ class RnsNttEngine:
         """(d_out0, d_out1) = sum_t p_t * rotation_t of the hoisted ciphertext; d_c1 is needed only when lt has a keyless term."""
         _check(lib().fhe_ct_linear_transform_hoisted(self.h, lt.h, _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), None if d_c1 is None else _ptr(d_c1), batch))
 
+    def import_public_key(self, d_pk0, d_pk1):
+        """(pk0, pk1): one [L][n] polynomial each, coefficient form, on the device.  The library keeps its own copies."""
+        out = ctypes.c_void_p()
+        _check(lib().fhe_public_key_create(self.h, ctypes.byref(out), _ptr(d_pk0), _ptr(d_pk1)))
+        return PublicKey(out)
+
+    def encrypt_reserve(self, sigma, batch):
+        """Pre-size what encrypt needs for this sigma and up to `batch` ciphertexts: afterwards a call allocates nothing."""
+        _check(lib().fhe_ct_encrypt_reserve(self.h, sigma, batch))
+
+    def encrypt(self, pk, t, sigma, seeds, d_out0, d_out1, d_m=None, batch=1):
+        """(d_out0, d_out1) = (pk0 * u + t e0 + m, pk1 * u + t e1) for `batch` ciphertexts; seeds = (u, e0, e1); d_m None encrypts zero."""
+        assert len(seeds) == 3
+        sd = (ctypes.c_uint64 * 3)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
+        _check(lib().fhe_ct_encrypt(self.h, pk.h, t, sigma, sd, _ptr(d_out0), _ptr(d_out1), None if d_m is None else _ptr(d_m), batch))
+
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))
 
@@ -531,6 +551,23 @@ class LinearTransform:
     def close(self):
         if self.h:
             lib().fhe_linear_transform_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PublicKey:
+    """A public key imported into an engine (copies owned by the library)."""
+
+    def __init__(self, h):
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib().fhe_public_key_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

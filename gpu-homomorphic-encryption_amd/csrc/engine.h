@@ -4,6 +4,7 @@
 //   core.hip        last error, device / memory entry points, host number theory, timers
 //   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
 //   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
+//   encrypt.hip     public keys, public-key encryption (composed path: sampling.hip.h and the entry points of transforms.hip; fused: encrypt.hip.h)
 //   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve (= the merge of need_* below)
 //   transforms.hip  wide and LDS launchers, the planners, forward / inverse / element-wise / multiply / tensor product (ntt_wide.hip.h,
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
@@ -68,9 +69,10 @@ struct EngineEnv {
     int force_width = 0;
     bool no_wide_lazy = false, no_wide_tiles = false;
     bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
-         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false,
+         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false,
          split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
     uint32_t small_batch_polys = 256, coop_polys = 64, split_pairs_polys = 128, overlap_chunks = 4;
+    uint32_t encrypt_per_ct_batch = 256; // fhe_ct_encrypt of at least this many ciphertexts runs one workgroup per ciphertext (plan_encrypt)
     int ct_form_force = 0;
 };
 
@@ -99,6 +101,8 @@ struct fhe_rns_ntt {
     // Hoisted linear transform: a fifth allocation.  Fused path: c0^ (and c1^) of the call in the hoist layout; composed path: the two components
     // of one weighted rotation before they are added to the outputs
     void *d_lin = nullptr; size_t lin_bytes = 0;
+    // fhe_ct_encrypt, composed path: u of the call as containers, a sixth allocation
+    void *d_enc = nullptr; size_t enc_bytes = 0;
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
@@ -197,6 +201,8 @@ LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource 
 LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
 bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys);   // hoisted rotations on the LDS kernels of hoist.hip.h (else the composed path)
 bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys); // hoisted linear transform on the LDS kernels of hoist_lincomb.hip.h (else the composed path)
+bool plan_fused_encrypt(const fhe_rns_ntt *h);                   // public-key encryption on the LDS kernel of encrypt.hip.h (else the composed path)
+bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch);  // ... on the one-workgroup-per-ciphertext grid (else one per (ciphertext, limb))
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
 WsNeed need_multiply(const fhe_rns_ntt *h, uint32_t batch);
@@ -218,6 +224,9 @@ int do_inverse(fhe_rns_ntt *h, void *d_data, uint32_t batch);
 template <int OP> int do_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint32_t batch, const char *what);   // OP 0: product, 1: add, 2: sub
 int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0, const void *b1, uint32_t batch);
 int compact_poly(fhe_rns_ntt *h, void *out, const void *in, size_t containers);   // containers -> compact polynomials (word-sized classes)
+
+// ---- sampling.hip ---------------------------------------------------------------------------------------------------------------
+int ensure_cdt(fhe_rns_ntt *h, double sigma, const char *what);   // h->d_cdt / cdt_len = the cumulative table of sigma (uploaded when sigma changes)
 
 // ---- rns.hip --------------------------------------------------------------------------------------------------------------------
 int ensure_crt(fhe_rns_ntt *h);          // CrtLimb[L] (and Q, where it fits 255 bits) on first use

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "lds_launch.h"
+#include "encrypt.hip.h"
 #include "hoist.hip.h"
 #include "hoist_lincomb.hip.h"
 #include "ntt_lds.hip.h"
@@ -99,6 +100,16 @@ static bool launch(const LdsArgs &A) {
                 hipLaunchKernelGGL((ntt_hoist_lincomb_kernel<F, LOGN, 2, split>), dim3(A.polys * (split ? 2 : 1)), block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const E *)A.c2,
                                    (const E *)A.add0, (const E *)A.add1, (const LincombTerm *)A.terms, A.num_terms, limbs, A.L, A.K);
             }
+            return true;
+        }
+        return false;
+    }
+    // Public-key encryption: m in containers (or none), containers out, nothing else
+    if (A.op == LDS_ENCRYPT) {
+        if constexpr (lds_encrypt(EB, LOGN)) {
+            if (in || out || !A.r0 || !A.r1 || !A.kb || !A.ka || !A.cdt || !A.cdt_len || A.cdt_len > ENCRYPT_MAX_CDT || A.polys % A.L) return false;
+            hipLaunchKernelGGL((ntt_encrypt_kernel<F, LOGN, 2>), dim3(A.per_ct ? A.polys / A.L : A.polys), block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const char *)A.a0,
+                               (const E *)A.kb, (const E *)A.ka, A.cdt, A.cdt_len, A.seeds[0], A.seeds[1], A.seeds[2], A.t, limbs, A.L, A.per_ct ? 1u : 0u);
             return true;
         }
         return false;

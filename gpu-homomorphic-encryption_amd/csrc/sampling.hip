@@ -65,22 +65,26 @@ extern "C" int fhe_rns_sample_ternary(fhe_rns_ntt_t *h, void *d_out, double prob
                        (const fhe_dev::CrtLimb *)h->d_crt, h->L, h->log_n, seed, thr, (const uint64_t *)nullptr, 0u, count);
     return post_launch(h->stream, "sample_small_kernel<ternary>");
 }
+// h->d_cdt = the cumulative table of sigma; built and uploaded when sigma differs from the last call's (synchronises and allocates then, never otherwise)
+int ensure_cdt(fhe_rns_ntt *h, double sigma, const char *what) {
+    if (h->cdt_sigma == sigma && h->d_cdt) return FHE_OK;
+    uint32_t len = 0;
+    int rc = fhe_gaussian_cdt(sigma, nullptr, 0, &len); if (rc) return rc;
+    if (!small_fits(h, len)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": 12 sigma does not fit below the smallest modulus");
+    std::vector<uint64_t> t(len);
+    if ((rc = fhe_gaussian_cdt(sigma, t.data(), len, &len))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));                 // an earlier launch may still read the old table
+    if (h->d_cdt) { HIP_TRY(hipFree(h->d_cdt)); h->d_cdt = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_cdt, len * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(h->d_cdt, t.data(), len * sizeof(uint64_t), hipMemcpyHostToDevice));
+    h->cdt_sigma = sigma; h->cdt_len = len;
+    return FHE_OK;
+}
 extern "C" int fhe_rns_sample_gaussian(fhe_rns_ntt_t *h, void *d_out, double sigma, uint64_t seed, uint32_t batch) {
     int rc = check_call(h, batch, "rns_sample_gaussian"); if (rc) return rc;
     if (!d_out) return fail(FHE_ERR_INVALID_ARG, "rns_sample_gaussian: null output");
     if ((rc = check_aligned({d_out}, "rns_sample_gaussian"))) return rc;
-    if (h->cdt_sigma != sigma || !h->d_cdt) {
-        uint32_t len = 0;
-        if ((rc = fhe_gaussian_cdt(sigma, nullptr, 0, &len))) return rc;
-        if (!small_fits(h, len)) return fail(FHE_ERR_INVALID_ARG, "rns_sample_gaussian: 12 sigma does not fit below the smallest modulus");
-        std::vector<uint64_t> t(len);
-        if ((rc = fhe_gaussian_cdt(sigma, t.data(), len, &len))) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));                 // an earlier launch may still read the old table
-        if (h->d_cdt) { HIP_TRY(hipFree(h->d_cdt)); h->d_cdt = nullptr; }
-        HIP_TRY(hipMalloc((void **)&h->d_cdt, len * sizeof(uint64_t)));
-        HIP_TRY(hipMemcpy(h->d_cdt, t.data(), len * sizeof(uint64_t), hipMemcpyHostToDevice));
-        h->cdt_sigma = sigma; h->cdt_len = len;
-    }
+    if ((rc = ensure_cdt(h, sigma, "rns_sample_gaussian"))) return rc;
     if ((rc = ensure_crt(h))) return rc;
     const size_t count = (size_t)batch * h->n;
     hipLaunchKernelGGL(fhe_dev::sample_small_kernel<1>, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out,

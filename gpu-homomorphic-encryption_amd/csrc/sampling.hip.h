@@ -13,22 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctr_rand.hip.h"                  // the counter-based generator: sm64, ctr_rand, the DRAW_* numbers
 #include "ntt256.hip.h"
 
 namespace fhe_dev {
-
-// ---- counter-based generator ------------------------------------------------------------------------------------------
-__device__ __host__ inline uint64_t sm64(uint64_t z) {          // SplitMix64 output function
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// 64 random bits for (seed, element index, draw number)
-__device__ __host__ inline uint64_t ctr_rand(uint64_t seed, uint64_t index, uint64_t draw) {
-    return sm64(sm64(seed ^ (index * 0xD1342543DE82EF95ull)) + draw);
-}
-enum : uint64_t { DRAW_TERNARY = 0, DRAW_CDT = 1, DRAW_SIGN = 2, DRAW_UNIFORM = 16 };
 
 __device__ __forceinline__ u256 u256_small(uint64_t v) { u256 r; r.l[0] = v; r.l[1] = r.l[2] = r.l[3] = 0; return r; }
 __device__ __forceinline__ bool lt256(const u256 &a, const u256 &b) {   // a < b

@@ -194,6 +194,13 @@ bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys) {
 bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys) {
     return plan_fused_hoist(h, packed_keys) && fhe_dev::lds_hoist_lincomb((int)residue_bytes(h), (int)h->log_n);
 }
+// Public-key encryption as the one launch of encrypt.hip.h: every LDS-resident word-sized size whose instance has the kernel
+bool plan_fused_encrypt(const fhe_rns_ntt *h) {
+    return h->width != FHE_WIDTH_256 && !h->sub_top && h->log_n >= 11 && fhe_dev::lds_encrypt((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_encrypt;
+}
+// ... one workgroup per ciphertext (draws once, loops over the limbs) from FHE_HIP_ENCRYPT_PER_CT_BATCH ciphertexts, below that one per
+// (ciphertext, limb): L times the workgroups for a device that the ciphertexts alone do not fill.  Same kernel, same bits.
+bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch) { return h->L > 1 && batch >= h->env.encrypt_per_ct_batch; }
 // Key switch of `polys` limb polynomials with K digits (KsSource: engine.h).  alone: no other chunk of the call runs beside it (the
 // few-ciphertext parts take d_ws).
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone) {

@@ -22,7 +22,12 @@ struct SecurityParams {          // include/fhe.cuh:15-21
     uint32_t hamming_weight;
 };
 
-struct PublicKey { Polynomial *pk0; Polynomial *pk1; };      // include/fhe.cuh:41-44
+struct PublicKey {                                            // include/fhe.cuh:41-44
+    Polynomial *pk0; Polynomial *pk1;
+    // engine-side copy for FHEContext::encrypt_fused (fhe_public_key_create), built on first use; shared, so that copies of the struct stay valid
+    mutable std::shared_ptr<fhe_public_key_t> imported;
+    mutable const void *imported_for = nullptr;
+};
 struct SecretKey { Polynomial *sk; };                         // include/fhe.cuh:47-49
 struct RelinKeys {                                            // include/fhe.cuh:52-55
     std::vector<PublicKey *> rlk_keys;     // level j*K + k: (b, a) with b = -a*s + e + g*s^2, g = 2^(k*w) in limb j, 0 elsewhere
@@ -596,6 +601,23 @@ public:
         draw_scaled_error(*e);
         E.add_rns(ct.components[1]->coeffs, ct.components[1]->coeffs, e->coeffs);            // + t*e2 (:166)
         device_synchronize();
+        ct.level = 0; ct.correction = 1; ct.noise_budget = 0; ct.is_ntt_form = false;
+    }
+
+    // The same ciphertext distribution as encrypt in ONE engine call (fhe_ct_encrypt): u, e1, e2 are drawn inside the kernel from three seeds of
+    // the context generator with security.sigma, the public key is imported once and kept.  Level 0.  encrypt itself stays as the reference has it.
+    void encrypt_fused(Ciphertext &ct, const Plaintext &pt, const PublicKey &pk) {
+        ensure_components(ct, 2, 0);
+        fhe_rns_ntt_t *h = params_.rns_ntt->handle();
+        if (!pk.imported || pk.imported_for != params_.rns_ntt) {
+            fhe_public_key_t *k = nullptr;
+            check(fhe_public_key_create(h, &k, pk.pk0->coeffs, pk.pk1->coeffs), "encrypt_fused: public key import");
+            pk.imported.reset(k, [](fhe_public_key_t *p) { fhe_public_key_destroy(p); });
+            pk.imported_for = params_.rns_ntt;
+        }
+        const uint64_t seeds[3] = {rng_(), rng_(), rng_()};
+        check(fhe_ct_encrypt(h, pk.imported.get(), params_.t, (double)params_.security.sigma, seeds, ct.components[0]->coeffs, ct.components[1]->coeffs,
+                             pt.poly->coeffs, 1), "encrypt_fused");
         ct.level = 0; ct.correction = 1; ct.noise_budget = 0; ct.is_ntt_form = false;
     }
 

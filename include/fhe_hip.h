@@ -224,6 +224,42 @@ int fhe_rns_rescale_drop_last(fhe_rns_ntt_t *h, void *d_out, const void *d_in, u
 int fhe_ct_mod_switch_drop_last(fhe_rns_ntt_t *h, uint64_t t, void *const *d_out, const void *const *d_in, uint32_t num_components,
                                 uint32_t batch);
 
+/* ---- public-key encryption as one call -------------------------------------------------------------------------------------------
+ * FHEContext::encrypt (src/fhe.cu:138-169; batched by examples/batch_processing.cu): c = (pk0 * u + t e0 + m, pk1 * u + t e1) with u
+ * ternary and e0, e1 discrete Gaussians.  For ciphertext b, limb i and coefficient x, with sampler index g = b * n + x:
+ *     u  = ternary(seeds[0], g), P(u != 0) = 1/2           exactly what fhe_rns_sample_ternary(h, ., 0.5, seeds[0], batch) writes
+ *     e0 = gaussian(sigma, seeds[1], g),  e1 = gaussian(sigma, seeds[2], g)       exactly fhe_rns_sample_gaussian (table of fhe_gaussian_cdt)
+ *     out0[b][i] = pk0_i (*) u_b + [t e0_b]_{q_i} + m[b][i],     out1[b][i] = pk1_i (*) u_b + [t e1_b]_{q_i}
+ * in Z_{q_i}[x] / (x^n + 1), canonical; a negative small integer -k embeds as q_i - (t k mod q_i) (0 stays 0).  All arithmetic is exact, so
+ * the result is bit-identical on every path to fhe_rns_sample_* + fhe_rns_ntt_multiply_bcast + a multiplication by the constant t +
+ * fhe_rns_poly_add, and depends only on (pk, t, sigma, seeds, m, b): never on the kernel form or the launch shape.  Because the sampler
+ * index is b * n + x, ciphertext b of a batch call differs from a batch-1 call with the same seeds unless b = 0: give every call its own seeds.
+ *
+ * On the LDS-resident word-sized sizes up to N = 2^14 (and sigma <= 85, so that the cumulative table fits the kernel's staging buffer) a
+ * call is ONE launch: a workgroup draws u, e0, e1 in registers, runs one forward transform of u, multiplies by the kept transforms of pk0
+ * and pk1 and finishes with two inverse transforms: 3 S bytes of HBM traffic (m in, c0 and c1 out), no workspace.  Elsewhere (full-width
+ * class, N >= 2^15, sizes below 2^11, sigma > 85, FHE_HIP_NO_FUSED_ENCRYPT=1) the library runs the composition itself through scratch of
+ * its own (u as containers), which fhe_rns_ntt_workspace_bytes counts.
+ *
+ * fhe_public_key_create: d_pk0, d_pk1 are [L][n] containers in coefficient form, canonical.  They are copied (the sources are not read
+ * again; their addresses are remembered only for the aliasing check of fhe_ct_encrypt, so an output placed where a freed source was is
+ * rejected), and for the one-launch path transformed once and kept in the order the kernel reads, as key rows are kept.  FHE_ERR_INVALID_ARG with
+ * *out untouched: a null or misaligned argument.  fhe_public_key_destroy(NULL) is FHE_OK. */
+typedef struct fhe_public_key fhe_public_key_t;
+int fhe_public_key_create(fhe_rns_ntt_t *h, fhe_public_key_t **out, const void *d_pk0, const void *d_pk1);
+int fhe_public_key_destroy(fhe_public_key_t *pk);
+/* Sizes everything a later fhe_ct_encrypt with this sigma and up to `batch` ciphertexts needs: the upload of the cumulative table (one
+ * table is kept per engine, shared with fhe_rns_sample_gaussian: a call with another sigma replaces it) and the composed path's scratch.
+ * After it fhe_ct_encrypt allocates nothing, fhe_rns_ntt_workspace_bytes does not change across the call, and the call can be captured
+ * into a hipGraph (re-capture after the table was replaced). */
+int fhe_ct_encrypt_reserve(fhe_rns_ntt_t *h, double sigma, uint32_t batch);
+/* (d_out0, d_out1) = the ciphertexts above, [batch][L][n] each; d_m is [batch][L][n] canonical containers (the encoded plaintext in every
+ * limb), NULL encrypts zero; seeds = {u, e0, e1}.  FHE_ERR_INVALID_ARG, with nothing launched and nothing written: a null handle, key,
+ * seeds or output; a misaligned pointer; outputs aliasing each other, d_m or the key's sources; a key of another engine; batch == 0;
+ * t < 2; a sigma that fhe_gaussian_cdt rejects; ceil(12 sigma) >= the smallest modulus. */
+int fhe_ct_encrypt(fhe_rns_ntt_t *h, const fhe_public_key_t *pk, uint64_t t, double sigma, const uint64_t seeds[3], void *d_out0, void *d_out1,
+                   const void *d_m, uint32_t batch);
+
 /* Fast base conversion (Bajard et al.) -- RNSContext::base_extend / fast_base_conversion_kernel (include/rns.cuh:47-48,
  * 116-125, undefined in the reference): d_out[b][j][x] = sum_i [x_i (Q/q_i)^-1]_{q_i} (Q/q_i) mod p_j for the primes p_j of
  * `target` (an engine of the same degree).  The value is that of X + alpha*Q, 0 <= alpha < L (inexact by design of the
