@@ -199,20 +199,26 @@ def _case(oracle, n, moduli, batch, with_m=True):
     return _cache[key]
 
 
-def _run(pkg, n, moduli, pk0, pk1, m, batch, seeds=SEEDS, reserve=False, twice=True):
+def _run(pkg, n, moduli, pk0, pk1, m, batch, seeds=SEEDS, reserve=False, twice=True, t=T, sigma=SIGMA, ws=None):
+    """ws: a list that receives workspace_bytes() of the fresh engine before the first call (after the key import and the reserve) and after
+    the last one: equal on the one-launch path, apart by at least the composed path's u (batch L n containers) otherwise."""
     e = pkg.RnsNttEngine(n, moduli)
     src = pkg.DeviceBuffer.from_numpy(pk0), pkg.DeviceBuffer.from_numpy(pk1)   # kept alive: an output at a source's address is rejected as aliasing
     pk = e.import_public_key(*src)
     if reserve:
-        e.encrypt_reserve(SIGMA, batch)
+        e.encrypt_reserve(sigma, batch)
     nbytes = batch * len(moduli) * n * 32
     dm = None if m is None else pkg.DeviceBuffer.from_numpy(m)
     o0, o1 = pkg.DeviceBuffer(nbytes), pkg.DeviceBuffer(nbytes)
     shape = (batch, len(moduli), n, 4)
+    if ws is not None:
+        ws.append(e.workspace_bytes())
     for _ in range(2 if twice else 1):
         memcheck.poison(pkg, o0); memcheck.poison(pkg, o1)
-        e.encrypt(pk, T, SIGMA, seeds, o0, o1, dm, batch)
+        e.encrypt(pk, t, sigma, seeds, o0, o1, dm, batch)
         got = o0.download(shape), o1.download(shape)
+    if ws is not None:
+        ws.append(e.workspace_bytes())
     if m is not None:
         assert np.array_equal(dm.download(shape), m)
     return got
