@@ -384,7 +384,10 @@ int fhe_linear_transform_create(fhe_rns_ntt_t *h, fhe_linear_transform_t **out, 
 int fhe_linear_transform_destroy(fhe_linear_transform_t *lt);
 /* Sizes whatever fhe_ct_linear_transform_hoisted (and the fhe_ct_hoist before it) needs for `batch` ciphertexts, so that neither allocates
  * afterwards (hipGraph capture).  The call's scratch is a fifth allocation of the engine, counted by fhe_rns_ntt_workspace_bytes; like
- * fhe_rns_ntt_reserve_hoist, growing the hoist workspace drops a kept decomposition, so reserve before hoisting. */
+ * fhe_rns_ntt_reserve_hoist, growing the hoist workspace drops a kept decomposition, so reserve before hoisting.  On the fused path
+ * (where fhe_rns_ntt_hoist_bytes is in residue form and every keyed term has packed tables) a fresh engine then holds
+ * batch * L * n * sizeof(residue) bytes for the compact c1 that fhe_ct_hoist reads plus the scratch of once (twice with a keyless term)
+ * that size; on the composed path the scratch is 2 * batch * L * n * 32 bytes beside what fhe_ct_apply_galois_hoisted needs. */
 int fhe_linear_transform_reserve(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, uint32_t batch);
 /* (d_out0, d_out1) = the sum above, [batch][L][n] each.  d_c0 is the c0 that belongs to the hoisted c1; d_c1 is required (and must be the
  * hoisted c1) iff lt has a keyless term, else may be NULL.  Inputs are read only.  FHE_ERR_INVALID_ARG, with nothing launched and nothing
