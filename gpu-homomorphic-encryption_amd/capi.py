@@ -119,6 +119,10 @@ def lib():
         "fhe_public_key_destroy": ([vp], ci),
         "fhe_ct_encrypt_reserve": ([vp, ctypes.c_double, u32], ci),
         "fhe_ct_encrypt": ([vp, vp, u64, ctypes.c_double, P(u64), vp, vp, vp, u32], ci),
+        "fhe_secret_key_create": ([vp, P(vp), vp], ci),
+        "fhe_secret_key_destroy": ([vp], ci),
+        "fhe_ct_decrypt_reserve": ([vp, u64, u32, u32], ci),
+        "fhe_ct_decrypt": ([vp, vp, u64, u64, vp, vp, P(vp), u32, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -511,6 +515,22 @@ class RnsNttEngine:
         sd = (ctypes.c_uint64 * 3)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
         _check(lib().fhe_ct_encrypt(self.h, pk.h, t, sigma, sd, _ptr(d_out0), _ptr(d_out1), None if d_m is None else _ptr(d_m), batch))
 
+    def import_secret_key(self, d_s):
+        """s: one [L][n] polynomial, coefficient form, on the device.  The library keeps its own copy (and s * s)."""
+        out = ctypes.c_void_p()
+        _check(lib().fhe_secret_key_create(self.h, ctypes.byref(out), _ptr(d_s)))
+        return SecretKey(out)
+
+    def decrypt_reserve(self, t, num_components, batch):
+        """Pre-size what decrypt needs for up to `num_components` components and `batch` ciphertexts: afterwards a call allocates nothing."""
+        _check(lib().fhe_ct_decrypt_reserve(self.h, t, num_components, batch))
+
+    def decrypt(self, sk, t, scale, d_m, d_noise_bits, components, batch=1):
+        """d_m[b][x] = ((v mod t) * scale) mod t (uint64) and d_noise_bits[b] = bit_length(max |v|) (uint32, or None), v the centred value of
+        c0 + c1 s (+ c2 s^2) for the 2 or 3 device buffers in `components`."""
+        comps = (ctypes.c_void_p * len(components))(*[_ptr(c) for c in components])
+        _check(lib().fhe_ct_decrypt(self.h, sk.h, t, scale, _ptr(d_m), None if d_noise_bits is None else _ptr(d_noise_bits), comps, len(components), batch))
+
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))
 
@@ -568,6 +588,23 @@ class PublicKey:
     def close(self):
         if self.h:
             lib().fhe_public_key_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SecretKey:
+    """A secret key imported into an engine (copies owned by the library)."""
+
+    def __init__(self, h):
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib().fhe_secret_key_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -5,6 +5,7 @@
 //   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
 //   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
 //   encrypt.hip     public keys, public-key encryption (composed path: sampling.hip.h and the entry points of transforms.hip; fused: encrypt.hip.h)
+//   decrypt.hip     secret keys, secret-key decryption (fused: decrypt.hip.h; composed path: the entry points of transforms.hip; the CRT kernels of decrypt.hip.h either way)
 //   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve (= the merge of need_* below)
 //   transforms.hip  wide and LDS launchers, the planners, forward / inverse / element-wise / multiply / tensor product (ntt_wide.hip.h,
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
@@ -69,7 +70,7 @@ struct EngineEnv {
     int force_width = 0;
     bool no_wide_lazy = false, no_wide_tiles = false;
     bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
-         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false,
+         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false, no_fused_decrypt = false,
          split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
     uint32_t small_batch_polys = 256, coop_polys = 64, split_pairs_polys = 128, overlap_chunks = 4;
     uint32_t encrypt_per_ct_batch = 256; // fhe_ct_encrypt of at least this many ciphertexts runs one workgroup per ciphertext (plan_encrypt)
@@ -103,6 +104,9 @@ struct fhe_rns_ntt {
     void *d_lin = nullptr; size_t lin_bytes = 0;
     // fhe_ct_encrypt, composed path: u of the call as containers, a sixth allocation
     void *d_enc = nullptr; size_t enc_bytes = 0;
+    // fhe_ct_decrypt, a seventh allocation.  Fused path: the residues of c0 + c1 s + c2 s^2 as compact polynomials between the two launches;
+    // composed path: c1 s (and c2 s^2) as containers
+    void *d_dec = nullptr; size_t dec_bytes = 0;
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
@@ -202,6 +206,7 @@ LdsPlan plan_extprod(const fhe_rns_ntt *h, size_t polys, uint32_t K);
 bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys);   // hoisted rotations on the LDS kernels of hoist.hip.h (else the composed path)
 bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys); // hoisted linear transform on the LDS kernels of hoist_lincomb.hip.h (else the composed path)
 bool plan_fused_encrypt(const fhe_rns_ntt *h);                   // public-key encryption on the LDS kernel of encrypt.hip.h (else the composed path)
+bool plan_fused_decrypt(const fhe_rns_ntt *h);                   // secret-key decryption on the LDS kernel of decrypt.hip.h (else the composed path)
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch);  // ... on the one-workgroup-per-ciphertext grid (else one per (ciphertext, limb))
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
@@ -230,5 +235,6 @@ int ensure_cdt(fhe_rns_ntt *h, double sigma, const char *what);   // h->d_cdt / 
 
 // ---- rns.hip --------------------------------------------------------------------------------------------------------------------
 int ensure_crt(fhe_rns_ntt *h);          // CrtLimb[L] (and Q, where it fits 255 bits) on first use
+int ensure_from_rns_word(fhe_rns_ntt *h);   // word-sized classes: d_from_rns_w_minv / d_from_rns_w_M on first use (from_rns, decrypt)
 
 #pragma GCC visibility pop

@@ -15,6 +15,7 @@ void destroy_impl(fhe_rns_ntt *h) {
     if (h->d_hoist) (void)hipFree(h->d_hoist);
     if (h->d_lin) (void)hipFree(h->d_lin);
     if (h->d_enc) (void)hipFree(h->d_enc);
+    if (h->d_dec) (void)hipFree(h->d_dec);
     if (h->d_cdt) (void)hipFree(h->d_cdt);
     if (h->d_flag) (void)hipFree(h->d_flag);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
@@ -202,6 +203,7 @@ static EngineEnv read_env() {
     e.no_fused_galois = set("FHE_HIP_NO_FUSED_GALOIS");                                // fhe_ct_apply_galois on the composed path everywhere (cross-check)
     e.no_fused_hoist = set("FHE_HIP_NO_FUSED_HOIST");                                  // hoisted rotations on the composed path everywhere (cross-check); key import is unchanged
     e.no_fused_encrypt = set("FHE_HIP_NO_FUSED_ENCRYPT");                              // fhe_ct_encrypt on the composed path everywhere (cross-check); read when a public key is imported too
+    e.no_fused_decrypt = set("FHE_HIP_NO_FUSED_DECRYPT");                              // fhe_ct_decrypt on the composed path everywhere (cross-check); read when a secret key is imported too
     e.encrypt_per_ct_batch = num("FHE_HIP_ENCRYPT_PER_CT_BATCH", 256, 0, LONG_MAX); // fused fhe_ct_encrypt of at least this many ciphertexts: one workgroup per ciphertext, sampling once (0 = always)
     e.split_keyswitch = set("FHE_HIP_SPLIT_KEYSWITCH");
     e.small_batch_polys = num("FHE_HIP_SMALL_BATCH_POLYS", 256, 0, LONG_MAX);       // fused multiply of at most this many limb polynomials runs the 16-per-thread latency kernel (0 = never)
@@ -354,7 +356,7 @@ extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
 }
 extern "C" int fhe_rns_ntt_workspace_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {
     if (!h || !bytes) return fail(FHE_ERR_INVALID_ARG, "workspace_bytes: null argument");
-    *bytes = (uint64_t)h->ws_bytes + h->ws2_bytes + h->ws3_bytes + h->lin_bytes + h->enc_bytes;
+    *bytes = (uint64_t)h->ws_bytes + h->ws2_bytes + h->ws3_bytes + h->lin_bytes + h->enc_bytes + h->dec_bytes;
     return FHE_OK;
 }
 extern "C" int fhe_rns_ntt_width_class(const fhe_rns_ntt_t *h) { return h ? h->width : fail(FHE_ERR_INVALID_ARG, "null handle"); }

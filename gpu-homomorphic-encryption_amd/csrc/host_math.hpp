@@ -147,6 +147,48 @@ inline bool is_prime(const U256 &n) {
     return true;
 }
 
+// ---- reduction modulo a plaintext modulus t, 2 <= t < 2^64, without a division (fhe_ct_decrypt) --------------------------------
+// Barrett-style: the quotient comes from one multiplication by a precomputed reciprocal, in the form of Moeller and Granlund ("Improved
+// division by invariant integers", 2011, algorithm 4).  t is normalised first: tn = t << s has its top bit set, x mod t = ((x << s) mod tn) >> s,
+// and v = floor((2^128 - 1) / tn) - 2^64 fits one word.  The same functions run on the host (tests, constants) and in the kernels.
+#if defined(__HIPCC__)
+#define FHE_HD __host__ __device__ inline
+#else
+#define FHE_HD inline
+#endif
+struct ModT {
+    uint64_t t, tn, v;       // the modulus, t << s, the reciprocal of tn
+    uint32_t s, _pad;
+};
+inline bool modt_init(ModT &M, uint64_t t) {         // host: the one place that divides
+    if (t < 2) return false;
+    M.t = t; M.s = (uint32_t)__builtin_clzll(t); M._pad = 0; M.tn = t << M.s;
+    M.v = (uint64_t)(~(u128)0 / M.tn - ((u128)1 << 64));
+    return true;
+}
+// (r 2^64 + w) mod tn for r < tn
+FHE_HD uint64_t modt_step(uint64_t r, uint64_t w, const ModT &M) {
+    const u128 p = (u128)M.v * r + (((u128)r << 64) | w);
+    const uint64_t q1 = (uint64_t)(p >> 64) + 1, q0 = (uint64_t)p;
+    uint64_t rem = w - q1 * M.tn;
+    if (rem > q0) rem += M.tn;
+    if (rem >= M.tn) rem -= M.tn;
+    return rem;
+}
+// x mod t for the NW-word integer x (least significant word first): the words of x << s, most significant first, through modt_step
+template <int NW>
+FHE_HD uint64_t modt_reduce(const uint64_t (&x)[NW], const ModT &M) {
+    const uint32_t s = M.s;
+    uint64_t r = s ? x[NW - 1] >> (64 - s) : 0;       // below 2^s <= tn
+    for (int k = NW - 1; k >= 0; k--) {
+        const uint64_t lo = (k && s) ? x[k - 1] >> (64 - s) : 0;
+        r = modt_step(r, (x[k] << s) | lo, M);
+    }
+    return r >> s;
+}
+FHE_HD uint64_t modt_reduce128(uint64_t hi, uint64_t lo, const ModT &M) { const uint64_t x[2] = {lo, hi}; return modt_reduce<2>(x, M); }
+FHE_HD uint64_t modt_mul(uint64_t a, uint64_t b, const ModT &M) { const u128 p = (u128)a * b; return modt_reduce128((uint64_t)(p >> 64), (uint64_t)p, M); }
+
 inline uint32_t bitrev(uint32_t x, uint32_t bits) {
     uint32_t r = 0;
     for (uint32_t i = 0; i < bits; i++) { r = (r << 1) | (x & 1); x >>= 1; }

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "lds_launch.h"
+#include "decrypt.hip.h"
 #include "encrypt.hip.h"
 #include "hoist.hip.h"
 #include "hoist_lincomb.hip.h"
@@ -110,6 +111,16 @@ static bool launch(const LdsArgs &A) {
             if (in || out || !A.r0 || !A.r1 || !A.kb || !A.ka || !A.cdt || !A.cdt_len || A.cdt_len > ENCRYPT_MAX_CDT || A.polys % A.L) return false;
             hipLaunchKernelGGL((ntt_encrypt_kernel<F, LOGN, 2>), dim3(A.per_ct ? A.polys / A.L : A.polys), block, 0, A.stream, (char *)A.r0, (char *)A.r1, (const char *)A.a0,
                                (const E *)A.kb, (const E *)A.ka, A.cdt, A.cdt_len, A.seeds[0], A.seeds[1], A.seeds[2], A.t, limbs, A.L, A.per_ct ? 1u : 0u);
+            return true;
+        }
+        return false;
+    }
+    // Secret-key decryption, first launch: containers in, the compact decryption workspace out
+    if (A.op == LDS_DECRYPT) {
+        if constexpr (lds_decrypt(EB, LOGN)) {
+            if (in || !out || !A.r0 || !A.a0 || !A.a1 || !A.kb || (A.c2 && !A.ka) || A.polys % A.L) return false;
+            hipLaunchKernelGGL((ntt_decrypt_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (E *)A.r0, (const char *)A.a0, (const char *)A.a1, (const char *)A.c2,
+                               (const E *)A.kb, (const E *)A.ka, limbs, A.L);
             return true;
         }
         return false;

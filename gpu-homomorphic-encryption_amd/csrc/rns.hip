@@ -103,10 +103,11 @@ extern "C" int fhe_rns_to_rns(fhe_rns_ntt_t *h, void *d_rns, const void *d_value
                        (const fhe_dev::CrtLimb *)h->d_crt, h->L, h->log_n, count);
     return post_launch(h->stream, "to_rns_kernel");
 }
-template <class F>
-static int from_rns_word(fhe_rns_ntt *h, void *d_values, const void *d_rns, uint32_t batch) {
-    using E = typename F::E; using V = typename F::V16;
-    if (!h->d_from_rns_w_minv) {
+// The CRT operands of the word-sized classes: ((Q / q_l)^-1 mod q_l) as pw operands and Q / q_l as plain integers (Q < 2^255: the callers check)
+int ensure_from_rns_word(fhe_rns_ntt *h) {
+    if (h->d_from_rns_w_minv) return FHE_OK;
+    return with_word_field(h, [&](auto f) {
+        using F = decltype(f); using E = typename F::E;
         const uint32_t L = h->L;
         std::vector<E> minv(L); std::vector<fhe_dev::u256> Ms(L);
         for (uint32_t l = 0; l < L; l++) {
@@ -116,9 +117,17 @@ static int from_rns_word(fhe_rns_ntt *h, void *d_values, const void *d_rns, uint
             minv[l] = word_operand<F>(inv_mod_u64((uint64_t)Mi_mod_q, q), q);
             std::memcpy(Ms[l].l, Mi.w, 32);
         }
+        void *d_minv = nullptr;
         int rc;
-        if ((rc = upload(h, minv, &h->d_from_rns_w_minv)) || (rc = upload(h, Ms, &h->d_from_rns_w_M))) return rc;
-    }
+        if ((rc = upload(h, minv, &d_minv)) || (rc = upload(h, Ms, &h->d_from_rns_w_M))) return rc;
+        h->d_from_rns_w_minv = d_minv;                 // set last: the pair is there or neither is
+        return (int)FHE_OK;
+    });
+}
+template <class F>
+static int from_rns_word(fhe_rns_ntt *h, void *d_values, const void *d_rns, uint32_t batch) {
+    using E = typename F::E; using V = typename F::V16;
+    if (int rc = ensure_from_rns_word(h)) return rc;
     const size_t count = (size_t)batch * h->n;
     hipLaunchKernelGGL((fhe_dev::from_rns_word_kernel<F>), dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_values, (const V *)d_rns,
                        (const fhe_dev::Limb<F> *)h->d_limbs, (const E *)h->d_from_rns_w_minv, (const fhe_dev::u256 *)h->d_from_rns_w_M, h->crt_big.Q,

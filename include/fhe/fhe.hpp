@@ -4,6 +4,7 @@
 // encryption).  Bootstrapping is out of scope of this engine.
 #pragma once
 #include <algorithm>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <memory>
@@ -28,7 +29,13 @@ struct PublicKey {                                            // include/fhe.cuh
     mutable std::shared_ptr<fhe_public_key_t> imported;
     mutable const void *imported_for = nullptr;
 };
-struct SecretKey { Polynomial *sk; };                         // include/fhe.cuh:47-49
+struct SecretKey {                                            // include/fhe.cuh:47-49
+    Polynomial *sk;
+    // engine-side copies for FHEContext::decrypt_fused / noise_budget_fused (fhe_secret_key_create), one per level (index = level), built on
+    // first use: a level's key is the first L - level limbs of sk, imported through the same pointer; shared, so that copies of the struct stay valid
+    mutable std::vector<std::shared_ptr<fhe_secret_key_t>> imported;
+    mutable const void *imported_for = nullptr;
+};
 struct RelinKeys {                                            // include/fhe.cuh:52-55
     std::vector<PublicKey *> rlk_keys;     // level j*K + k: (b, a) with b = -a*s + e + g*s^2, g = 2^(k*w) in limb j, 0 elsewhere
     uint32_t decomp_bits = 16;
@@ -329,6 +336,7 @@ public:
 
     void keygen(PublicKey &pk, SecretKey &sk) {                                            // src/fhe.cu:54-74
         sk.sk = new_polynomial(); pk.pk0 = new_polynomial(); pk.pk1 = new_polynomial();
+        sk.imported.clear();                                                                // engine-side copies of an earlier key
         draw_ternary(*sk.sk);                                                               // ternary secret (:57)
         draw_uniform(*pk.pk1);                                                              // :64
         std::unique_ptr<Polynomial> as(new_polynomial());
@@ -639,6 +647,29 @@ public:
         pt.is_ntt_form = false;
     }
 
+    // decrypt in ONE engine call (fhe_ct_decrypt) on the engine of ct's level: the n plaintext coefficients come back as 8-byte integers, already
+    // reduced mod t and divided by ct.correction (scale = correction^-1 mod t).  The secret key is imported once per level and kept.  Equals
+    // decrypt slot for slot; decrypt itself stays as it is.
+    void decrypt_fused(Plaintext &pt, const Ciphertext &ct, const SecretKey &sk) {
+        const uint32_t n = params_.n;
+        std::vector<uint64_t> m(n);
+        run_decrypt(ct, sk, m.data(), nullptr);
+        std::vector<long long> sm(m.begin(), m.end());
+        if (!pt.poly) pt.poly = new_polynomial();
+        upload_signed(*pt.poly, sm);
+        pt.is_ntt_form = false;
+    }
+    // estimate_noise_budget from the same call: max(0, bit_length(Q_l) - 2 - bit_length(max |v|)).  The engine reports the bit length of the
+    // maximum, which cannot tell 2^k from 2^k + 1, so this is the bound that is never optimistic: equal to estimate_noise_budget, except one bit
+    // lower when the maximum is an exact power of two (and the budget is not already 0).
+    float noise_budget_fused(const Ciphertext &ct, const SecretKey &sk) {
+        uint32_t bits = 0;
+        run_decrypt(ct, sk, nullptr, &bits);
+        uint64_t Q[4] = {1, 0, 0, 0};
+        for (uint32_t l = 0; l < num_levels() - ct.level; l++) mul_small(Q, params_.rns_moduli[l].limbs[0]);
+        return (float)std::max(0, bit_length(Q) - 2 - (int)bits);
+    }
+
     const SchemeParams &params() const { return params_; }
 
 private:
@@ -669,6 +700,39 @@ private:
         for (uint32_t l = 0; l < Ll; l++) mul_small(Q, params_.rns_moduli[l].limbs[0]);
         for (int i = 0; i < 4; i++) half[i] = (Q[i] >> 1) | (i < 3 ? Q[i + 1] << 63 : 0);
         return v;
+    }
+    // the secret key on the engine of `level`, imported on first use (SecretKey::imported)
+    const fhe_secret_key_t *secret_key_at(const SecretKey &sk, uint32_t level) {
+        if (sk.imported_for != params_.rns_ntt) { sk.imported.clear(); sk.imported_for = params_.rns_ntt; }
+        if (sk.imported.size() < num_levels()) sk.imported.resize(num_levels());
+        if (!sk.imported[level]) {
+            fhe_secret_key_t *k = nullptr;
+            check(fhe_secret_key_create(engine(level).handle(), &k, sk.sk->coeffs), "decrypt_fused: secret key import");
+            sk.imported[level].reset(k, [](fhe_secret_key_t *p) { fhe_secret_key_destroy(p); });
+        }
+        return sk.imported[level].get();
+    }
+    // one fhe_ct_decrypt of ct at its level; m (n values) and / or noise_bits may be null
+    void run_decrypt(const Ciphertext &ct, const SecretKey &sk, uint64_t *m, uint32_t *noise_bits) {
+        const uint32_t n = params_.n, Ll = num_levels() - ct.level;
+        if (ct.components.size() != 2 && ct.components.size() != 3) throw std::runtime_error("FHEContext: a ciphertext of 2 or 3 components is needed");
+        for (const Polynomial *c : ct.components)
+            if (c->num_limbs != Ll) throw std::runtime_error("FHEContext: ciphertext components do not have the limbs of its level");
+        const fhe_secret_key_t *key = secret_key_at(sk, ct.level);
+        const size_t m_bytes = (size_t)n * sizeof(uint64_t), words = (m_bytes + sizeof(uint32_t) + sizeof(uint256_t) - 1) / sizeof(uint256_t);
+        uint256_t *d_out = device_alloc(words);                     // [n] plaintext coefficients, then the noise bits
+        uint64_t *d_m = reinterpret_cast<uint64_t *>(d_out);
+        uint32_t *d_bits = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(d_out) + m_bytes);
+        std::vector<const uint256_t *> comps;
+        for (const Polynomial *c : ct.components) comps.push_back(c->coeffs);
+        std::vector<uint256_t> host(words);
+        try {
+            engine(ct.level).decrypt(key, params_.t, inv_mod_t(ct.correction), d_m, noise_bits ? d_bits : nullptr, comps.data(), (uint32_t)comps.size());
+            device_synchronize(); copy_to_host(host.data(), d_out, words);
+        } catch (...) { device_free(d_out); throw; }
+        device_free(d_out);
+        if (m) std::memcpy(m, host.data(), m_bytes);
+        if (noise_bits) std::memcpy(noise_bits, reinterpret_cast<const char *>(host.data()) + m_bytes, sizeof(uint32_t));
     }
     static void same_level(const Ciphertext &a, const Ciphertext &b, const char *what) {
         if (a.level != b.level) throw std::runtime_error(std::string(what) + ": operands at different levels (mod_switch_to_level first)");

@@ -73,6 +73,11 @@ public:
     void rescale_drop_last(uint256_t *d_out, const uint256_t *d_in, uint32_t batch = 1) { check(fhe_rns_rescale_drop_last(h_, d_out, d_in, batch), "rescale_drop_last"); }
     // FHEContext::mod_switch_to_next (include/fhe.cuh:109): BGV modulus switch of up to three ciphertext components in one launch; d_in / d_out are
     // HOST arrays of num_components device pointers, [batch][L][n] in and [batch][L-1][n] out; the plaintext keeps the factor q_last^-1 mod t
+    // fhe_ct_decrypt: d_m[b][x] = ((v mod t) scale) mod t, d_noise_bits[b] = bit_length(max |v|), v the centred c0 + c1 s (+ c2 s^2)
+    void decrypt(const fhe_secret_key_t *sk, uint64_t t, uint64_t scale, uint64_t *d_m, uint32_t *d_noise_bits, const uint256_t *const *d_components,
+                 uint32_t num_components, uint32_t batch = 1) {
+        check(fhe_ct_decrypt(h_, sk, t, scale, d_m, d_noise_bits, reinterpret_cast<const void *const *>(d_components), num_components, batch), "decrypt");
+    }
     void mod_switch_drop_last(uint64_t t, uint256_t *const *d_out, const uint256_t *const *d_in, uint32_t num_components, uint32_t batch = 1) {
         check(fhe_ct_mod_switch_drop_last(h_, t, reinterpret_cast<void *const *>(d_out), reinterpret_cast<const void *const *>(d_in), num_components, batch),
               "mod_switch_drop_last");

@@ -260,6 +260,46 @@ int fhe_ct_encrypt_reserve(fhe_rns_ntt_t *h, double sigma, uint32_t batch);
 int fhe_ct_encrypt(fhe_rns_ntt_t *h, const fhe_public_key_t *pk, uint64_t t, double sigma, const uint64_t seeds[3], void *d_out0, void *d_out1,
                    const void *d_m, uint32_t batch);
 
+/* ---- secret-key decryption as one call ------------------------------------------------------------------------------------------
+ * FHEContext::decrypt (src/fhe.cu:171-195) and FHEContext::estimate_noise_budget in one call, the inverse of fhe_ct_encrypt.  d_components
+ * is a HOST array of num_components (2 or 3) device pointers to [batch][L][n] canonical containers: c0, c1 and optionally c2 (the convention
+ * of fhe_ct_mod_switch_drop_last).  With Q the product of the engine's moduli and, for ciphertext b and coefficient x,
+ *     w = (c0 + c1 (*) s + c2 (*) s (*) s)[b][x] mod Q in [0, Q)       (products in Z_Q[x] / (x^n + 1), by CRT over the limbs)
+ *     v = w if w <= floor(Q / 2), else w - Q                            the centred representative, in (-Q/2, Q/2]; Q is odd: no tie
+ * the outputs are
+ *     d_m[b][x]        = ((v mod t) * scale) mod t                      a plain uint64_t in [0, t); d_m is [batch][n]
+ *     d_noise_bits[b]  = bit_length(max_x |v[b][x]|)                     0 when every v is 0; d_noise_bits is [batch] and may be NULL
+ * where v mod t is the non-negative residue.  scale is what include/fhe/fhe.hpp calls correction^-1 mod t (1: no correction).  The result is an
+ * exact function of (components, s, t, scale): every path gives the same bits, whatever the batch, the grid or the kernel form.  Any t with
+ * 2 <= t < 2^64 is accepted; the reduction modulo t is division-free (a reciprocal prepared on the host per call, passed as a kernel argument).
+ *
+ * Q must be below 2^255, the limit of fhe_rns_from_rns, because the noise bits need the integer itself: FHE_ERR_UNSUPPORTED otherwise
+ * (from fhe_ct_decrypt_reserve too).
+ *
+ * On the LDS-resident word-sized sizes, N = 2^11 .. 2^14, a call is TWO launches: one workgroup per (ciphertext, limb) transforms c1 (and c2),
+ * multiplies by the kept transforms of s (and s^2), inverts, adds c0 and writes the limb's residues compactly into a library workspace; a
+ * second launch, one lane per coefficient, does the CRT, the centring, the reduction modulo t and the per-ciphertext maximum.  2 S (3 S)
+ * bytes of containers are read.  Elsewhere (full-width class, N >= 2^15, sizes below 2^11, FHE_HIP_NO_FUSED_DECRYPT=1) the library composes
+ * fhe_rns_ntt_multiply_bcast and fhe_rns_poly_add through container scratch of its own and runs the second launch on that.
+ * fhe_rns_ntt_workspace_bytes counts the workspace either way.
+ *
+ * fhe_secret_key_create: d_s is [L][n] canonical containers in coefficient form.  It is copied (its address is remembered only for the aliasing
+ * check of fhe_ct_decrypt); s (*) s and, for the two-launch path, the transforms of both are built at import, which is complete when the call
+ * returns.  FHE_ERR_INVALID_ARG with *out untouched: a null or misaligned argument.  fhe_secret_key_destroy(NULL) is FHE_OK. */
+typedef struct fhe_secret_key fhe_secret_key_t;
+int fhe_secret_key_create(fhe_rns_ntt_t *h, fhe_secret_key_t **out, const void *d_s);
+int fhe_secret_key_destroy(fhe_secret_key_t *sk);
+/* Sizes everything a later fhe_ct_decrypt with up to `num_components` components and up to `batch` ciphertexts needs (CRT tables, the
+ * decryption workspace, the composed path's product workspaces).  After it such a call allocates nothing, fhe_rns_ntt_workspace_bytes does
+ * not change across it, and it can be captured into a hipGraph (the zeroing of d_noise_bits is part of the capture).  t is checked only:
+ * its constants travel with every call. */
+int fhe_ct_decrypt_reserve(fhe_rns_ntt_t *h, uint64_t t, uint32_t num_components, uint32_t batch);
+/* FHE_ERR_INVALID_ARG, with nothing launched and nothing written: a null handle, key, d_m, d_components or component; num_components outside
+ * {2, 3}; a key of another engine; a component or d_m that is not 16-byte aligned (d_noise_bits: 4-byte); d_m or d_noise_bits equal to each
+ * other, to a component, or to the key's source; batch == 0; t < 2; scale == 0 or scale >= t. */
+int fhe_ct_decrypt(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint64_t t, uint64_t scale, uint64_t *d_m, uint32_t *d_noise_bits,
+                   const void *const *d_components, uint32_t num_components, uint32_t batch);
+
 /* Fast base conversion (Bajard et al.) -- RNSContext::base_extend / fast_base_conversion_kernel (include/rns.cuh:47-48,
  * 116-125, undefined in the reference): d_out[b][j][x] = sum_i [x_i (Q/q_i)^-1]_{q_i} (Q/q_i) mod p_j for the primes p_j of
  * `target` (an engine of the same degree).  The value is that of X + alpha*Q, 0 <= alpha < L (inexact by design of the

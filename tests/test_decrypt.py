@@ -1,0 +1,475 @@
+"""Secret-key decryption as one engine call (fhe_secret_key_create / fhe_ct_decrypt_reserve / fhe_ct_decrypt).
+
+With v[b][x] the centred representative in (-Q/2, Q/2] of (c0 + c1 s + c2 s^2)[b][x] mod Q:
+
+    d_m[b][x] = ((v mod t) * scale) mod t,        d_noise_bits[b] = bit_length(max_x |v[b][x]|)
+
+The expected values come from Python integers alone: the oracle's RnsPlan.polymul per limb, CRT, centring, % t, * scale % t and
+int.bit_length.  Every comparison is bit for bit; the inputs are uniformly random canonical residues for c0, c1, c2 AND for s."""
+import concurrent.futures
+import ctypes
+import math
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import memcheck
+import ntt_math as nm
+from test_encrypt import _containers, _embed, _ints, _keygen
+from test_hoisted import CSRC, HIPCC, RES_FIELDS, RES_FLAGS, _resource_remarks
+from workload import rns_poly
+
+NEW_SYMBOLS = ("fhe_secret_key_create", "fhe_secret_key_destroy", "fhe_ct_decrypt_reserve", "fhe_ct_decrypt")
+T, SIGMA = 65537, 3.2
+T_BIG = (1 << 64) - 59
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ------------------------------------------------------------------------------------------------ host maths
+def _crt_centred(res, moduli):
+    """[...][L][n] Python-integer residues -> centred integers [...][n] (negative exactly above floor(Q / 2))."""
+    Q = math.prod(moduli)
+    tot = 0
+    for l, q in enumerate(moduli):
+        Ml = Q // q
+        tot = (tot + res[..., l, :] % q * (Ml * pow(Ml, -1, q))) % Q
+    return np.where(tot > Q // 2, tot - Q, tot)
+
+
+def _outputs(v, t, scale):
+    """centred integers [batch][n] -> (d_m as uint64 [batch][n], d_noise_bits as uint32 [batch])"""
+    m = np.array((v % t) * scale % t, dtype=object).astype(np.uint64)
+    bits = np.array([max(int(abs(x)) for x in row).bit_length() for row in v], dtype=np.uint32)
+    return m, bits
+
+
+def _expected(oracle, n, moduli, comps, s, t=T, scale=1):
+    """comps: 2 or 3 arrays [batch][L][n][4]; s: [L][n][4].  The definition, by the oracle's polymul and Python integers."""
+    rp = oracle.RnsPlan(n, moduli)
+    batch = comps[0].shape[0]
+    sb = np.ascontiguousarray(np.broadcast_to(s[None], comps[1].shape))
+    res = _ints(comps[0]) + _ints(rp.polymul(np.ascontiguousarray(comps[1]), sb, threads=8))
+    if len(comps) == 3:
+        s2 = rp.polymul(np.ascontiguousarray(s[None]), np.ascontiguousarray(s[None]), threads=8)
+        s2b = np.ascontiguousarray(np.broadcast_to(s2, comps[2].shape))
+        res = res + _ints(rp.polymul(np.ascontiguousarray(comps[2]), s2b, threads=8))
+    assert res.shape == (batch, len(moduli), n)
+    return _outputs(_crt_centred(res, moduli), t, scale)
+
+
+def _primes(bits, n, count):
+    return nm.largest_ntt_primes(bits, n, count) if bits == 64 else nm.ntt_primes(bits, n, count)
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_exports_wrappers_and_rejection_without_device(pkg):
+    lib = pkg.lib()
+    for name in NEW_SYMBOLS:
+        assert hasattr(lib, name), name
+    for method in ("import_secret_key", "decrypt", "decrypt_reserve"):
+        assert callable(getattr(pkg.RnsNttEngine, method)), method
+    assert callable(pkg.capi.SecretKey)
+    out = ctypes.c_void_p(0x1234)
+    assert lib.fhe_secret_key_create(None, ctypes.byref(out), None) == -1 and out.value == 0x1234
+    assert lib.fhe_ct_decrypt_reserve(None, 65537, 2, 1) == -1
+    comps = (ctypes.c_void_p * 2)(None, None)
+    assert lib.fhe_ct_decrypt(None, None, 65537, 1, None, None, comps, 2, 1) == -1
+    assert lib.fhe_secret_key_destroy(None) == 0
+
+
+RES_SRC = """#include "lds_launch.h"
+#include "decrypt.hip.h"
+using namespace fhe_dev;
+template __global__ void fhe_dev::ntt_decrypt_kernel<RES_FIELD, RES_LOGN, 2>(RES_FIELD::E*, const char*, const char*, const char*, const RES_FIELD::E*, const RES_FIELD::E*,
+    const Limb<RES_FIELD>*, uint32_t);
+"""
+TABLE_SRC = """#include <cstdio>
+#include "lds_launch.h"
+int main() {
+    for (int eb : {4, 8}) for (int n = 11; n <= 15; n++) std::printf("%d %d %d\\n", eb, n, (int)fhe_dev::lds_decrypt(eb, n));
+    return 0;
+}
+"""
+# (VGPRs, waves per SIMD) an instance must keep: the kernel is compiled for two workgroups per CU (256 VGPRs); the 4-byte residues hold two
+# 32-register arrays and fit three waves per SIMD (512 / 3 -> 168 VGPRs)
+BUDGET = {"F32": (168, 3), "F52": (256, 2), "F64": (256, 2), "F64X": (256, 2)}
+
+
+def test_decrypt_kernels_stay_within_their_budgets(tmp_path):
+    """fhe_dev::lds_decrypt is pinned for every (4, 8) x (11..15).  Every instance it names compiles for gfx950 with NO scratch and inside the
+    VGPR budget of its field.  The instance it leaves out (4-byte residues at N = 2^15: 1024-thread workgroups cap a thread at 128 VGPRs) is
+    compiled too and must MISS that: it is why that size takes the composed path."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not installed")
+    (tmp_path / "table.hip").write_text(TABLE_SRC)
+    res = subprocess.run([HIPCC, "-std=c++17", "-I", CSRC, "-o", str(tmp_path / "table"), str(tmp_path / "table.hip")], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    table = {}
+    for line in subprocess.run([str(tmp_path / "table")], capture_output=True, text=True, timeout=60).stdout.splitlines():
+        eb, n, dec = (int(x) for x in line.split())
+        table[(eb, n)] = bool(dec)
+    assert table == {(eb, n): n <= 14 for eb in (4, 8) for n in range(11, 16)}, table
+    named = [(f, n) for f, (eb, sizes) in RES_FIELDS.items() for n in sizes if table[(eb, n)]]
+    left_out = [(f, n) for f, (eb, sizes) in RES_FIELDS.items() for n in sizes if not table[(eb, n)]]
+    assert left_out == [("F32", 15)] and len(named) == 16, (left_out, named)
+    (tmp_path / "dec_res.hip").write_text(RES_SRC)
+    jobs = [((f, n), [HIPCC, *RES_FLAGS, f"-DRES_FIELD={f}", f"-DRES_LOGN={n}", "-c", "-o", str(tmp_path / f"d_{f}_{n}.o"), str(tmp_path / "dec_res.hip")])
+            for f, n in named + left_out]
+
+    def run(job):
+        res = subprocess.run(job[1], capture_output=True, text=True, timeout=1500)
+        assert res.returncode == 0, res.stderr[-3000:]
+        return job[0], _resource_remarks(res.stderr)
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
+        got = dict(ex.map(run, jobs))
+    for (f, n) in named:
+        ks = [r for k, r in got[(f, n)].items() if "ntt_decrypt_kernel" in k]
+        assert len(ks) == 1, (f, n, list(got[(f, n)]))
+        r = ks[0]
+        print(f, n, r)
+        assert r["vgprs"] <= BUDGET[f][0] and r["occupancy"] >= BUDGET[f][1], (f, n, r)
+        assert r.get("scratch", 0) == 0, (f, n, r)
+    for (f, n) in left_out:
+        ks = [r for k, r in got[(f, n)].items() if "ntt_decrypt_kernel" in k]
+        print("left out:", f, n, ks)
+        assert len(ks) == 1 and ks[0].get("scratch", 0) > 0, (f, n, got[(f, n)])
+
+
+MODT_SRC = """#include <cinttypes>
+#include <cstdio>
+#include "host_math.hpp"
+// stdin: lines "t w3 w2 w1 w0 b" (hex); stdout: x mod t for the 128-bit x = (w1, w0), for the 256-bit x = (w3..w0), and (w0 mod t) * b mod t
+int main() {
+    unsigned long long t, w[4], b;
+    while (std::scanf("%llx %llx %llx %llx %llx %llx", &t, &w[3], &w[2], &w[1], &w[0], &b) == 6) {
+        fhe_host::ModT M;
+        if (!fhe_host::modt_init(M, t)) return 2;
+        const uint64_t x[4] = {w[0], w[1], w[2], w[3]};
+        const uint64_t r0 = fhe_host::modt_reduce128(w[1], w[0], M);
+        std::printf("%llx %llx %llx\\n", (unsigned long long)r0, (unsigned long long)fhe_host::modt_reduce<4>(x, M),
+                    (unsigned long long)fhe_host::modt_mul(fhe_host::modt_reduce128(0, w[0], M), b, M));
+    }
+    return 0;
+}
+"""
+
+
+def test_the_division_free_reduction_modulo_t_matches_python(tmp_path):
+    """The reduction of host_math.hpp (the same functions the CRT kernel runs) as a stand-alone host program against Python's %: t at both
+    ends of the range and in between, random 128- and 256-bit inputs and the extremes."""
+    cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else HIPCC
+    (tmp_path / "modt.cpp").write_text(MODT_SRC)
+    res = subprocess.run([cxx, "-std=c++17", "-O1", "-I", CSRC, "-o", str(tmp_path / "modt"), str(tmp_path / "modt.cpp")], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    rng = random.Random(5)
+    M64 = (1 << 64) - 1
+    ts = [2, 3, 65537, (1 << 32) - 5, (1 << 63) + 0x1234567, T_BIG, (1 << 63), (1 << 64) - 1, (1 << 33) + 1]
+    cases = []
+    for t in ts:
+        words = [[rng.getrandbits(64) for _ in range(4)] for _ in range(200)]
+        words += [[0, 0, 0, 0], [M64] * 4, [0, 0, M64, M64], [0, 0, t - 1, M64], [0, 0, 0, t], [0, 0, 0, t - 1], [1 << 63, 0, 0, 0], [0, 0, 1, 0], [M64, 0, 0, 0]]
+        for w in words:
+            cases.append((t, w, rng.getrandbits(64) if rng.random() < 0.9 else M64))
+    text = "".join(f"{t:x} {w[0]:x} {w[1]:x} {w[2]:x} {w[3]:x} {b:x}\n" for t, w, b in cases)
+    out = subprocess.run([str(tmp_path / "modt")], input=text, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0
+    lines = out.stdout.split("\n")[:-1]
+    assert len(lines) == len(cases)
+    for (t, w, b), line in zip(cases, lines):
+        r128, r256, rmul = (int(x, 16) for x in line.split())
+        x128 = (w[2] << 64) | w[3]
+        x256 = (w[0] << 192) | (w[1] << 128) | x128
+        assert (r128, r256, rmul) == (x128 % t, x256 % t, (w[3] % t) * b % t), (hex(t), [hex(x) for x in w], hex(b))
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+_cache = {}
+
+
+def _case(oracle, n, moduli, batch, ncomp, t=T, scale=1, seed=40):
+    key = (n, tuple(moduli), batch, ncomp, t, scale, seed)
+    if key not in _cache:
+        comps = [rns_poly(seed + k, moduli, n, batch) for k in range(ncomp)]
+        s = rns_poly(seed + 7, moduli, n, 1)[0]
+        _cache[key] = (comps, s) + _expected(oracle, n, moduli, comps, s, t, scale)
+    return _cache[key]
+
+
+def _run(pkg, n, moduli, comps, s, t=T, scale=1, noise=True, reserve=False, twice=True, ws=None):
+    batch = comps[0].shape[0]
+    e = pkg.RnsNttEngine(n, moduli)
+    ds = pkg.DeviceBuffer.from_numpy(s)
+    sk = e.import_secret_key(ds)
+    if reserve:
+        e.decrypt_reserve(t, len(comps), batch)
+    dc = [pkg.DeviceBuffer.from_numpy(c) for c in comps]
+    dm, dn = pkg.DeviceBuffer(batch * n * 8), pkg.DeviceBuffer(batch * 4)
+    if ws is not None:
+        ws.append(e.workspace_bytes())
+    for _ in range(2 if twice else 1):
+        memcheck.poison(pkg, dm); memcheck.poison(pkg, dn)
+        e.decrypt(sk, t, scale, dm, dn if noise else None, dc, batch)
+        got = dm.download((batch, n)), dn.download((batch,), np.uint32)
+    if ws is not None:
+        ws.append(e.workspace_bytes())
+    for c, d in zip(comps, dc):
+        assert np.array_equal(d.download(c.shape), c)
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ncomp", [2, 3])
+@pytest.mark.parametrize("bits", [30, 40, 60, 64])
+def test_decrypt_matches_python_on_every_width_class(pkg, oracle, bits, ncomp):
+    n, L, batch = 2048, 2, 3
+    moduli = _primes(bits, n, L)
+    comps, s, wm, wb = _case(oracle, n, moduli, batch, ncomp)
+    gm, gb = _run(pkg, n, moduli, comps, s)
+    assert np.array_equal(gb, wb), (gb, wb)
+    assert np.array_equal(gm, wm)
+
+
+def _unit(t, seed):
+    rng = random.Random(seed)
+    while True:
+        u = rng.randrange(2, t)
+        if math.gcd(u, t) == 1:
+            return u
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("t", [2, 65537, T_BIG])
+def test_plaintext_moduli_and_scales(pkg, oracle, t):
+    n, L, batch = 2048, 2, 2
+    moduli = _primes(30, n, L)
+    for scale in sorted({1, t - 1, _unit(t, 3) if t > 3 else 1}):
+        comps, s, wm, wb = _case(oracle, n, moduli, batch, 2, t, scale)
+        gm, gb = _run(pkg, n, moduli, comps, s, t, scale, twice=False)
+        assert np.array_equal(gb, wb) and np.array_equal(gm, wm), (t, scale)
+        assert int(gm.max()) < t
+
+
+@pytest.mark.gpu
+def test_crafted_noise_and_centring_edges(pkg):
+    """c1 = 0 and c0 the embedding of chosen integers: ciphertext 0 is v = 0 everywhere (0 bits); ciphertext 1 holds
+    1, -1, 2^k, 2^k + 1, -2^k, floor(Q / 2), floor(Q / 2) + 1 (= -floor(Q / 2)) and Q - 1 (= -1) at different coefficients, with the largest
+    magnitude moved between runs; ciphertext 2 is small again: one ciphertext's maximum does not leak into another's."""
+    n, L, batch, k = 2048, 2, 3, 37
+    moduli = _primes(30, n, L)
+    Q = math.prod(moduli)
+    s = rns_poly(1, moduli, n, 1)[0]
+    zero = np.zeros((batch, L, n, 4), np.uint64)
+    runs = [
+        {5: 1, 70: -1, 130: 1 << k, 700: (1 << k) + 1, 1500: -(1 << k)},                        # largest: 2^k + 1 -> k + 1 bits
+        {5: 1, 70: -1, 130: 1 << k, 1500: -(1 << k)},                                              # largest: 2^k (both signs) -> k + 1 bits
+        {5: 1, 70: -1, 130: (1 << k) - 1},                                                         # largest: 2^k - 1 -> k bits
+        {0: Q // 2, 5: 1},                                                                         # the largest positive value
+        {2047: Q // 2 + 1, 5: 1 << k},                                                             # = -floor(Q / 2)
+        {64: Q - 1},                                                                               # = -1 -> 1 bit
+        {63: 1},
+    ]
+    want_bits = [k + 1, k + 1, k, (Q // 2).bit_length(), (Q // 2).bit_length(), 1, 1]
+    for t, scale in ((T, 1), (T_BIG, T_BIG - 1)):
+        for spec, bits1 in zip(runs, want_bits):
+            w = np.zeros((batch, n), dtype=object)
+            for x, val in spec.items():
+                w[1, x] = val % Q
+            w[2, 9] = 3; w[2, 10] = Q - 2
+            c0 = _embed(w, moduli)
+            v = np.where(w > Q // 2, w - Q, w)
+            wm, wb = _outputs(v, t, scale)
+            assert list(wb) == [0, bits1, 2]
+            gm, gb = _run(pkg, n, moduli, [c0, zero], s, t, scale, twice=False)
+            assert np.array_equal(gb, wb), (spec, gb, wb)
+            assert np.array_equal(gm, wm), spec
+
+
+def _encrypt(pkg, e, n, moduli, pk0, pk1, m, batch, seeds=(11, 22, 33)):
+    src = pkg.DeviceBuffer.from_numpy(pk0), pkg.DeviceBuffer.from_numpy(pk1)
+    pk = e.import_public_key(*src)
+    nbytes = batch * len(moduli) * n * 32
+    o0, o1 = pkg.DeviceBuffer(nbytes), pkg.DeviceBuffer(nbytes)
+    e.encrypt(pk, T, SIGMA, seeds, o0, o1, pkg.DeviceBuffer.from_numpy(m), batch)
+    return o0, o1, src
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [2048, 8192])
+def test_round_trip_with_fhe_ct_encrypt(pkg, oracle, n):
+    """A real key pair: fhe_ct_encrypt then fhe_ct_decrypt returns the messages, and the noise is at most bit_length(t B (2n + 1) + t),
+    B = ceil(12 sigma): the bound test_encrypt.py::test_the_definition_decrypts_on_the_oracle derives."""
+    L, batch = 3, 4
+    moduli = _primes(30, n, L)
+    s, pk0, pk1 = _keygen(oracle, n, moduli, T, 77)
+    rng = np.random.default_rng(3)
+    msg = rng.integers(0, T, (batch, n)).astype(object)
+    e = pkg.RnsNttEngine(n, moduli)
+    o0, o1, _keep = _encrypt(pkg, e, n, moduli, pk0, pk1, _embed(msg, moduli), batch)
+    ds = pkg.DeviceBuffer.from_numpy(_embed(s[None], moduli)[0])                # kept alive: an output at the source's address is rejected as aliasing
+    sk = e.import_secret_key(ds)
+    dm, dn = pkg.DeviceBuffer(batch * n * 8), pkg.DeviceBuffer(batch * 4)
+    e.decrypt(sk, T, 1, dm, dn, [o0, o1], batch)
+    assert np.array_equal(dm.download((batch, n)), msg.astype(np.uint64))
+    bits = dn.download((batch,), np.uint32)
+    bound = (T * math.ceil(12 * SIGMA) * (2 * n + 1) + T).bit_length()
+    assert (bits <= bound).all() and (bits > T.bit_length()).all(), (bits, bound)
+
+
+CHILD = """import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import importlib
+import numpy as np
+pkg = importlib.import_module("gpu-homomorphic-encryption_amd")
+from test_decrypt import _primes, _run
+from workload import rns_poly
+out = {{}}
+for bits in (30, 40, 60, 64):
+    for ncomp in (2, 3):
+        n, L, batch = 2048, 2, 3
+        moduli = _primes(bits, n, L)
+        comps = [rns_poly(40 + k, moduli, n, batch) for k in range(ncomp)]
+        s = rns_poly(47, moduli, n, 1)[0]
+        ws = []
+        gm, gb = _run(pkg, n, moduli, comps, s, twice=False, ws=ws)
+        assert ws[1] - ws[0] >= (ncomp - 1) * batch * L * n * 32, ws          # the composed path's container scratch
+        out[f"m_{{bits}}_{{ncomp}}"] = gm; out[f"b_{{bits}}_{{ncomp}}"] = gb
+np.savez(sys.argv[1], **out)
+"""
+
+
+@pytest.mark.gpu
+def test_the_composed_path_gives_the_same_bits(pkg, oracle, tmp_path):
+    """FHE_HIP_NO_FUSED_DECRYPT=1 in a child process (the switch is read at engine creation; a fresh process keeps it out of this one) on every
+    width class at n = 2048, against Python."""
+    (tmp_path / "child.py").write_text(CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests")))
+    env = dict(os.environ, FHE_HIP_NO_FUSED_DECRYPT="1")
+    res = subprocess.run([sys.executable, str(tmp_path / "child.py"), str(tmp_path / "out.npz")], capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    got = np.load(tmp_path / "out.npz")
+    for bits in (30, 40, 60, 64):
+        for ncomp in (2, 3):
+            _, _, wm, wb = _case(oracle, 2048, _primes(bits, 2048, 2), 3, ncomp)
+            assert np.array_equal(got[f"b_{bits}_{ncomp}"], wb) and np.array_equal(got[f"m_{bits}_{ncomp}"], wm), (bits, ncomp)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,bits,L,batch,ncomp", [(2048, 120, 2, 2, 3), (32768, 30, 2, 1, 2), (64, 30, 2, 3, 3), (16, 30, 2, 5, 2)])
+def test_sizes_and_classes_that_take_the_composed_path(pkg, oracle, n, bits, L, batch, ncomp):
+    """The full-width class (2 x 120-bit), N = 2^15 (no kernel instance) and rings below the LDS range (n = 16: several ciphertexts per wave
+    in the CRT launch)."""
+    moduli = _primes(bits, n, L)
+    comps, s, wm, wb = _case(oracle, n, moduli, batch, ncomp)
+    ws = []
+    gm, gb = _run(pkg, n, moduli, comps, s, twice=False, ws=ws)
+    assert np.array_equal(gb, wb) and np.array_equal(gm, wm)
+    assert ws[1] - ws[0] >= (ncomp - 1) * batch * L * n * 32
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L,batch", [(1, 1), (6, 1), (1, 257), (6, 257)])
+def test_limb_counts_and_batches_cover_the_grid_maps(pkg, oracle, L, batch):
+    """n = 4096: one limb and six, one ciphertext and 257 (a grid that is no multiple of the 8 XCDs; the CRT launch past one grid's worth of
+    lanes).  Ciphertext 0 and the last are compared with Python; ciphertext 0 does not depend on the batch."""
+    n = 4096
+    moduli = _primes(30, n, L)
+    ends = [0, batch - 1] if batch > 1 else [0]
+    comps = [rns_poly(60 + k, moduli, n, batch) for k in range(3)]
+    s = rns_poly(67, moduli, n, 1)[0]
+    wm, wb = _expected(oracle, n, moduli, [c[ends] for c in comps], s)
+    gm, gb = _run(pkg, n, moduli, comps, s, twice=False)
+    assert np.array_equal(gb[ends], wb) and np.array_equal(gm[ends], wm)
+    assert (gb > 0).all()
+
+
+@pytest.mark.gpu
+def test_after_a_modulus_switch(pkg, oracle):
+    """n = 2048, 3 x 30-bit: encrypt, fhe_ct_mod_switch_drop_last once, import s on the 2-limb engine, decrypt with
+    scale = (q_last^-1 mod t)^-1 = q_last mod t: the message."""
+    n, L, batch = 2048, 3, 2
+    moduli = _primes(30, n, L)
+    s, pk0, pk1 = _keygen(oracle, n, moduli, T, 78)
+    rng = np.random.default_rng(4)
+    msg = rng.integers(0, T, (batch, n)).astype(object)
+    e3, e2 = pkg.RnsNttEngine(n, moduli), pkg.RnsNttEngine(n, moduli[:2])
+    o0, o1, _keep = _encrypt(pkg, e3, n, moduli, pk0, pk1, _embed(msg, moduli), batch)
+    lo = [pkg.DeviceBuffer(batch * 2 * n * 32) for _ in range(2)]
+    e3.ct_mod_switch(T, lo, [o0, o1], batch)
+    ds = pkg.DeviceBuffer.from_numpy(_embed(s[None], moduli[:2])[0])            # kept alive, as above
+    sk = e2.import_secret_key(ds)
+    dm, dn = pkg.DeviceBuffer(batch * n * 8), pkg.DeviceBuffer(batch * 4)
+    scale = pow(pow(moduli[2], -1, T), -1, T)
+    assert scale == moduli[2] % T
+    e2.decrypt(sk, T, scale, dm, dn, lo, batch)
+    assert np.array_equal(dm.download((batch, n)), msg.astype(np.uint64))
+    e2.decrypt(sk, T, 1, dm, None, lo, batch)                                   # without the correction: the message times q_last^-1
+    assert np.array_equal(dm.download((batch, n)), (msg * pow(moduli[2], -1, T) % T).astype(np.uint64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["default", "composed"])
+def test_guard_bands_rejections_and_reserve(pkg, oracle, monkeypatch, variant):
+    """d_m and d_noise_bits inside guard bands, poisoned first: fully overwritten, guards intact, inputs read only.  Every rejected call leaves
+    the poisoned outputs untouched.  After fhe_ct_decrypt_reserve a call does not change fhe_rns_ntt_workspace_bytes."""
+    if variant == "composed":
+        monkeypatch.setenv("FHE_HIP_NO_FUSED_DECRYPT", "1")
+    n, L, batch = 2048, 2, 3
+    moduli = _primes(30, n, L)
+    comps, s, wm, wb = _case(oracle, n, moduli, batch, 3)
+    S = L * n * 32
+    e = pkg.RnsNttEngine(n, moduli); other = pkg.RnsNttEngine(n, moduli)
+    arena = memcheck.GuardedArena(pkg, [("c0", batch * S), ("m", batch * n * 8), ("c1", batch * S), ("bits", batch * 4), ("c2", batch * S), ("s", S)], S)
+    for name, c in zip(("c0", "c1", "c2"), comps):
+        arena[name].upload(c)
+    arena["s"].upload(s)
+    sk = e.import_secret_key(arena["s"]); foreign = other.import_secret_key(arena["s"])
+    e.decrypt_reserve(T, 3, batch)
+    before = e.workspace_bytes()
+    assert before >= batch * L * n * 4
+    dm, dn = arena["m"].poison(), arena["bits"].poison()
+    lib = pkg.lib(); P = pkg.capi._ptr
+    c = [P(arena[k]) for k in ("c0", "c1", "c2")]
+
+    def call(h=e.h, key=sk.h, t=T, scale=1, m=P(dm), bits=P(dn), cs=c, nc=3, bt=batch):
+        arr = None if cs is None else (ctypes.c_void_p * 3)(*cs)
+        return lib.fhe_ct_decrypt(h, key, t, scale, m, bits, arr, nc, bt)
+
+    bad = [call(h=None), call(key=None), call(m=None), call(cs=None), call(cs=[c[0], None, c[2]]), call(nc=1), call(nc=4), call(nc=0), call(scale=T), call(scale=T + 5),
+           call(scale=0), call(t=1), call(t=0), call(m=c[0]), call(m=c[2]), call(bits=c[1]), call(m=P(arena["s"])), call(bits=P(dm)), call(key=foreign.h),
+           call(m=P(dm) + 8), call(bits=P(dn) + 2), call(cs=[c[0] + 8, c[1], c[2]]), call(bt=0)]
+    assert all(rc == -1 for rc in bad), bad
+    arena.verify(inputs=("c0", "c1", "c2", "s"))
+    assert memcheck.is_poison(dm.download((batch, n))) and memcheck.is_poison(dn.download((batch,), np.uint32))
+    assert call() == 0
+    arena.verify(inputs=("c0", "c1", "c2", "s"))
+    assert np.array_equal(dn.download((batch,), np.uint32), wb) and np.array_equal(dm.download((batch, n)), wm)
+    assert e.workspace_bytes() == before
+    dm.poison()
+    assert call(cs=[c[0], c[1], c[2]], nc=2, bits=None) == 0                     # fewer components and no noise output: inside what was reserved
+    arena.verify(inputs=("c0", "c1", "c2", "s"))
+    _, _, wm2, _ = _case(oracle, n, moduli, batch, 2)
+    assert np.array_equal(dm.download((batch, n)), wm2) and e.workspace_bytes() == before
+    assert np.array_equal(dn.download((batch,), np.uint32), wb)                  # untouched by the call without a noise output
+
+
+@pytest.mark.gpu
+def test_a_modulus_product_of_256_bits_and_more_is_unsupported(pkg):
+    n, L = 2048, 5
+    moduli = _primes(60, n, L)
+    assert math.prod(moduli) >= 1 << 255
+    e = pkg.RnsNttEngine(n, moduli)
+    s = pkg.DeviceBuffer.from_numpy(rns_poly(1, moduli, n, 1)[0])
+    sk = e.import_secret_key(s)
+    c = [pkg.DeviceBuffer.from_numpy(rns_poly(2 + k, moduli, n, 1)) for k in range(2)]
+    dm = pkg.DeviceBuffer(n * 8); memcheck.poison(pkg, dm)
+    lib = pkg.lib(); P = pkg.capi._ptr
+    arr = (ctypes.c_void_p * 2)(P(c[0]), P(c[1]))
+    unsupported = -5                                                              # FHE_ERR_UNSUPPORTED
+    assert lib.fhe_ct_decrypt(e.h, sk.h, T, 1, P(dm), None, arr, 2, 1) == unsupported
+    assert b"2^255" in lib.fhe_hip_last_error()
+    assert lib.fhe_ct_decrypt_reserve(e.h, T, 2, 1) == unsupported
+    assert memcheck.is_poison(dm.download((n,)))
