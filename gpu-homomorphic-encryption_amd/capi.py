@@ -123,6 +123,8 @@ def lib():
         "fhe_secret_key_destroy": ([vp], ci),
         "fhe_ct_decrypt_reserve": ([vp, u64, u32, u32], ci),
         "fhe_ct_decrypt": ([vp, vp, u64, u64, vp, vp, P(vp), u32, u32], ci),
+        "fhe_keyswitch_keys_generate": ([vp, vp, u32, P(u32), u32, u64, ctypes.c_double, P(u64), P(vp)], ci),
+        "fhe_relin_keys_export": ([vp, vp, vp, vp], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -530,6 +532,20 @@ class RnsNttEngine:
         c0 + c1 s (+ c2 s^2) for the 2 or 3 device buffers in `components`."""
         comps = (ctypes.c_void_p * len(components))(*[_ptr(c) for c in components])
         _check(lib().fhe_ct_decrypt(self.h, sk.h, t, scale, _ptr(d_m), None if d_noise_bits is None else _ptr(d_noise_bits), comps, len(components), batch))
+
+    def generate_keyswitch_keys(self, sk, decomp_bits, elts, noise_scale, sigma, seeds):
+        """One key set per entry of `elts` (0: relinearisation key; odd g below 2n: Galois key of g), generated on the device from the secret
+        key `sk` with seeds = (a, e).  Returns the key-set objects, as import_relin_keys would for the same rows."""
+        k = len(elts)
+        ge = (ctypes.c_uint32 * max(k, 1))(*[int(g) for g in elts])
+        sd = (ctypes.c_uint64 * 2)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
+        outs = (ctypes.c_void_p * max(k, 1))()
+        _check(lib().fhe_keyswitch_keys_generate(self.h, sk.h, decomp_bits, ge, k, noise_scale, sigma, sd, outs))
+        return [RelinKeys(ctypes.c_void_p(outs[i])) for i in range(k)]
+
+    def export_keys(self, rk, d_keys_b, d_keys_a):
+        """The rows of any key set as [L*K][L][n] canonical containers in coefficient form (the inverse of import_relin_keys)."""
+        _check(lib().fhe_relin_keys_export(self.h, rk.h, _ptr(d_keys_b), _ptr(d_keys_a)))
 
     def check_canonical(self, d_data, batch=1):
         _check(lib().fhe_rns_check_canonical(self.h, _ptr(d_data), batch))

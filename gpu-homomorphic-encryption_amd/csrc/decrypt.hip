@@ -9,12 +9,6 @@
 #define FHE_DECRYPT_CRT_KERNELS
 #include "decrypt.hip.h"
 
-struct fhe_secret_key {
-    fhe_rns_ntt *owner = nullptr;
-    const void *src = nullptr;                      // what the key was imported from (outputs must not alias it)
-    void *d_s = nullptr;                            // s as given followed by s^2 = s (*) s: 2 x [L][n] containers, coefficient form (the composed path multiplies by these)
-    void *d_packed = nullptr;                       // fused path: (s^, s^ . s^), 2 x [L][n] residues, transformed and packed like one key row each
-};
 extern "C" int fhe_secret_key_destroy(fhe_secret_key_t *sk) {
     if (sk) {
         for (void *p : {sk->d_s, sk->d_packed}) if (p) (void)hipFree(p);

@@ -11,6 +11,8 @@
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
 //   keyswitch.hip   key import, relinearisation, multiply + relinearise, Galois, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
 //                   key / digit / monomial kernels of ntt_word.hip.h)
+//   keygen.hip      key-switching key generation and key export (fused: keygen.hip.h; composed path: the entry points of transforms.hip, sampling.hip
+//                   and keyswitch.hip with the small kernels of keygen.hip; the unpack kernel of ntt_word.hip.h)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once
@@ -69,6 +71,7 @@ inline unsigned ew_grid(size_t items) {
 struct EngineEnv {
     int force_width = 0;
     bool no_wide_lazy = false, no_wide_tiles = false;
+    bool no_fused_keygen = false;
     bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
          no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false, no_fused_decrypt = false,
          split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
@@ -133,6 +136,13 @@ struct fhe_relin_keys {
     uint32_t decomp_bits = 0, K = 0, num_keys = 0;
     void *d_kb = nullptr, *d_ka = nullptr;      // [num_keys][L][n] containers, NTT domain, canonical
     void *d_pkb = nullptr, *d_pka = nullptr;    // packed tables for the fused key-switch kernel (word-sized paths)
+};
+
+struct fhe_secret_key {                             // created by decrypt.hip; keygen.hip reads it
+    fhe_rns_ntt *owner = nullptr;
+    const void *src = nullptr;                      // what the key was imported from (outputs must not alias it)
+    void *d_s = nullptr;                            // s as given followed by s^2 = s (*) s: 2 x [L][n] containers, coefficient form (the composed paths multiply by these)
+    void *d_packed = nullptr;                       // fused paths: (s^, s^ . s^), 2 x [L][n] residues, transformed and packed like one key row each
 };
 
 // The one place that maps a word-sized width class to its field type: fn(F32{}) / fn(F52{}) / fn(F64{}) / fn(F64X{}), in the body
@@ -207,6 +217,7 @@ bool plan_fused_hoist(const fhe_rns_ntt *h, bool packed_keys);   // hoisted rota
 bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys); // hoisted linear transform on the LDS kernels of hoist_lincomb.hip.h (else the composed path)
 bool plan_fused_encrypt(const fhe_rns_ntt *h);                   // public-key encryption on the LDS kernel of encrypt.hip.h (else the composed path)
 bool plan_fused_decrypt(const fhe_rns_ntt *h);                   // secret-key decryption on the LDS kernel of decrypt.hip.h (else the composed path)
+bool plan_fused_keygen(const fhe_rns_ntt *h, bool packed_keys);  // key-switching key generation on the LDS kernel of keygen.hip.h (else the composed path)
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch);  // ... on the one-workgroup-per-ciphertext grid (else one per (ciphertext, limb))
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials
@@ -230,8 +241,18 @@ template <int OP> int do_ew(fhe_rns_ntt *h, void *r, const void *a, const void *
 int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0, const void *b1, uint32_t batch);
 int compact_poly(fhe_rns_ntt *h, void *out, const void *in, size_t containers);   // containers -> compact polynomials (word-sized classes)
 
+// ---- keyswitch.hip --------------------------------------------------------------------------------------------------------------
+uint32_t relin_digits(const fhe_rns_ntt *h, uint32_t decomp_bits);               // K of fhe_relin_num_digits
+bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K);   // whether such a key set gets packed tables, i.e. runs the fused kernels
+int pack_relin_keys(fhe_rns_ntt *h, fhe_relin_keys *rk);                         // allocates d_pkb / d_pka and packs d_kb / d_ka (NTT domain) into them
+int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what);   // odd and below 2n
+// sigma_g of one or two components (in1 == nullptr: one) into out0 / out1, zero_out (optional) cleared beside them; compact: residues out
+int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact);
+
 // ---- sampling.hip ---------------------------------------------------------------------------------------------------------------
 int ensure_cdt(fhe_rns_ntt *h, double sigma, const char *what);   // h->d_cdt / cdt_len = the cumulative table of sigma (uploaded when sigma changes)
+// fhe_rns_sample_uniform for the polynomials first_poly .. first_poly + polys - 1 of a stream (first_poly a multiple of L), into d_out[0 .. polys)
+int sample_uniform_from(fhe_rns_ntt *h, void *d_out, uint64_t seed, size_t first_poly, size_t polys);
 
 // ---- rns.hip --------------------------------------------------------------------------------------------------------------------
 int ensure_crt(fhe_rns_ntt *h);          // CrtLimb[L] (and Q, where it fits 255 bits) on first use

@@ -11,7 +11,7 @@
 // ------------------------------------------------------------------------------------------------------
 // relinearisation / key switching (general path: digit embedding -> batched forward NTT -> MAC -> inverse)
 // ------------------------------------------------------------------------------------------------------
-static uint32_t relin_digits(const fhe_rns_ntt *h, uint32_t w) {
+uint32_t relin_digits(const fhe_rns_ntt *h, uint32_t w) {
     int mx = 0;
     for (const U256 &q : h->moduli) mx = q.bit_length() > mx ? q.bit_length() : mx;
     return ((uint32_t)mx + w - 1) / w;
@@ -43,8 +43,10 @@ static int pack_relin_keys_t(fhe_rns_ntt *h, fhe_relin_keys *rk) {
     return post_launch(h->stream, "pack_keys_kernel");
 }
 
+int pack_relin_keys(fhe_rns_ntt *h, fhe_relin_keys *rk) { return with_word_field(h, [&](auto f) { return pack_relin_keys_t<decltype(f)>(h, rk); }); }
+
 // Whether a key set of K digits of decomp_bits bits gets packed tables, i.e. runs the fused kernels (fhe_ct_hoist asks before any key set is seen)
-static bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K) {
+bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K) {
     const size_t num_keys = (size_t)h->L * K;
     // The fused kernels feed a digit of limb j (< min(2^w, q_j)) straight into limb i's lazy forward transform, whose
     // integer butterflies accept inputs below 4*q_i; bases mixing very different prime sizes go through the general
@@ -99,7 +101,7 @@ extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, u
     int rc = do_forward(h, rk->d_kb, num_keys);
     if (!rc) rc = do_forward(h, rk->d_ka, num_keys);
     if (!rc && keys_get_packed(h, decomp_bits, K)) {
-        rc = with_word_field(h, [&](auto f) { return pack_relin_keys_t<decltype(f)>(h, rk); });
+        rc = pack_relin_keys(h, rk);
         if (!rc) {   // the fused kernels read only the packed tables (n * sizeof(E) bytes per key polynomial instead of n * 32): drop the
                      // container copy, so that a bootstrapping key of several hundred RGSW ciphertexts fits (hipFree waits for the packing)
             (void)hipFree(rk->d_kb); (void)hipFree(rk->d_ka);
@@ -321,7 +323,7 @@ extern "C" int fhe_galois_element(uint32_t n, int32_t steps, uint32_t *elt) {
     *elt = (uint32_t)r;
     return FHE_OK;
 }
-static int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what) {
+int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what) {
     if (!(g & 1) || g >= 2 * h->n)
         return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the Galois element must be odd and below 2n");
     return FHE_OK;
@@ -351,7 +353,7 @@ static int galois_word(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, c
     else hipLaunchKernelGGL((fhe_dev::galois_kernel<F, false>), grid, block, 0, h->stream, (V *)out0, (V *)out1, (V *)zero_out, (const V *)in0, (const V *)in1, limbs, h->L, h->log_n, g_inv, polys);
     return post_launch(h->stream, "galois_kernel");
 }
-static int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact) {
+int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact) {
     const uint32_t g_inv = galois_inverse(h, g);
     if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) { return galois_word<decltype(f)>(h, out0, out1, zero_out, in0, in1, g_inv, polys, compact); });
     if (compact) return fail(FHE_ERR_UNSUPPORTED, "compact polynomials exist on the word-sized classes only");

@@ -7,6 +7,7 @@
 #include "encrypt.hip.h"
 #include "hoist.hip.h"
 #include "hoist_lincomb.hip.h"
+#include "keygen.hip.h"
 #include "ntt_lds.hip.h"
 #include "ntt_lds_small.hip.h"
 
@@ -121,6 +122,16 @@ static bool launch(const LdsArgs &A) {
             if (in || !out || !A.r0 || !A.a0 || !A.a1 || !A.kb || (A.c2 && !A.ka) || A.polys % A.L) return false;
             hipLaunchKernelGGL((ntt_decrypt_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (E *)A.r0, (const char *)A.a0, (const char *)A.a1, (const char *)A.c2,
                                (const E *)A.kb, (const E *)A.ka, limbs, A.L);
+            return true;
+        }
+        return false;
+    }
+    // Key-switching key generation: nothing in but the kept secret key, the packed tables of every set out
+    if (A.op == LDS_KEYGEN) {
+        if constexpr (lds_keygen(EB, LOGN)) {
+            if (in || out || !A.a0 || !A.kb || !A.ka || !A.cdt || !A.cdt_len || A.cdt_len > ENCRYPT_MAX_CDT || !A.K || !A.w || A.polys % (A.L * A.K * A.L)) return false;
+            hipLaunchKernelGGL((ntt_keygen_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (const KeygenSet *)A.a0, (const E *)A.kb, (const E *)A.ka, A.cdt, A.cdt_len,
+                               A.seeds[0], A.seeds[1], A.t, limbs, A.L, A.K, A.w);
             return true;
         }
         return false;

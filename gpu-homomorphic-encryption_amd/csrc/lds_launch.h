@@ -11,11 +11,12 @@ namespace fhe_dev {
 // LDS_HOIST / LDS_HOIST_APPLY: hoisted rotations (hoist.hip.h), one form each.  LDS_HOIST_FWD / LDS_HOIST_LINCOMB: the two launches of the
 // hoisted linear transform (hoist_lincomb.hip.h), one form each.  LDS_ENCRYPT: public-key encryption with in-kernel sampling (encrypt.hip.h),
 // one kernel on two grids (LdsArgs::per_ct).  LDS_DECRYPT: the first launch of secret-key decryption (decrypt.hip.h), one form.
+// LDS_KEYGEN: key-switching key generation with in-kernel sampling (keygen.hip.h), one form.
 // The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
 // over the top stages and the sub-transforms of the 2^top blocks
 #define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
     X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") X(LDS_HOIST, "hoist") X(LDS_HOIST_APPLY, "hoisted rotation") \
-    X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") X(LDS_ENCRYPT, "encryption") X(LDS_DECRYPT, "decryption") \
+    X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") X(LDS_ENCRYPT, "encryption") X(LDS_DECRYPT, "decryption") X(LDS_KEYGEN, "key generation") \
     X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
 #define LDS_ENUMERATOR(id, name) id,
 #define LDS_NAME_CASE(id, name) case id: return name;
@@ -75,6 +76,9 @@ constexpr bool lds_encrypt(int elem_bytes, int log_n) { (void)elem_bytes; return
 // workgroups cap a thread at 128 VGPRs (the kernel parks 176 bytes per lane in scratch there): that size takes the composed path
 // (tests/test_decrypt.py compiles every instance and pins the budgets: no scratch anywhere)
 constexpr bool lds_decrypt(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
+// key-switching key generation (ntt_keygen_kernel: one live array, every draw in registers): the sizes of the encryption and decryption
+// kernels; N = 2^15 takes the composed path like them (tests/test_keygen.py compiles every instance and pins the budgets: no scratch anywhere)
+constexpr bool lds_keygen(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
 // entries of a cumulative Gaussian table the kernel stages in its exchange buffer (8 KiB: the buffer of the smallest instance); larger
 // tables (sigma > 85) take the composed path
 constexpr uint32_t ENCRYPT_MAX_CDT = 1024;
@@ -104,6 +108,13 @@ struct LincombTerm {
     const void *kb, *ka;                 // packed key tables of the term's key set (pack_keys_kernel)
     const void *pt;                      // the term's plaintext, transformed and packed like one key row: [L][n] residues
     uint32_t g, _pad;                    // Galois element (1 for a keyless term)
+};
+
+// One key set of a key-generation call (device table read by ntt_keygen_kernel): the set's packed tables and its Galois element
+// (0: the relinearisation key, target s^2)
+struct KeygenSet {
+    void *kb, *ka;
+    uint32_t g, _pad;
 };
 
 // One launch request.  The host fills the members that are operands of ITS op, by name (lds_args of engine.h sets the common ones from the
@@ -144,6 +155,8 @@ struct LdsArgs {
     bool per_ct = false;
     // LDS_DECRYPT: r0 = the decryption workspace ([polys][n] residues, compact) = a0 + a1 (*) s + c2 (*) s^2 limb-wise; a0, a1 = c0, c1 and c2 = c2 or
     // nullptr (containers); kb / ka = the packed transformed s and s^2 ([L][n] residues each); polys = ciphertexts x limbs, out_compact set
+    // LDS_KEYGEN: a0 = KeygenSet[polys / (L K L)] (device): both packed tables of every set are written; kb / ka = the packed transformed s and s^2;
+    // cdt / cdt_len as LDS_ENCRYPT; seeds[0], seeds[1] = the streams of a and e; t = the noise scale; polys = sets x rows x limbs
     const uint32_t *shifts = nullptr;    // LDS_EXTPROD: device array of per-ciphertext monomial exponents
     uint32_t K = 0, w = 0;
     uint32_t b_polys = 0;                // LDS_MULTIPLY: polynomials behind b0 (0 = as many as the batch; L = one RNS polynomial broadcast over the batch)

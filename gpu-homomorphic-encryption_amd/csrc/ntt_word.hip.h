@@ -97,6 +97,29 @@ pack_keys_kernel(typename F::E *__restrict__ packed, const typename F::V16 *__re
     }
 }
 
+// The inverse of pack_keys_kernel (fhe_relin_keys_export): packed tables -> [num_keys][L][n] canonical containers, NTT domain, natural
+// positions.  canon(pw_mul(entry, 1)) takes the 2^W off again (mul_const below); one half container per lane.
+template <class F>
+__global__ void __launch_bounds__(256)
+unpack_keys_kernel(typename F::V16 *__restrict__ keys_ntt, const typename F::E *__restrict__ packed, const Limb<F> *__restrict__ limbs,
+                   uint32_t L, uint32_t log_n, uint32_t num_keys) {
+    using E = typename F::E;
+    constexpr uint32_t VPL = 16 / sizeof(E);
+    const uint32_t n = 1u << log_n, T = n >> 5;
+    const size_t halves = (size_t)num_keys * L * n * 2, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < halves; g += stride) {
+        E o = 0;
+        if (!(g & 1)) {
+            const size_t c = g >> 1, poly = c >> log_n;
+            const uint32_t x = (uint32_t)(c & (n - 1)), tid = x >> 5, r = x & 31;
+            const Limb<F> &P = limbs[(uint32_t)(poly % L)];
+            const E v = packed[poly * n + ((size_t)(r / VPL) * T + tid) * VPL + r % VPL];
+            o = F::canon_inv(F::pw_mul(v, (E)1, P.q, P.qinv), P.q);
+        }
+        __builtin_nontemporal_store(F::pack(o), keys_ntt + g);
+    }
+}
+
 // ---- relinearisation building blocks (general path; the fused key-switch kernels are above) --------------------
 // Digit polynomials of c2 embedded in every limb: D[jk][b][i][x] = ((c2[b][j][x] >> (k*w)) & (2^w - 1)) mod q_i,
 // jk = j*K + k.  One 16-byte half container per lane.

@@ -95,10 +95,13 @@ extern "C" int fhe_rns_sample_uniform(fhe_rns_ntt_t *h, void *d_out, uint64_t se
     int rc = check_call(h, batch, "rns_sample_uniform"); if (rc) return rc;
     if (!d_out) return fail(FHE_ERR_INVALID_ARG, "rns_sample_uniform: null output");
     if ((rc = check_aligned({d_out}, "rns_sample_uniform"))) return rc;
-    if ((rc = ensure_crt(h))) return rc;
-    const size_t count = (size_t)batch * h->L * h->n;
+    return sample_uniform_from(h, d_out, seed, 0, (size_t)batch * h->L);
+}
+int sample_uniform_from(fhe_rns_ntt *h, void *d_out, uint64_t seed, size_t first_poly, size_t polys) {
+    if (int rc = ensure_crt(h)) return rc;
+    const size_t count = polys * h->n;
     hipLaunchKernelGGL(fhe_dev::sample_uniform_rns_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out,
-                       (const fhe_dev::CrtLimb *)h->d_crt, h->L, h->log_n, seed, count);
+                       (const fhe_dev::CrtLimb *)h->d_crt, h->L, h->log_n, seed, first_poly * h->n, count);
     return post_launch(h->stream, "sample_uniform_rns_kernel");
 }
 extern "C" int fhe_poly_mod_switch(void *d_r, const void *d_a, const uint64_t old_q[4], const uint64_t new_q[4], size_t count, void *stream) {

@@ -76,9 +76,10 @@ sample_small_kernel(u256 *__restrict__ out, const CrtLimb *__restrict__ limbs, u
 // Uniform residues in [0, q_l) by rejection on bit-length-masked draws (no modulo bias); one lane per container.
 // Draw t of element g uses words DRAW_UNIFORM + 4 t .. + 4 t + 3.  After 64 rejections (probability < 2^-64) the top bit is cleared.
 __global__ void __launch_bounds__(256)
-sample_uniform_rns_kernel(u256 *__restrict__ out, const CrtLimb *__restrict__ limbs, uint32_t L, uint32_t log_n, uint64_t seed, size_t count /* batch * L * n */) {
+sample_uniform_rns_kernel(u256 *__restrict__ out, const CrtLimb *__restrict__ limbs, uint32_t L, uint32_t log_n, uint64_t seed, size_t first, size_t count /* batch * L * n */) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < count; g += stride) {
+    for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < count; o += stride) {
+        const size_t g = first + o;                                     // element of the stream (first: a multiple of L n), written at out[o]
         const u256 q = limbs[(uint32_t)((g >> log_n) % L)].q;
         int top = 3; while (top > 0 && q.l[top] == 0) top--;
         const int bits = 64 - __builtin_clzll(q.l[top]);                // q != 0
@@ -91,7 +92,7 @@ sample_uniform_rns_kernel(u256 *__restrict__ out, const CrtLimb *__restrict__ li
             if (lt256(v, q)) break;
             if (t == 63) { v.l[top] &= mask >> 1; break; }
         }
-        store_u256(out + g, v);
+        store_u256(out + o, v);
     }
 }
 

@@ -202,6 +202,11 @@ bool plan_fused_encrypt(const fhe_rns_ntt *h) {
 bool plan_fused_decrypt(const fhe_rns_ntt *h) {
     return h->width != FHE_WIDTH_256 && !h->sub_top && h->log_n >= 11 && fhe_dev::lds_decrypt((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_decrypt;
 }
+// Key-switching key generation as the one launch of keygen.hip.h: every LDS-resident word-sized size whose instance has the kernel, for key
+// sets that get packed tables (the kernel writes nothing else)
+bool plan_fused_keygen(const fhe_rns_ntt *h, bool packed_keys) {
+    return packed_keys && h->width != FHE_WIDTH_256 && !h->sub_top && h->log_n >= 11 && fhe_dev::lds_keygen((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_keygen;
+}
 // ... one workgroup per ciphertext (draws once, loops over the limbs) from FHE_HIP_ENCRYPT_PER_CT_BATCH ciphertexts, below that one per
 // (ciphertext, limb): L times the workgroups for a device that the ciphertexts alone do not fill.  Same kernel, same bits.
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch) { return h->L > 1 && batch >= h->env.encrypt_per_ct_batch; }

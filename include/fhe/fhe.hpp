@@ -387,6 +387,54 @@ public:
         }
     }
 
+    // relinkey_gen / galoiskey_gen in ONE engine call each (fhe_keyswitch_keys_generate): a, e are drawn on the device with seeds from the
+    // context generator, noise scale t, sigma = security.sigma.  The generated handles ARE the level-0 import (nothing is imported again); the
+    // rows are read back with fhe_relin_keys_export, so that relin_keys_at / galois_keys_at slice lower levels as they do for host-made keys.
+    // relinkey_gen / galoiskey_gen themselves stay as they are.
+    void relinkey_gen_fused(RelinKeys &rlk, const SecretKey &sk, uint32_t decomp_bits = 16) {
+        const uint32_t zero = 0;
+        fhe_relin_keys_t *set = nullptr;
+        generate_key_sets(sk, decomp_bits, &zero, 1, &set);
+        for (PublicKey *k : rlk.rlk_keys) { if (k) { delete k->pk0; delete k->pk1; delete k; } }
+        rlk.rlk_keys.clear(); rlk.drop_levels(); fhe_relin_keys_destroy(rlk.imported);
+        rlk.decomp_bits = decomp_bits; rlk.imported = set; rlk.imported_for = params_.rns_ntt;
+        rows_from_export(rlk.rlk_keys, set, relin_levels(decomp_bits));
+    }
+    // every element of (steps, columns) that gal_keys does not hold yet, ALL in one call
+    void galoiskey_gen_fused(GaloisKeys &gal_keys, const SecretKey &sk, const std::vector<int> &steps, bool columns, uint32_t decomp_bits) {
+        if (!gal_keys.gal_keys.empty() && gal_keys.decomp_bits != decomp_bits)
+            throw std::runtime_error("FHEContext::galoiskey_gen_fused: the key set already holds keys of another digit width");
+        std::vector<uint32_t> want, elts;
+        for (int st : steps) want.push_back(galois_element(st));
+        if (columns) want.push_back(column_element());
+        for (uint32_t g : want)
+            if (std::find(gal_keys.elements.begin(), gal_keys.elements.end(), g) == gal_keys.elements.end() && std::find(elts.begin(), elts.end(), g) == elts.end())
+                elts.push_back(g);
+        gal_keys.decomp_bits = decomp_bits;
+        if (elts.empty()) return;
+        import_galois_keys(gal_keys);                                                       // what it already holds (host-made rows), before the new handles join
+        std::vector<fhe_relin_keys_t *> sets(elts.size(), nullptr);
+        generate_key_sets(sk, decomp_bits, elts.data(), (uint32_t)elts.size(), sets.data());
+        std::vector<PublicKey *> rows;
+        try {
+            for (fhe_relin_keys_t *set : sets) rows_from_export(rows, set, relin_levels(decomp_bits));
+        } catch (...) {
+            for (fhe_relin_keys_t *set : sets) fhe_relin_keys_destroy(set);
+            for (PublicKey *k : rows) { delete k->pk0; delete k->pk1; delete k; }
+            throw;
+        }
+        gal_keys.drop_levels();
+        gal_keys.gal_keys.insert(gal_keys.gal_keys.end(), rows.begin(), rows.end());
+        gal_keys.imported.insert(gal_keys.imported.end(), sets.begin(), sets.end());
+        gal_keys.elements.insert(gal_keys.elements.end(), elts.begin(), elts.end());
+        gal_keys.imported_for = params_.rns_ntt;
+    }
+    void galoiskey_gen_fused(GaloisKeys &gal_keys, const SecretKey &sk) {                   // the default set of galoiskey_gen
+        std::vector<int> steps;
+        for (uint32_t s = 1; s < params_.n / 2; s <<= 1) { steps.push_back((int)s); steps.push_back(-(int)s); }
+        galoiskey_gen_fused(gal_keys, sk, steps, true, 16);
+    }
+
     // result = sigma_g(ct), key-switched back to s (one fhe_ct_apply_galois call); `result` may be `ct`.
     void apply_galois(Ciphertext &result, const Ciphertext &ct, uint32_t galois_elt, const GaloisKeys &gal_keys) {
         if (ct.components.size() != 2) throw std::runtime_error("FHEContext::apply_galois: 2-component ciphertext expected (relinearize first)");
@@ -711,6 +759,28 @@ private:
             sk.imported[level].reset(k, [](fhe_secret_key_t *p) { fhe_secret_key_destroy(p); });
         }
         return sk.imported[level].get();
+    }
+    // one fhe_keyswitch_keys_generate on the top-level engine: noise scale t, sigma = security.sigma, seeds from the context generator
+    void generate_key_sets(const SecretKey &sk, uint32_t decomp_bits, const uint32_t *elts, uint32_t num_sets, fhe_relin_keys_t **sets) {
+        const uint64_t seeds[2] = {rng_(), rng_()};
+        check(fhe_keyswitch_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, elts, num_sets, params_.t, (double)params_.security.sigma,
+                                          seeds, sets), "FHEContext: key-switching key generation");
+    }
+    // appends the `levels` rows of a key set to `rows` as coefficient-form polynomials (fhe_relin_keys_export)
+    void rows_from_export(std::vector<PublicKey *> &rows, const fhe_relin_keys_t *set, uint32_t levels) {
+        const size_t poly = (size_t)num_levels() * params_.n;
+        uint256_t *d = device_alloc(2 * poly * levels);
+        try {
+            check(fhe_relin_keys_export(params_.rns_ntt->handle(), set, d, d + poly * levels), "FHEContext: key export");
+            for (uint32_t r = 0; r < levels; r++) {
+                PublicKey *key = new PublicKey{new_polynomial(), new_polynomial()};
+                rows.push_back(key);
+                check(fhe_hip_memcpy_d2d(key->pk0->coeffs, d + poly * r, poly * sizeof(uint256_t)), "memcpy d2d");
+                check(fhe_hip_memcpy_d2d(key->pk1->coeffs, d + poly * (levels + r), poly * sizeof(uint256_t)), "memcpy d2d");
+            }
+            device_synchronize();
+        } catch (...) { device_free(d); throw; }
+        device_free(d);
     }
     // one fhe_ct_decrypt of ct at its level; m (n values) and / or noise_bits may be null
     void run_decrypt(const Ciphertext &ct, const SecretKey &sk, uint64_t *m, uint32_t *noise_bits) {

@@ -486,6 +486,36 @@ int fhe_poly_mod_switch(void *d_r, const void *d_a, const uint64_t old_q[4], con
  * data[i] = sub_mod(data[i], data[i + n]) for i < n (the upper half is left unchanged). */
 int fhe_negacyclic_reduce(void *d_data, const uint64_t q[4], size_t n, void *stream);
 
+/* ---- key-switching key generation as one call; key export ---------------------------------------------------------------------------
+ * FHEContext::relinkey_gen (src/fhe.cu:76-111) and galoiskey_gen (include/fhe.cuh:86) on the device: num_sets key sets from one call.
+ * galois_elts[e] == 0 asks for a relinearisation key (target s (*) s, what fhe_secret_key_create keeps); an odd g in [1, 2n) for the Galois
+ * key of g (target sigma_g(s), what fhe_rns_automorphism gives).  With K = fhe_relin_num_digits, row r = j K + k of set e, polynomial index
+ * P = e L K + r, limb l, position x:
+ *     U_P[l][x]  the uniform residue that fhe_rns_sample_uniform(h, ., seeds[0], num_sets L K) writes at element (P L + l) n + x, taken AS THE
+ *                NTT-DOMAIN VALUE of a: a^_P = U_P, a_P = fhe_rns_ntt_inverse(U_P)  (a uniform polynomial is uniform in either domain; one
+ *                forward transform per limb polynomial is saved)
+ *     e_P[x]     what fhe_rns_sample_gaussian(h, ., sigma, seeds[1], num_sets L K) writes at element P n + x, the same small integer in every limb
+ *     b_P[l]     = -a_P[l] (*) s[l] + [noise_scale e_P]_{q_l} + (l == j ? (2^(k w) mod q_j) target[j] : 0), canonical
+ * out_sets[e] is the handle fhe_relin_keys_create would return for the rows (b_P, a_P) of set e: the same bits in the same tables (packed
+ * tables where the import packs, NTT-domain containers otherwise), accepted unchanged by every consumer.  All arithmetic is exact: the result
+ * is a function of (s, decomp_bits, elements, noise_scale, sigma, seeds) only, never of the path or the launch shape.  The same element may
+ * appear more than once (different rows of the streams: different keys for the same target).
+ *
+ * On the LDS-resident word-sized sizes, N = 2^11 .. 2^14, with key sets that get packed tables, a secret key that has its packed transforms
+ * and sigma <= 85, the call is ONE launch, one workgroup per (set, row, limb), which draws e and U in registers and writes both packed rows;
+ * Galois targets are gathered in the kernel from the transform of s.  Elsewhere (full-width class, N >= 2^15, sizes below 2^11, unpacked
+ * key sets, sigma > 85, FHE_HIP_NO_FUSED_KEYGEN=1) the library composes the samplers, the transforms and element-wise kernels, one key set
+ * at a time, through scratch of (L K + 2) S bytes that it frees before it returns.  The keys are complete when the call returns.
+ *
+ * FHE_ERR_INVALID_ARG with nothing launched, nothing allocated and every out_sets[i] untouched: a null argument; a key of another engine;
+ * num_sets == 0; an even element or one not below 2n; decomp_bits outside [1, 64]; noise_scale == 0; a sigma fhe_gaussian_cdt rejects;
+ * ceil(12 sigma) not below the smallest modulus.  On a failure after that every handle made so far is destroyed and every out_sets[i] is NULL. */
+int fhe_keyswitch_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t decomp_bits, const uint32_t *galois_elts, uint32_t num_sets,
+                                uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_relin_keys_t **out_sets);
+/* The inverse of fhe_relin_keys_create for ANY key set of h, however it was made: d_keys_b / d_keys_a receive its rows as
+ * [num_keys][L][n] canonical containers in coefficient form (num_keys = L K; packed sets are unpacked first).  Outputs must be distinct. */
+int fhe_relin_keys_export(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_keys_b, void *d_keys_a);
+
 /* Scan a [batch][L][n] buffer for coefficients that are not canonical (>= q_limb, or non-zero
  * upper limbs on the narrow paths).  Synchronises.  FHE_OK or FHE_ERR_NONCANONICAL. */
 int fhe_rns_check_canonical(fhe_rns_ntt_t *h, const void *d_data, uint32_t batch);
