@@ -125,6 +125,14 @@ def lib():
         "fhe_ct_decrypt": ([vp, vp, u64, u64, vp, vp, P(vp), u32, u32], ci),
         "fhe_keyswitch_keys_generate": ([vp, vp, u32, P(u32), u32, u64, ctypes.c_double, P(u64), P(vp)], ci),
         "fhe_relin_keys_export": ([vp, vp, vp, vp], ci),
+        "fhe_batch_encoder_create": ([vp, P(vp), u64, ci], ci),
+        "fhe_batch_encoder_destroy": ([vp], ci),
+        "fhe_batch_encoder_reserve": ([vp, vp, u32], ci),
+        "fhe_batch_encoder_scratch_bytes": ([vp, P(u64)], ci),
+        "fhe_batch_encoder_slot_table": ([u32, ci, P(u32)], ci),
+        "fhe_slots_encode": ([vp, vp, vp, vp, u32], ci),
+        "fhe_slots_decode": ([vp, vp, vp, vp, u32], ci),
+        "fhe_slots_decode_poly": ([vp, vp, vp, vp, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -621,6 +629,56 @@ class SecretKey:
     def close(self):
         if self.h:
             lib().fhe_secret_key_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SLOTS_NATURAL, SLOTS_ROWS = 0, 1
+
+
+def slot_table(n, order):
+    """The encoder's table, position of the NTT domain -> slot index, built on the host (no device needed): numpy uint32 [n]."""
+    out = np.zeros(n, dtype=np.uint32)
+    _check(lib().fhe_batch_encoder_slot_table(n, order, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+    return out
+
+
+class BatchEncoder:
+    """Slot values <-> plaintext polynomials of the engine `eng` for the plaintext modulus t (a prime = 1 mod 2n), on the device."""
+
+    def __init__(self, eng, t, order=SLOTS_NATURAL):
+        self.h = None
+        self.eng = eng
+        out = ctypes.c_void_p()
+        _check(lib().fhe_batch_encoder_create(eng.h, ctypes.byref(out), t, order))
+        self.h = out
+
+    def reserve(self, batch):
+        """Pre-size the encoder's scratch for up to `batch` plaintexts: afterwards no call allocates."""
+        _check(lib().fhe_batch_encoder_reserve(self.eng.h, self.h, batch))
+
+    def scratch_bytes(self):
+        b = ctypes.c_uint64(0); _check(lib().fhe_batch_encoder_scratch_bytes(self.h, ctypes.byref(b))); return b.value
+
+    def encode(self, d_out, d_values, batch=1):
+        """d_out[b][l][x] = m_b[x] mod q_l ([batch][L][n] containers) for the [batch][n] uint64 slot values below t in d_values."""
+        _check(lib().fhe_slots_encode(self.eng.h, self.h, _ptr(d_out), _ptr(d_values), batch))
+
+    def decode(self, d_values, d_m, batch=1):
+        """d_values[b][i] = m_b at slot i, for [batch][n] uint64 coefficients below t in d_m (what decrypt writes); d_values may be d_m."""
+        _check(lib().fhe_slots_decode(self.eng.h, self.h, _ptr(d_values), _ptr(d_m), batch))
+
+    def decode_poly(self, d_values, d_poly, batch=1):
+        """The same from [batch][L][n] containers (limb 0 is read)."""
+        _check(lib().fhe_slots_decode_poly(self.eng.h, self.h, _ptr(d_values), _ptr(d_poly), batch))
+
+    def close(self):
+        if self.h:
+            lib().fhe_batch_encoder_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -13,6 +13,8 @@
 //                   key / digit / monomial kernels of ntt_word.hip.h)
 //   keygen.hip      key-switching key generation and key export (fused: keygen.hip.h; composed path: the entry points of transforms.hip, sampling.hip
 //                   and keyswitch.hip with the small kernels of keygen.hip; the unpack kernel of ntt_word.hip.h)
+//   encode.hip      batch encoder: slots <-> plaintexts (fused: encode.hip.h on the engine of the plaintext modulus; composed path: the small
+//                   kernels of encode.hip.h around do_inverse / do_forward)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once
@@ -73,7 +75,7 @@ struct EngineEnv {
     bool no_wide_lazy = false, no_wide_tiles = false;
     bool no_fused_keygen = false;
     bool no_square = false, single_transforms = false, global_twiddles = false, no_fused_keyswitch = false, no_word_conversions = false,
-         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false, no_fused_decrypt = false,
+         no_fused_blind_rotate = false, no_fused_ct_relin = false, no_compact_blind_rotate = false, no_two_launch_ct = false, no_fused_galois = false, no_fused_hoist = false, no_fused_encrypt = false, no_fused_decrypt = false, no_fused_encode = false,
          split_keyswitch = false, relin_chunks_forced = false, no_prerotation = false, no_c2_compaction = false, check_inputs = false;
     uint32_t small_batch_polys = 256, coop_polys = 64, split_pairs_polys = 128, overlap_chunks = 4;
     uint32_t encrypt_per_ct_batch = 256; // fhe_ct_encrypt of at least this many ciphertexts runs one workgroup per ciphertext (plan_encrypt)
@@ -218,6 +220,7 @@ bool plan_fused_lincomb(const fhe_rns_ntt *h, bool packed_keys); // hoisted line
 bool plan_fused_encrypt(const fhe_rns_ntt *h);                   // public-key encryption on the LDS kernel of encrypt.hip.h (else the composed path)
 bool plan_fused_decrypt(const fhe_rns_ntt *h);                   // secret-key decryption on the LDS kernel of decrypt.hip.h (else the composed path)
 bool plan_fused_keygen(const fhe_rns_ntt *h, bool packed_keys);  // key-switching key generation on the LDS kernel of keygen.hip.h (else the composed path)
+bool plan_fused_slots(const fhe_rns_ntt *te);                    // batch encoder on the LDS kernels of encode.hip.h; te = the encoder's engine on (n, t) (else the composed path)
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch);  // ... on the one-workgroup-per-ciphertext grid (else one per (ciphertext, limb))
 // What a call of `batch` units needs (K digits; packed: the key set has packed tables, i.e. runs the fused kernels); the last four: keyswitch.hip
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys);                       // forward / inverse of `polys` limb polynomials

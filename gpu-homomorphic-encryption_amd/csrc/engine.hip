@@ -204,6 +204,7 @@ static EngineEnv read_env() {
     e.no_fused_hoist = set("FHE_HIP_NO_FUSED_HOIST");                                  // hoisted rotations on the composed path everywhere (cross-check); key import is unchanged
     e.no_fused_encrypt = set("FHE_HIP_NO_FUSED_ENCRYPT");                              // fhe_ct_encrypt on the composed path everywhere (cross-check); read when a public key is imported too
     e.no_fused_decrypt = set("FHE_HIP_NO_FUSED_DECRYPT");                              // fhe_ct_decrypt on the composed path everywhere (cross-check); read when a secret key is imported too
+    e.no_fused_encode = set("FHE_HIP_NO_FUSED_ENCODE");                                // fhe_slots_encode / fhe_slots_decode on the composed path everywhere (cross-check); read when an encoder is created
     e.no_fused_keygen = set("FHE_HIP_NO_FUSED_KEYGEN");                                // fhe_keyswitch_keys_generate on the composed path everywhere (cross-check)
     e.encrypt_per_ct_batch = num("FHE_HIP_ENCRYPT_PER_CT_BATCH", 256, 0, LONG_MAX); // fused fhe_ct_encrypt of at least this many ciphertexts: one workgroup per ciphertext, sampling once (0 = always)
     e.split_keyswitch = set("FHE_HIP_SPLIT_KEYSWITCH");

@@ -4,6 +4,7 @@
 #include <type_traits>
 #include "lds_launch.h"
 #include "decrypt.hip.h"
+#include "encode.hip.h"
 #include "encrypt.hip.h"
 #include "hoist.hip.h"
 #include "hoist_lincomb.hip.h"
@@ -132,6 +133,25 @@ static bool launch(const LdsArgs &A) {
             if (in || out || !A.a0 || !A.kb || !A.ka || !A.cdt || !A.cdt_len || A.cdt_len > ENCRYPT_MAX_CDT || !A.K || !A.w || A.polys % (A.L * A.K * A.L)) return false;
             hipLaunchKernelGGL((ntt_keygen_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (const KeygenSet *)A.a0, (const E *)A.kb, (const E *)A.ka, A.cdt, A.cdt_len,
                                A.seeds[0], A.seeds[1], A.t, limbs, A.L, A.K, A.w);
+            return true;
+        }
+        return false;
+    }
+    // Batch encoder: this instance is the field of the plaintext modulus; slot words in, containers out / words or containers in, slot words out
+    if (A.op == LDS_SLOTS_ENCODE || A.op == LDS_SLOTS_DECODE) {
+        if constexpr (lds_slots(EB, LOGN)) {
+            if (!A.r0 || !A.a0 || !A.kb || !A.L) return false;
+            if (A.op == LDS_SLOTS_ENCODE) {
+                if (!in || out || !A.ka) return false;
+                hipLaunchKernelGGL((ntt_slots_encode_kernel<F, LOGN>), grid, block, 0, A.stream, (char *)A.r0, (const uint64_t *)A.a0, (const uint32_t *)A.kb,
+                                   (const fhe_host::ModT *)A.ka, limbs, A.L);
+            } else {
+                if (!out) return false;
+                with_bools([&](auto IN) {
+                    hipLaunchKernelGGL((ntt_slots_decode_kernel<F, LOGN, !decltype(IN)::value>), grid, block, 0, A.stream, (uint64_t *)A.r0, (const char *)A.a0,
+                                       (const uint32_t *)A.kb, limbs, A.L);
+                }, in);
+            }
             return true;
         }
         return false;

@@ -12,11 +12,13 @@ namespace fhe_dev {
 // hoisted linear transform (hoist_lincomb.hip.h), one form each.  LDS_ENCRYPT: public-key encryption with in-kernel sampling (encrypt.hip.h),
 // one kernel on two grids (LdsArgs::per_ct).  LDS_DECRYPT: the first launch of secret-key decryption (decrypt.hip.h), one form.
 // LDS_KEYGEN: key-switching key generation with in-kernel sampling (keygen.hip.h), one form.
+// LDS_SLOTS_ENCODE / LDS_SLOTS_DECODE: the batch encoder (encode.hip.h), one form each, on the instance of the PLAINTEXT modulus' field.
 // The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
 // over the top stages and the sub-transforms of the 2^top blocks
 #define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
     X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") X(LDS_HOIST, "hoist") X(LDS_HOIST_APPLY, "hoisted rotation") \
     X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") X(LDS_ENCRYPT, "encryption") X(LDS_DECRYPT, "decryption") X(LDS_KEYGEN, "key generation") \
+    X(LDS_SLOTS_ENCODE, "slot encoding") X(LDS_SLOTS_DECODE, "slot decoding") \
     X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
 #define LDS_ENUMERATOR(id, name) id,
 #define LDS_NAME_CASE(id, name) case id: return name;
@@ -79,6 +81,10 @@ constexpr bool lds_decrypt(int elem_bytes, int log_n) { (void)elem_bytes; return
 // key-switching key generation (ntt_keygen_kernel: one live array, every draw in registers): the sizes of the encryption and decryption
 // kernels; N = 2^15 takes the composed path like them (tests/test_keygen.py compiles every instance and pins the budgets: no scratch anywhere)
 constexpr bool lds_keygen(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
+// batch encoder (ntt_slots_encode_kernel / ntt_slots_decode_kernel: one live array, no scratch anywhere): the sizes of the encryption,
+// decryption and key-generation kernels, which it feeds and drains; N = 2^15 takes the composed path like them (tests/test_batch_encoder.py
+// compiles every instance and pins the budgets)
+constexpr bool lds_slots(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
 // entries of a cumulative Gaussian table the kernel stages in its exchange buffer (8 KiB: the buffer of the smallest instance); larger
 // tables (sigma > 85) take the composed path
 constexpr uint32_t ENCRYPT_MAX_CDT = 1024;
@@ -157,6 +163,11 @@ struct LdsArgs {
     // nullptr (containers); kb / ka = the packed transformed s and s^2 ([L][n] residues each); polys = ciphertexts x limbs, out_compact set
     // LDS_KEYGEN: a0 = KeygenSet[polys / (L K L)] (device): both packed tables of every set are written; kb / ka = the packed transformed s and s^2;
     // cdt / cdt_len as LDS_ENCRYPT; seeds[0], seeds[1] = the streams of a and e; t = the noise scale; polys = sets x rows x limbs
+    // LDS_SLOTS_ENCODE: r0 = [polys][L][n] containers = the plaintexts of a0 = [polys][n] slot values (8-byte words: in_compact set); kb = the
+    // position -> slot table (uint32_t[n]), ka = ModT[L], the reduction modulo the target's q_l (t == 0: none); limbs = the ONE limb of the
+    // encoder's engine on (n, t); L = limbs of the TARGET engine; polys = plaintexts
+    // LDS_SLOTS_DECODE: r0 = [polys][n] slot values (8-byte words: out_compact set) of a0 = [polys][n] 8-byte words (in_compact) or limb 0 of
+    // [polys][L][n] containers; kb, limbs, L, polys as for LDS_SLOTS_ENCODE.  r0 == a0 is allowed for 8-byte words
     const uint32_t *shifts = nullptr;    // LDS_EXTPROD: device array of per-ciphertext monomial exponents
     uint32_t K = 0, w = 0;
     uint32_t b_polys = 0;                // LDS_MULTIPLY: polynomials behind b0 (0 = as many as the batch; L = one RNS polynomial broadcast over the batch)

@@ -207,6 +207,10 @@ bool plan_fused_decrypt(const fhe_rns_ntt *h) {
 bool plan_fused_keygen(const fhe_rns_ntt *h, bool packed_keys) {
     return packed_keys && h->width != FHE_WIDTH_256 && !h->sub_top && h->log_n >= 11 && fhe_dev::lds_keygen((int)residue_bytes(h), (int)h->log_n) && !h->env.no_fused_keygen;
 }
+// The batch encoder as one launch of encode.hip.h: te is the encoder's one-limb engine on (n, t), whose field the kernels run on
+bool plan_fused_slots(const fhe_rns_ntt *te) {
+    return te->width != FHE_WIDTH_256 && !te->sub_top && te->log_n >= 11 && fhe_dev::lds_slots((int)residue_bytes(te), (int)te->log_n) && !te->env.no_fused_encode;
+}
 // ... one workgroup per ciphertext (draws once, loops over the limbs) from FHE_HIP_ENCRYPT_PER_CT_BATCH ciphertexts, below that one per
 // (ciphertext, limb): L times the workgroups for a device that the ciphertexts alone do not fill.  Same kernel, same bits.
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch) { return h->L > 1 && batch >= h->env.encrypt_per_ct_batch; }

@@ -643,6 +643,76 @@ public:
         slot_transform(values, false);
     }
 
+    // encode / decode on the device (fhe_slots_encode / fhe_slots_decode_poly): the n values go up as 8-byte words and the [L][n] plaintext is
+    // written there once.  Natural slot order: equal to encode / decode value for value; encode and decode themselves stay as they are.
+    void encode_fused(Plaintext &pt, const std::vector<uint64_t> &values) { encode_slots(pt, values, FHE_SLOTS_NATURAL); }
+    void decode_fused(std::vector<uint64_t> &values, const Plaintext &pt) { decode_slots(values, pt, FHE_SLOTS_NATURAL); }
+    // decrypt_fused and decode_fused chained on the device: fhe_ct_decrypt writes the n coefficients, fhe_slots_decode turns them into the
+    // slot values in place, n 8-byte words come back
+    void decrypt_decode_fused(std::vector<uint64_t> &values, const Ciphertext &ct, const SecretKey &sk) { decrypt_decode_slots(values, ct, sk, FHE_SLOTS_NATURAL); }
+
+private:
+    friend class BatchEncoder;                               // the row order of the same three
+    // the three above in either slot order (fhe_slot_order)
+    void encode_slots(Plaintext &pt, const std::vector<uint64_t> &values, int order) {
+        const uint32_t n = params_.n; const uint64_t t = params_.t;
+        std::vector<uint64_t> v(n, 0);
+        for (size_t i = 0; i < values.size() && i < n; i++) v[i] = values[i] % t;
+        if (!pt.poly) pt.poly = new_polynomial();
+        const uint32_t level = num_levels() - pt.poly->num_limbs;
+        uint256_t *d_v = device_alloc(slot_words());
+        try {
+            check(fhe_hip_memcpy_h2d(d_v, v.data(), (size_t)n * sizeof(uint64_t)), "encode_fused: upload");
+            check(fhe_slots_encode(engine(level).handle(), encoder_at(level, order), pt.poly->coeffs, reinterpret_cast<const uint64_t *>(d_v), 1), "encode_fused");
+            device_synchronize();
+        } catch (...) { device_free(d_v); throw; }
+        device_free(d_v);
+        pt.is_ntt_form = false;
+    }
+    void decode_slots(std::vector<uint64_t> &values, const Plaintext &pt, int order) {
+        const uint32_t n = params_.n, level = num_levels() - pt.poly->num_limbs;
+        uint256_t *d_v = device_alloc(slot_words());
+        values.assign(n, 0);
+        try {
+            check(fhe_slots_decode_poly(engine(level).handle(), encoder_at(level, order), reinterpret_cast<uint64_t *>(d_v), pt.poly->coeffs, 1), "decode_fused");
+            device_synchronize();
+            check(fhe_hip_memcpy_d2h(values.data(), d_v, (size_t)n * sizeof(uint64_t)), "decode_fused: download");
+        } catch (...) { device_free(d_v); throw; }
+        device_free(d_v);
+    }
+    void decrypt_decode_slots(std::vector<uint64_t> &values, const Ciphertext &ct, const SecretKey &sk, int order) {
+        const uint32_t n = params_.n, Ll = num_levels() - ct.level;
+        if (ct.components.size() != 2 && ct.components.size() != 3) throw std::runtime_error("FHEContext: a ciphertext of 2 or 3 components is needed");
+        for (const Polynomial *c : ct.components)
+            if (c->num_limbs != Ll) throw std::runtime_error("FHEContext: ciphertext components do not have the limbs of its level");
+        const fhe_secret_key_t *key = secret_key_at(sk, ct.level);
+        std::vector<const uint256_t *> comps;
+        for (const Polynomial *c : ct.components) comps.push_back(c->coeffs);
+        uint256_t *d_v = device_alloc(slot_words());
+        uint64_t *d_m = reinterpret_cast<uint64_t *>(d_v);
+        values.assign(n, 0);
+        try {
+            engine(ct.level).decrypt(key, params_.t, inv_mod_t(ct.correction), d_m, nullptr, comps.data(), (uint32_t)comps.size());
+            check(fhe_slots_decode(engine(ct.level).handle(), encoder_at(ct.level, order), d_m, d_m, 1), "decrypt_decode_fused");
+            device_synchronize();
+            check(fhe_hip_memcpy_d2h(values.data(), d_v, (size_t)n * sizeof(uint64_t)), "decrypt_decode_fused: download");
+        } catch (...) { device_free(d_v); throw; }
+        device_free(d_v);
+    }
+    // the encoder of (level, order), created on first use and kept
+    const fhe_batch_encoder_t *encoder_at(uint32_t level, int order) {
+        if (order != FHE_SLOTS_NATURAL && order != FHE_SLOTS_ROWS) throw std::runtime_error("FHEContext: unknown slot order");
+        if (encoders_.size() < 2 * (size_t)num_levels()) encoders_.resize(2 * (size_t)num_levels());
+        std::shared_ptr<fhe_batch_encoder_t> &e = encoders_[2 * (size_t)level + (size_t)order];
+        if (!e) {
+            fhe_batch_encoder_t *p = nullptr;
+            check(fhe_batch_encoder_create(engine(level).handle(), &p, params_.t, order), "FHEContext: batch encoder (t must be a prime = 1 mod 2n)");
+            e.reset(p, [](fhe_batch_encoder_t *q) { fhe_batch_encoder_destroy(q); });
+        }
+        return e.get();
+    }
+
+public:
     void encrypt(Ciphertext &ct, const Plaintext &pt, const PublicKey &pk) {               // src/fhe.cu:138-169
         ensure_components(ct, 2, 0);
         RNS_NTTEngine &E = *params_.rns_ntt;
@@ -725,6 +795,8 @@ private:
     std::mt19937_64 rng_{0x5EED0000ull};
     bool device_sampling_ = false;
     std::vector<std::unique_ptr<RNS_NTTEngine>> level_engines_;   // index = level; entry 0 unused (params_.rns_ntt)
+    std::vector<std::shared_ptr<fhe_batch_encoder_t>> encoders_;  // index = 2 level + slot order (encoder_at)
+    size_t slot_words() const { return ((size_t)params_.n * sizeof(uint64_t) + sizeof(uint256_t) - 1) / sizeof(uint256_t); }   // n 8-byte words in containers
 
     // c0 + c1*s (+ c2*s^2) of a ciphertext at its level as integers in [0, Q_l); Q = Q_l and half = floor(Q_l / 2) as 256-bit integers
     std::vector<uint256_t> decrypt_values(const Ciphertext &ct, const SecretKey &sk, uint64_t Q[4], uint64_t half[4]) {
@@ -979,6 +1051,21 @@ private:
         for (Polynomial *&p : ct.components) if (p->num_limbs != limbs) { delete p; p = new_polynomial(level); }
         while (ct.components.size() < num) ct.components.push_back(new_polynomial(level));   // the reference `new`s and never frees (src/fhe.cu:202-205)
     }
+};
+
+// include/fhe.cuh:150-157 (the reference's is a passthrough, src/fhe.cu:267-279): slots in the ROW order of the Galois section -- two rows of
+// n / 2, rotate_rows shifts both cyclically, rotate_columns swaps them -- encoded and decoded on the device (fhe_slots_encode /
+// fhe_slots_decode_poly).  The context is not const: it keeps the encoders.
+class BatchEncoder {
+public:
+    explicit BatchEncoder(FHEContext &context) : ctx_(context), slot_count_(context.params().n) {}
+    void encode(Plaintext &pt, const std::vector<uint64_t> &values) { ctx_.encode_slots(pt, values, FHE_SLOTS_ROWS); }
+    void decode(std::vector<uint64_t> &values, const Plaintext &pt) { ctx_.decode_slots(values, pt, FHE_SLOTS_ROWS); }
+    uint32_t slot_count() const { return slot_count_; }
+
+private:
+    FHEContext &ctx_;
+    uint32_t slot_count_;
 };
 
 }  // namespace fhe

@@ -516,6 +516,44 @@ int fhe_keyswitch_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, ui
  * [num_keys][L][n] canonical containers in coefficient form (num_keys = L K; packed sets are unpacked first).  Outputs must be distinct. */
 int fhe_relin_keys_export(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_keys_b, void *d_keys_a);
 
+/* ---- batch encoder: slot values <-> plaintext polynomials on the device --------------------------------------------------------------
+ * FHEContext::encode / decode and BatchEncoder (include/fhe.cuh:89-90, 150-157).  With psi = fhe_find_psi(n, t) and e(i) the exponent of slot i:
+ *   FHE_SLOTS_NATURAL  e(i) = 2 i + 1                                          (what the mirror's host encode / decode evaluate)
+ *   FHE_SLOTS_ROWS     e(k) = 3^k mod 2n, e(n/2 + k) = 2n - e(k), k < n/2      (the order of the Galois section above: rotate_rows(r) is a
+ *                      cyclic left shift by r of both halves, rotate_columns swaps the halves)
+ * encode       d_values is [batch][n] uint64_t, each below t (canonical, like every data input).  m_b is the polynomial of degree < n over Z_t
+ *              with m_b(psi^e(i)) = values[b][i]; d_out[b][l][x] = m_b[x] mod q_l as canonical containers, [batch][L][n]: the d_m of
+ *              fhe_ct_encrypt, and one [L][n] slice is a plaintext of fhe_linear_transform_create.  Where t <= q_l the residue is m itself,
+ *              where t > q_l it is reduced (division-free, one table entry per limb prepared at creation).
+ * decode       d_m is [batch][n] uint64_t below t, what fhe_ct_decrypt writes; values[b][i] = m_b(psi^e(i)) mod t.  d_values == d_m is allowed.
+ * decode_poly  the same from [batch][L][n] containers, reading limb 0; FHE_ERR_UNSUPPORTED when t > q_0 (the residue is then not m).
+ * All arithmetic is exact: the result is a function of (t, n, order, inputs) only, never of the path, the batch or h's width class.
+ *
+ * fhe_batch_encoder_create builds and owns a one-limb engine on (n, t), so t must be a prime = 1 (mod 2n): FHE_ERR_BAD_MODULUS with *out
+ * untouched otherwise; an order outside the enum is FHE_ERR_INVALID_ARG.  It uploads one n-entry table, position of the NTT domain -> slot
+ * (fhe_batch_encoder_slot_table builds the same table on the host, no device needed), and the per-limb reductions.  For N = 2^11 .. 2^14 a
+ * call is ONE launch on the kernels of t's field (t = 65537 runs the 4-byte field whatever h's primes are; a full-width h too) and allocates
+ * nothing.  Elsewhere (and under FHE_HIP_NO_FUSED_ENCODE=1, read at creation) the library composes a gather, a transform of the owned engine and a
+ * streaming kernel through scratch of batch n 32 bytes that the ENCODER owns: fhe_batch_encoder_reserve sizes it, after which no call
+ * allocates and a call can be captured into a hipGraph; fhe_batch_encoder_scratch_bytes reports it.  Work is enqueued on h's stream.
+ * FHE_ERR_INVALID_ARG, with nothing launched and nothing written: a null handle, encoder or buffer; an encoder of another engine; batch == 0;
+ * a container pointer not 16-byte aligned or a uint64_t pointer not 8-byte aligned; an encode output overlapping its input (a decode output
+ * may be d_m itself, not overlap it otherwise).  fhe_batch_encoder_destroy(NULL) is FHE_OK.  None of these returns FHE_ERR_NO_DEVICE: every
+ * one needs an engine, which cannot exist without a device (fhe_rns_ntt_create reports that); fhe_batch_encoder_slot_table needs neither.
+ * The `const` of the encoder argument says that a call changes nothing a caller can observe, NOT that calls may run concurrently: like the
+ * workspaces of an engine, the scratch and the owned engine belong to one call at a time, so all calls on one encoder must be ordered on
+ * one stream, and a composed-path call that has to grow the scratch (no reserve before it) synchronises that stream first. */
+typedef enum fhe_slot_order { FHE_SLOTS_NATURAL = 0, FHE_SLOTS_ROWS = 1 } fhe_slot_order;
+typedef struct fhe_batch_encoder fhe_batch_encoder_t;
+int fhe_batch_encoder_create(fhe_rns_ntt_t *h, fhe_batch_encoder_t **out, uint64_t t, int slot_order);
+int fhe_batch_encoder_destroy(fhe_batch_encoder_t *enc);
+int fhe_batch_encoder_reserve(fhe_rns_ntt_t *h, fhe_batch_encoder_t *enc, uint32_t batch);
+int fhe_batch_encoder_scratch_bytes(const fhe_batch_encoder_t *enc, uint64_t *bytes);
+int fhe_batch_encoder_slot_table(uint32_t n, int slot_order, uint32_t *table);   /* host: table[n], position -> slot index */
+int fhe_slots_encode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, void *d_out, const uint64_t *d_values, uint32_t batch);
+int fhe_slots_decode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, uint64_t *d_values, const uint64_t *d_m, uint32_t batch);
+int fhe_slots_decode_poly(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, uint64_t *d_values, const void *d_poly, uint32_t batch);
+
 /* Scan a [batch][L][n] buffer for coefficients that are not canonical (>= q_limb, or non-zero
  * upper limbs on the narrow paths).  Synchronises.  FHE_OK or FHE_ERR_NONCANONICAL. */
 int fhe_rns_check_canonical(fhe_rns_ntt_t *h, const void *d_data, uint32_t batch);
