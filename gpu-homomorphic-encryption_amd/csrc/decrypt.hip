@@ -1,4 +1,4 @@
-// decrypt.hip -- secret keys and secret-key decryption (fhe_secret_key_*, fhe_ct_decrypt*).
+// decrypt.hip -- secret-key decryption (fhe_ct_decrypt*; the keys: keys.hip).
 // Fused path (plan_fused_decrypt; kernels: decrypt.hip.h): the key is kept transformed, with its pointwise square, packed like one key row each;
 // a call is two launches, ntt_decrypt_kernel into the compact decryption workspace d_dec and decrypt_crt_kernel from it.  Composed path
 // (full-width class, sizes outside the LDS-resident range, FHE_HIP_NO_FUSED_DECRYPT=1): fhe_rns_ntt_multiply_bcast against s (and against the
@@ -8,49 +8,6 @@
 #include "ntt_word.hip.h"
 #define FHE_DECRYPT_CRT_KERNELS
 #include "decrypt.hip.h"
-
-extern "C" int fhe_secret_key_destroy(fhe_secret_key_t *sk) {
-    if (sk) {
-        for (void *p : {sk->d_s, sk->d_packed}) if (p) (void)hipFree(p);
-        delete sk;
-    }
-    return FHE_OK;
-}
-extern "C" int fhe_secret_key_create(fhe_rns_ntt_t *h, fhe_secret_key_t **out, const void *d_s) {
-    if (!h || !out || !d_s) return fail(FHE_ERR_INVALID_ARG, "secret_key_create: null argument");
-    int rc = check_aligned({d_s}, "secret_key_create"); if (rc) return rc;
-    (void)hipGetLastError();
-    fhe_secret_key *sk = new (std::nothrow) fhe_secret_key();
-    if (!sk) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
-    sk->owner = h; sk->src = d_s;
-    const size_t S = (size_t)h->L * h->n * 32;
-    void *d_tr = nullptr;                            // (s^, s^ . s^), containers
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&sk->d_s, 2 * S));
-        HIP_TRY(hipMemcpyAsync(sk->d_s, d_s, S, hipMemcpyDeviceToDevice, h->stream));
-        if (int r = fhe_rns_ntt_multiply(h, (char *)sk->d_s + S, sk->d_s, sk->d_s, 1)) return r;
-        if (plan_fused_decrypt(h)) {
-            HIP_TRY(hipMalloc(&d_tr, 2 * S));
-            HIP_TRY(hipMemcpyAsync(d_tr, sk->d_s, S, hipMemcpyDeviceToDevice, h->stream));
-            if (int r = do_forward(h, d_tr, 1)) return r;
-            if (int r = fhe_rns_ntt_pointwise(h, (char *)d_tr + S, d_tr, d_tr, 1)) return r;
-            HIP_TRY(hipMalloc(&sk->d_packed, 2 * (size_t)h->L * h->n * residue_bytes(h)));
-            if (int r = with_word_field(h, [&](auto f) {
-                    using F = decltype(f);
-                    hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid(2 * (size_t)h->L * h->n)), dim3(256), 0, h->stream, (typename F::E *)sk->d_packed,
-                                       (const typename F::V16 *)d_tr, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, 2u);
-                    return post_launch(h->stream, "pack_keys_kernel (secret key)");
-                })) return r;
-        }
-        HIP_TRY(hipStreamSynchronize(h->stream));     // the transformed copy is freed below; the import is complete when the call returns
-        return FHE_OK;
-    };
-    rc = body();
-    if (d_tr) (void)hipFree(d_tr);
-    if (rc) { fhe_secret_key_destroy(sk); return rc; }
-    *out = sk;
-    return FHE_OK;
-}
 
 static int decrypt_q_fits(fhe_rns_ntt *h, const char *what) {
     if (int rc = ensure_crt(h)) return rc;
@@ -101,9 +58,8 @@ extern "C" int fhe_ct_decrypt(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint
     const bool fused = sk->d_packed && plan_fused_decrypt(h);
     const void *res = h->d_dec;
     if (fused) {
-        const size_t half = (size_t)h->L * h->n * residue_bytes(h);
         fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_DECRYPT, {}, batch * h->L);
-        A.r0 = h->d_dec; A.a0 = c[0]; A.a1 = c[1]; A.c2 = c[2]; A.kb = sk->d_packed; A.ka = (const char *)sk->d_packed + half; A.out_compact = true;
+        A.r0 = h->d_dec; A.a0 = c[0]; A.a1 = c[1]; A.c2 = c[2]; A.kb = sk->d_packed; A.ka = (const char *)sk->d_packed + packed_row_bytes(h); A.out_compact = true;
         if ((rc = lds_launch(h, A, "ntt_decrypt_kernel"))) return rc;
     } else {
         char *p0 = (char *)h->d_dec, *p1 = p0 + (size_t)batch * S;

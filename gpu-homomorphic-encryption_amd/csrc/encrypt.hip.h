@@ -7,7 +7,7 @@
 // A workgroup first draws its ciphertext's u, e0, e1 at the coefficients of the forward transform's input layout (pattern A: thread tid,
 // register r <-> coefficient tid + r T) and keeps them as PACKED SMALL INTEGERS: u as two 32-bit masks (non-zero, negative), every error as
 // 16 bits (15 of magnitude, one of sign), 34 VGPRs in all.  The cumulative table is staged in the exchange buffer, which nothing else uses yet,
-// and inverted by a branch-free binary search (the host admits tables that fit: ENCRYPT_MAX_CDT entries, i.e. sigma <= 85): ceil(log2 len)
+// and inverted by a branch-free binary search (cdt_count, ctr_rand.hip.h; the host admits tables that fit: ENCRYPT_MAX_CDT entries, i.e. sigma <= 85): ceil(log2 len)
 // LDS reads per coefficient instead of the linear scan's len 64-bit compares, same count because the table is non-decreasing.
 // Then, for every limb i of its range, with TWO live arrays:
 //     u^ = NTT_i(u);  x = pk0^_i . u^ -> INTT -> + t e0 + m -> containers;  x = pk1^_i . u^ -> INTT -> + t e1 -> containers
@@ -24,17 +24,6 @@
 #include "ntt_lds.hip.h"
 
 namespace fhe_dev {
-
-// count = #{ j < len : r >= cdt[j] } of a non-decreasing table: the largest pos <= len with cdt[pos - 1] <= r, by binary lifting from
-// top = the largest power of two <= len.  Constant trip count, no divergence.
-__device__ __forceinline__ uint32_t cdt_count(const uint64_t *cdt, uint32_t len, uint32_t top, uint64_t r) {
-    uint32_t pos = 0;
-    for (uint32_t s = top; s; s >>= 1) {
-        const uint32_t idx = pos + s, at = (idx <= len ? idx : len) - 1;
-        pos = (idx <= len && cdt[at] <= r) ? idx : pos;
-    }
-    return pos;
-}
 
 template <class F, int LOGN, int MINW = 1>
 __global__ void __launch_bounds__(NttCfg<LOGN>::T, MINW)

@@ -4,15 +4,17 @@
 //   core.hip        last error, device / memory entry points, host number theory, timers
 //   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
 //   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
-//   encrypt.hip     public keys, public-key encryption (composed path: sampling.hip.h and the entry points of transforms.hip; fused: encrypt.hip.h)
-//   decrypt.hip     secret keys, secret-key decryption (fused: decrypt.hip.h; composed path: the entry points of transforms.hip; the CRT kernels of decrypt.hip.h either way)
+//   keys.hip        the lifetime of every key object: import, export and destruction of key sets, secret keys, public keys; packing rows into
+//                   the register order of the fused kernels and back (the pack / unpack kernels of ntt_word.hip.h)
+//   encrypt.hip     public-key encryption (composed path: the entry points of sampling.hip and transforms.hip with the small kernel of encrypt.hip; fused: encrypt.hip.h)
+//   decrypt.hip     secret-key decryption (fused: decrypt.hip.h; composed path: the entry points of transforms.hip; the CRT kernels of decrypt.hip.h either way)
 //   engine.hip      engine lifetime, width-class choice, environment switches, limb tables, workspaces, reserve (= the merge of need_* below)
 //   transforms.hip  wide and LDS launchers, the planners, forward / inverse / element-wise / multiply / tensor product (ntt_wide.hip.h,
 //                   ntt256_transforms.hip.h; ew / compact / check kernels of ntt_word.hip.h)
-//   keyswitch.hip   key import, relinearisation, multiply + relinearise, Galois, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
-//                   key / digit / monomial kernels of ntt_word.hip.h)
-//   keygen.hip      key-switching key generation and key export (fused: keygen.hip.h; composed path: the entry points of transforms.hip, sampling.hip
-//                   and keyswitch.hip with the small kernels of keygen.hip; the unpack kernel of ntt_word.hip.h)
+//   keyswitch.hip   relinearisation, multiply + relinearise, Galois, hoisting, linear transform, blind rotation (galois.hip.h, ntt256_keyswitch.hip.h;
+//                   digit / monomial kernels of ntt_word.hip.h)
+//   keygen.hip      key-switching key generation (fused: keygen.hip.h; composed path: the entry points of transforms.hip, sampling.hip, keyswitch.hip
+//                   and keys.hip with the small kernels of keygen.hip)
 //   encode.hip      batch encoder: slots <-> plaintexts (fused: encode.hip.h on the engine of the plaintext modulus; composed path: the small
 //                   kernels of encode.hip.h around do_inverse / do_forward)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
@@ -140,11 +142,17 @@ struct fhe_relin_keys {
     void *d_pkb = nullptr, *d_pka = nullptr;    // packed tables for the fused key-switch kernel (word-sized paths)
 };
 
-struct fhe_secret_key {                             // created by decrypt.hip; keygen.hip reads it
+struct fhe_secret_key {                             // keys.hip; decrypt.hip and keygen.hip read it
     fhe_rns_ntt *owner = nullptr;
     const void *src = nullptr;                      // what the key was imported from (outputs must not alias it)
     void *d_s = nullptr;                            // s as given followed by s^2 = s (*) s: 2 x [L][n] containers, coefficient form (the composed paths multiply by these)
     void *d_packed = nullptr;                       // fused paths: (s^, s^ . s^), 2 x [L][n] residues, transformed and packed like one key row each
+};
+struct fhe_public_key {                             // keys.hip; encrypt.hip reads it
+    fhe_rns_ntt *owner = nullptr;
+    const void *src0 = nullptr, *src1 = nullptr;    // what the key was imported from (outputs must not alias them)
+    void *d_pk = nullptr;                           // (pk0, pk1) as given: 2 x [L][n] containers, coefficient form (the composed path multiplies by these)
+    void *d_packed = nullptr;                       // fused path: (pk0^, pk1^), 2 x [L][n] residues, transformed and packed like one key row each
 };
 
 // The one place that maps a word-sized width class to its field type: fn(F32{}) / fn(F52{}) / fn(F64{}) / fn(F64X{}), in the body
@@ -161,6 +169,17 @@ int with_word_field(const fhe_rns_ntt *h, Fn &&fn) {
 }
 inline size_t residue_bytes(const fhe_rns_ntt *h) { return h->residue_bytes; }   // of a compact polynomial's coefficient
 inline int lds_width_id(const fhe_rns_ntt *h) { return h->lds_id; }
+inline size_t packed_row_bytes(const fhe_rns_ntt *h) { return (size_t)h->L * h->n * residue_bytes(h); }   // of one packed row: [L][n] residues
+
+struct Scratch {                                     // device allocations of one call, freed when it ends
+    std::vector<void *> p;
+    ~Scratch() { for (void *d : p) if (d) (void)hipFree(d); }
+    int get(void **out, size_t bytes) {
+        HIP_TRY(hipMalloc(out, bytes));
+        p.push_back(*out);
+        return FHE_OK;
+    }
+};
 
 // ---- engine.hip -----------------------------------------------------------------------------------------------------------------
 int create_impl(fhe_rns_ntt **out, uint32_t n, const uint64_t (*moduli)[4], uint32_t L, bool base_only = false);
@@ -244,10 +263,18 @@ template <int OP> int do_ew(fhe_rns_ntt *h, void *r, const void *a, const void *
 int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0, const void *a1, const void *b0, const void *b1, uint32_t batch);
 int compact_poly(fhe_rns_ntt *h, void *out, const void *in, size_t containers);   // containers -> compact polynomials (word-sized classes)
 
+// ---- keys.hip -------------------------------------------------------------------------------------------------------------------
+// `rows` polynomials of [L][n] NTT-domain containers -> packed residues (times 2^W, register order of the fused kernels), and back; `what` names the launch
+int pack_rows(fhe_rns_ntt *h, void *dst, const void *src, uint32_t rows, const char *what);
+int unpack_rows(fhe_rns_ntt *h, void *dst, const void *src, uint32_t rows, const char *what);
+fhe_relin_keys *new_key_set(fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K);   // an empty set of L K rows (nullptr: out of host memory)
+// A generated or imported set whose tables are complete (NTT domain): packed = what keys_get_packed says of it.  Packs d_kb / d_ka into
+// d_pkb / d_pka and drops the containers where the set has them, and records K for fhe_rns_ntt_reserve.
+int finish_key_set(fhe_rns_ntt *h, fhe_relin_keys *rk, bool packed);
+
 // ---- keyswitch.hip --------------------------------------------------------------------------------------------------------------
 uint32_t relin_digits(const fhe_rns_ntt *h, uint32_t decomp_bits);               // K of fhe_relin_num_digits
 bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K);   // whether such a key set gets packed tables, i.e. runs the fused kernels
-int pack_relin_keys(fhe_rns_ntt *h, fhe_relin_keys *rk);                         // allocates d_pkb / d_pka and packs d_kb / d_ka (NTT domain) into them
 int check_galois_element(const fhe_rns_ntt *h, uint32_t g, const char *what);   // odd and below 2n
 // sigma_g of one or two components (in1 == nullptr: one) into out0 / out1, zero_out (optional) cleared beside them; compact: residues out
 int do_galois(fhe_rns_ntt *h, void *out0, void *out1, void *zero_out, const void *in0, const void *in1, uint32_t g, size_t polys, bool compact);

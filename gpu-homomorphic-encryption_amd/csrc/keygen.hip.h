@@ -21,8 +21,7 @@
 // likewise (pw_mul(canonical target^ 2^W, canonical 2^(k w) mod q_j)); subtraction and addition are canonical (ew_sub / ew_add);
 // to_pw_operand takes and gives canonical values.  F64X is canonical throughout.
 #pragma once
-#include "ctr_rand.hip.h"
-#include "encrypt.hip.h"                   // cdt_count
+#include "ctr_rand.hip.h"                  // the generator and cdt_count
 #include "lds_launch.h"
 #include "ntt_lds.hip.h"
 

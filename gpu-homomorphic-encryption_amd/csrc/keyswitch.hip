@@ -1,4 +1,4 @@
-// keyswitch.hip -- key import and packing, relinearisation, multiply + relinearise, Galois automorphisms, blind rotation.
+// keyswitch.hip -- relinearisation, multiply + relinearise, Galois automorphisms, hoisted rotations and linear transform, blind rotation.
 #include "engine.h"
 
 #include <algorithm>
@@ -22,29 +22,6 @@ extern "C" int fhe_relin_num_digits(const fhe_rns_ntt_t *h, uint32_t decomp_bits
     *digits = relin_digits(h, decomp_bits);
     return FHE_OK;
 }
-extern "C" int fhe_relin_keys_destroy(fhe_relin_keys_t *rk) {
-    if (rk) {
-        for (void *p : {rk->d_kb, rk->d_ka, rk->d_pkb, rk->d_pka}) if (p) (void)hipFree(p);
-        delete rk;
-    }
-    return FHE_OK;
-}
-
-// packed key tables for the fused key-switch kernels (word-sized paths)
-template <class F>
-static int pack_relin_keys_t(fhe_rns_ntt *h, fhe_relin_keys *rk) {
-    const size_t elems = (size_t)rk->num_keys * h->L * h->n;
-    HIP_TRY(hipMalloc(&rk->d_pkb, elems * sizeof(typename F::E)));
-    HIP_TRY(hipMalloc(&rk->d_pka, elems * sizeof(typename F::E)));
-    hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid(elems)), dim3(256), 0, h->stream, (typename F::E *)rk->d_pkb,
-                       (const typename F::V16 *)rk->d_kb, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->num_keys);
-    hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid(elems)), dim3(256), 0, h->stream, (typename F::E *)rk->d_pka,
-                       (const typename F::V16 *)rk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, rk->num_keys);
-    return post_launch(h->stream, "pack_keys_kernel");
-}
-
-int pack_relin_keys(fhe_rns_ntt *h, fhe_relin_keys *rk) { return with_word_field(h, [&](auto f) { return pack_relin_keys_t<decltype(f)>(h, rk); }); }
-
 // Whether a key set of K digits of decomp_bits bits gets packed tables, i.e. runs the fused kernels (fhe_ct_hoist asks before any key set is seen)
 bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K) {
     const size_t num_keys = (size_t)h->L * K;
@@ -69,49 +46,6 @@ bool keys_get_packed(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t K) {
     // more (L*K*L*n residues: not reached by any parameter set of the reference) stays on the general composition
     const bool table_fits = (size_t)num_keys * h->L * h->n * (h->width == FHE_WIDTH_32 ? 4 : 8) < ((size_t)1 << 32);
     return h->width != FHE_WIDTH_256 && !h->sub_top && digits_fit && table_fits && !h->env.no_fused_keyswitch;
-}
-extern "C" int fhe_relin_keys_create(fhe_rns_ntt_t *h, fhe_relin_keys_t **out, uint32_t decomp_bits,
-                                     const void *const *d_keys_b, const void *const *d_keys_a, uint32_t num_keys) {
-    if (!h || !out || !d_keys_b || !d_keys_a) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null argument");
-    *out = nullptr;
-    if (decomp_bits < 1 || decomp_bits > 64) return fail(FHE_ERR_INVALID_ARG, "decomp_bits must be in [1, 64]");
-    const uint32_t K = relin_digits(h, decomp_bits);
-    if (num_keys != h->L * K) {
-        char buf[128]; snprintf(buf, sizeof buf, "relin_keys_create: expected %u keys (L = %u limbs x K = %u digits), got %u", h->L * K, h->L, K, num_keys);
-        return fail(FHE_ERR_INVALID_ARG, buf);
-    }
-    for (uint32_t i = 0; i < num_keys; i++) if (!d_keys_b[i] || !d_keys_a[i]) return fail(FHE_ERR_INVALID_ARG, "relin_keys_create: null key pointer");
-    for (uint32_t i = 0; i < num_keys; i++) if (int rc = check_aligned({d_keys_b[i], d_keys_a[i]}, "relin_keys_create")) return rc;
-    (void)hipGetLastError();
-    fhe_relin_keys *rk = new (std::nothrow) fhe_relin_keys();
-    if (!rk) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
-    rk->owner = h; rk->decomp_bits = decomp_bits; rk->K = K; rk->num_keys = num_keys;
-    if (K > h->max_digits) h->max_digits = K;                          // fhe_rns_ntt_reserve sizes the key-switch workspaces for it
-    const size_t S = (size_t)h->L * h->n * 32;
-    hipError_t e;
-    if ((e = hipMalloc(&rk->d_kb, S * num_keys)) != hipSuccess || (e = hipMalloc(&rk->d_ka, S * num_keys)) != hipSuccess) {
-        fhe_relin_keys_destroy(rk); return fail(FHE_ERR_HIP, std::string("relin_keys_create: ") + hipGetErrorString(e));
-    }
-    for (uint32_t i = 0; i < num_keys; i++) {
-        if ((e = hipMemcpyAsync((char *)rk->d_kb + i * S, d_keys_b[i], S, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync((char *)rk->d_ka + i * S, d_keys_a[i], S, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess) {
-            fhe_relin_keys_destroy(rk); return fail(FHE_ERR_HIP, std::string("relin_keys_create copy: ") + hipGetErrorString(e));
-        }
-    }
-    int rc = do_forward(h, rk->d_kb, num_keys);
-    if (!rc) rc = do_forward(h, rk->d_ka, num_keys);
-    if (!rc && keys_get_packed(h, decomp_bits, K)) {
-        rc = pack_relin_keys(h, rk);
-        if (!rc) {   // the fused kernels read only the packed tables (n * sizeof(E) bytes per key polynomial instead of n * 32): drop the
-                     // container copy, so that a bootstrapping key of several hundred RGSW ciphertexts fits (hipFree waits for the packing)
-            (void)hipFree(rk->d_kb); (void)hipFree(rk->d_ka);
-            rk->d_kb = rk->d_ka = nullptr;
-        }
-    }
-    if (rc) { fhe_relin_keys_destroy(rk); return rc; }
-    if (!rk->d_pkb && K > h->max_composed_digits) h->max_composed_digits = K;   // this key set runs the composed key switch (digit polynomials in the workspace)
-    *out = rk;
-    return FHE_OK;
 }
 
 // D[jk][b][i] = digit jk of src[b] embedded in limb i, as containers (K digits of w bits per limb)
@@ -563,31 +497,25 @@ extern "C" int fhe_linear_transform_create(fhe_rns_ntt_t *h, fhe_linear_transfor
     lt->owner = h; lt->decomp_bits = decomp_bits; lt->K = K; lt->fused = fused; lt->keyless = keyless;
     lt->g.assign(galois_elts, galois_elts + num_terms); lt->gk.assign(gks, gks + num_terms);
     const size_t S = (size_t)h->L * h->n * 32;
-    void *d_copy = nullptr;                          // the plaintexts as containers
+    Scratch scratch;
     auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&d_copy, S * num_terms));
+        void *d_copy = nullptr;                      // the plaintexts as containers: scratch of the fused path, the transform's own copy otherwise
+        if (fused) { if (int r = scratch.get(&d_copy, S * num_terms)) return r; }
+        else { HIP_TRY(hipMalloc(&lt->d_plain, S * num_terms)); d_copy = lt->d_plain; }
         for (uint32_t t = 0; t < num_terms; t++) HIP_TRY(hipMemcpyAsync((char *)d_copy + t * S, d_plain[t], S, hipMemcpyDeviceToDevice, h->stream));
-        if (!fused) { lt->d_plain = d_copy; d_copy = nullptr; return post_launch(h->stream, "linear_transform_create copy"); }
+        if (!fused) return post_launch(h->stream, "linear_transform_create copy");
         if (int r = do_forward(h, d_copy, num_terms)) return r;
         std::vector<fhe_dev::LincombTerm> terms(num_terms);
-        const size_t eb = residue_bytes(h);
-        HIP_TRY(hipMalloc(&lt->d_plain, (size_t)num_terms * h->L * h->n * eb));
+        HIP_TRY(hipMalloc(&lt->d_plain, num_terms * packed_row_bytes(h)));
         HIP_TRY(hipMalloc(&lt->d_terms, num_terms * sizeof(fhe_dev::LincombTerm)));
-        if (int r = with_word_field(h, [&](auto f) {
-                using F = decltype(f);
-                hipLaunchKernelGGL((fhe_dev::pack_keys_kernel<F>), dim3(ew_grid((size_t)num_terms * h->L * h->n)), dim3(256), 0, h->stream, (typename F::E *)lt->d_plain,
-                                   (const typename F::V16 *)d_copy, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, num_terms);
-                return post_launch(h->stream, "pack_keys_kernel (plaintexts)");
-            })) return r;
+        if (int r = pack_rows(h, lt->d_plain, d_copy, num_terms, "pack_keys_kernel (plaintexts)")) return r;
         for (uint32_t t = 0; t < num_terms; t++)
-            terms[t] = {gks[t] ? gks[t]->d_pkb : nullptr, gks[t] ? gks[t]->d_pka : nullptr, (const char *)lt->d_plain + (size_t)t * h->L * h->n * eb, galois_elts[t], 0};
+            terms[t] = {gks[t] ? gks[t]->d_pkb : nullptr, gks[t] ? gks[t]->d_pka : nullptr, (const char *)lt->d_plain + t * packed_row_bytes(h), galois_elts[t], 0};
         HIP_TRY(hipMemcpyAsync(lt->d_terms, terms.data(), num_terms * sizeof(fhe_dev::LincombTerm), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));     // `terms` leaves scope; hipFree of the copy waits anyway
+        HIP_TRY(hipStreamSynchronize(h->stream));     // `terms` leaves scope; the scratch is freed when the call returns
         return FHE_OK;
     };
-    rc = body();
-    if (d_copy) (void)hipFree(d_copy);
-    if (rc) { fhe_linear_transform_destroy(lt); return rc; }
+    if ((rc = body())) { fhe_linear_transform_destroy(lt); return rc; }
     *out = lt;
     return FHE_OK;
 }

@@ -85,7 +85,7 @@ constexpr bool lds_keygen(int elem_bytes, int log_n) { (void)elem_bytes; return 
 // decryption and key-generation kernels, which it feeds and drains; N = 2^15 takes the composed path like them (tests/test_batch_encoder.py
 // compiles every instance and pins the budgets)
 constexpr bool lds_slots(int elem_bytes, int log_n) { (void)elem_bytes; return log_n <= 14; }
-// entries of a cumulative Gaussian table the kernel stages in its exchange buffer (8 KiB: the buffer of the smallest instance); larger
+// entries of a cumulative Gaussian table the kernel stages in its exchange buffer (8 KiB: the buffer of the smallest instance; searched with cdt_count, ctr_rand.hip.h); larger
 // tables (sigma > 85) take the composed path
 constexpr uint32_t ENCRYPT_MAX_CDT = 1024;
 
@@ -111,7 +111,7 @@ constexpr const char *lds_form_name(int form) { switch (form) { LDS_FORMS(LDS_NA
 // One term of a hoisted linear transform (device table owned by the fhe_linear_transform object, read by ntt_hoist_lincomb_kernel).
 // kb == nullptr: no key switch, the term is p * (c0, c1)
 struct LincombTerm {
-    const void *kb, *ka;                 // packed key tables of the term's key set (pack_keys_kernel)
+    const void *kb, *ka;                 // packed key tables of the term's key set (pack_rows, keys.hip)
     const void *pt;                      // the term's plaintext, transformed and packed like one key row: [L][n] residues
     uint32_t g, _pad;                    // Galois element (1 for a keyless term)
 };

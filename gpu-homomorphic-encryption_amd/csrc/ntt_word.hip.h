@@ -78,7 +78,8 @@ check_kernel(const typename F::V16 *__restrict__ a, const Limb<F> *__restrict__ 
 // Key tables in the kernel's own register order ("packed"): for level jk and limb i, element (chunk c, thread tid, e) holds
 // KEY_ntt[i][tid*32 + c*VPL + e] * 2^W mod q_i, VPL = 16 / sizeof(E) values per 16-byte lane load, so a wave instruction
 // reads 1 KiB contiguous and pw_mul's 2^-W cancels.  Tables for one engine total 2 * L*K * L * N * sizeof(E) bytes
-// (2 MiB at N = 8192, L = 4, K = 2, F32) and stay L2-resident across the batch.
+// (2 MiB at N = 8192, L = 4, K = 2, F32) and stay L2-resident across the batch.  keys.hip launches this kernel and its inverse (pack_rows,
+// unpack_rows) for every source: key sets, secret and public keys, the plaintexts of a linear transform.
 template <class F>
 __global__ void __launch_bounds__(256)
 pack_keys_kernel(typename F::E *__restrict__ packed, const typename F::V16 *__restrict__ keys_ntt, const Limb<F> *__restrict__ limbs,

@@ -18,7 +18,6 @@
 
 namespace fhe_dev {
 
-__device__ __forceinline__ u256 u256_small(uint64_t v) { u256 r; r.l[0] = v; r.l[1] = r.l[2] = r.l[3] = 0; return r; }
 __device__ __forceinline__ bool lt256(const u256 &a, const u256 &b) {   // a < b
 #pragma unroll
     for (int i = 3; i >= 0; i--) { if (a.l[i] != b.l[i]) return a.l[i] < b.l[i]; }
@@ -58,11 +57,8 @@ sample_small_kernel(u256 *__restrict__ out, const CrtLimb *__restrict__ limbs, u
             mag = (r & 0xffffffffull) < thr ? 1 : 0;
             neg = (r >> 63) != 0;
         } else {
-            const uint64_t r = ctr_rand(seed, g, DRAW_CDT);
-            uint32_t m = 0;
-            for (uint32_t j = 0; j < cdt_len; j++) m += r >= cdt[j] ? 1u : 0u;   // constant work per coefficient
-            mag = m;
-            neg = (ctr_rand(seed, g, DRAW_SIGN) >> 63) != 0;
+            const GaussianDraw d = gaussian_draw(seed, g, cdt, cdt_len);
+            mag = d.mag; neg = d.neg;
         }
         const size_t b = g >> log_n, x = g & (n - 1);
         for (uint32_t l = 0; l < L; l++) {

@@ -69,6 +69,15 @@ __device__ __forceinline__ u256 sub_mod(const u256 &a, const u256 &b, const u256
     return r;
 }
 
+__device__ __forceinline__ u256 u256_small(uint64_t v) { u256 r; r.l[0] = v; r.l[1] = r.l[2] = r.l[3] = 0; return r; }
+// [+-scale mag] mod q for a small magnitude (a sampler's draw): scale mod q, mag times by double-and-add (no division beyond the one of a
+// word-sized q), then the sign
+__device__ __forceinline__ u256 scaled_small_mod(uint32_t mag, bool neg, uint64_t scale, const u256 &q) {
+    u256 te = u256_small(0), pw = u256_small((q.l[1] | q.l[2] | q.l[3]) ? scale : scale % q.l[0]);
+    for (uint32_t k = mag; k; k >>= 1) { if (k & 1) te = add_mod(te, pw, q); pw = add_mod(pw, pw, q); }
+    return neg ? sub_mod(u256_small(0), te, q) : te;
+}
+
 // include/bigint.cuh:76-140.  Same value as the reference's separated product + 4 reduction rounds:
 // the rows are interleaved (product row i, then reduction round i) so only 6 limbs are live; the
 // multipliers m_i are identical because round i only ever reads limb i of the running sum, which is
