@@ -125,6 +125,9 @@ def lib():
         "fhe_ct_decrypt": ([vp, vp, u64, u64, vp, vp, P(vp), u32, u32], ci),
         "fhe_keyswitch_keys_generate": ([vp, vp, u32, P(u32), u32, u64, ctypes.c_double, P(u64), P(vp)], ci),
         "fhe_relin_keys_export": ([vp, vp, vp, vp], ci),
+        "fhe_rgsw_keys_generate": ([vp, vp, u32, P(ctypes.c_int32), u32, u64, ctypes.c_double, P(u64), P(vp), P(vp)], ci),
+        "fhe_lwe_prepare_accumulator": ([vp, u64, u32, vp, vp, vp, vp, vp, u32], ci),
+        "fhe_rlwe_sample_extract": ([vp, vp, vp, vp, u32, u32], ci),
         "fhe_batch_encoder_create": ([vp, P(vp), u64, ci], ci),
         "fhe_batch_encoder_destroy": ([vp], ci),
         "fhe_batch_encoder_reserve": ([vp, vp, u32], ci),
@@ -550,6 +553,24 @@ class RnsNttEngine:
         outs = (ctypes.c_void_p * max(k, 1))()
         _check(lib().fhe_keyswitch_keys_generate(self.h, sk.h, decomp_bits, ge, k, noise_scale, sigma, sd, outs))
         return [RelinKeys(ctypes.c_void_p(outs[i])) for i in range(k)]
+
+    def generate_rgsw_keys(self, sk, decomp_bits, mu, noise_scale, sigma, seeds):
+        """One RGSW ciphertext per entry of `mu` (small integers, |mu| <= 2^15), generated on the device from `sk` with seeds = (a, e).
+        Returns (rows_c0, rows_c1), two lists of key-set objects as fhe_blind_rotate takes them."""
+        k = len(mu)
+        ms = (ctypes.c_int32 * max(k, 1))(*[int(m) for m in mu])
+        sd = (ctypes.c_uint64 * 2)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
+        o0, o1 = (ctypes.c_void_p * max(k, 1))(), (ctypes.c_void_p * max(k, 1))()
+        _check(lib().fhe_rgsw_keys_generate(self.h, sk.h, decomp_bits, ms, k, noise_scale, sigma, sd, o0, o1))
+        return [RelinKeys(ctypes.c_void_p(o0[i])) for i in range(k)], [RelinKeys(ctypes.c_void_p(o1[i])) for i in range(k)]
+
+    def lwe_prepare_accumulator(self, q_lwe, n_lwe, d_lwe, d_tv, d_acc0, d_acc1, d_shifts, batch=1):
+        """d_lwe: device uint64 [batch][n_lwe + 1] -> acc0 = X^(2n - ms(b)) tv, acc1 = 0, d_shifts = device uint32 [n_lwe][batch]."""
+        _check(lib().fhe_lwe_prepare_accumulator(self.h, q_lwe, n_lwe, _ptr(d_lwe), _ptr(d_tv), _ptr(d_acc0), _ptr(d_acc1), _ptr(d_shifts), batch))
+
+    def sample_extract(self, d_out, d_c0, d_c1, idx, batch=1):
+        """Coefficient idx of (c0, c1) as LWE samples: d_out = device uint64 [batch][L][n + 1]."""
+        _check(lib().fhe_rlwe_sample_extract(self.h, _ptr(d_out), _ptr(d_c0), _ptr(d_c1), idx, batch))
 
     def export_keys(self, rk, d_keys_b, d_keys_a):
         """The rows of any key set as [L*K][L][n] canonical containers in coefficient form (the inverse of import_relin_keys)."""

@@ -1,0 +1,65 @@
+// bootstrap.hip -- what stands around the blind-rotation loop (fhe_blind_rotate, keyswitch.hip): an LWE ciphertext into the loop's inputs
+// (fhe_lwe_prepare_accumulator) and one coefficient of the result out as an LWE sample (fhe_rlwe_sample_extract).  One launch each, no
+// workspace, nothing allocated: both can be captured into a hipGraph with the loop.  Kernels: bootstrap.hip.h.  (The RGSW rows the loop
+// consumes: fhe_rgsw_keys_generate, keygen.hip.)
+#include "engine.h"
+
+#include <type_traits>
+
+#include "bootstrap.hip.h"
+
+static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+extern "C" int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uint32_t n_lwe, const uint64_t *d_lwe, const void *d_tv, void *d_acc0,
+                                           void *d_acc1, uint32_t *d_shifts, uint32_t batch) {
+    int rc = check_call(h, batch, "lwe_prepare_accumulator"); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "lwe_prepare_accumulator: every modulus must be below 2^64");
+    if (!d_lwe || !d_tv || !d_acc0 || !d_acc1 || !d_shifts) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: null argument");
+    if ((rc = check_aligned({d_tv, d_acc0, d_acc1}, "lwe_prepare_accumulator"))) return rc;
+    if (((uintptr_t)d_lwe & 7) || ((uintptr_t)d_shifts & 3)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: d_lwe must be 8-byte, d_shifts 4-byte aligned");
+    if (!n_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: n_lwe must be at least 1");
+    if (q_lwe < 2 || q_lwe > (1ull << 48)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: q_lwe must be in [2, 2^48]");
+    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: n must be at least 8");
+    const size_t S = (size_t)h->L * h->n * 32, acc = S * batch, sh = (size_t)n_lwe * batch * 4, lw = ((size_t)n_lwe + 1) * batch * 8;
+    if (overlaps(d_acc0, acc, d_acc1, acc) || overlaps(d_acc0, acc, d_shifts, sh) || overlaps(d_acc1, acc, d_shifts, sh))
+        return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: the outputs must not overlap");
+    for (const void *o : {(const void *)d_acc0, (const void *)d_acc1})
+        if (overlaps(o, acc, d_lwe, lw) || overlaps(o, acc, d_tv, S)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: an output overlaps an input");
+    if (overlaps(d_shifts, sh, d_lwe, lw) || overlaps(d_shifts, sh, d_tv, S)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: an output overlaps an input");
+    if ((rc = check_inputs(h, {d_tv}, 1))) return rc;
+    using V = fhe_dev::v2u64;
+    const size_t halves = (size_t)batch * h->L * h->n * 2;
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::lwe_prepare_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)d_acc0, (V *)d_acc1, d_shifts, d_lwe, (const V *)d_tv, limbs,
+                           q_lwe, n_lwe, batch, h->L, h->log_n, halves);
+        return post_launch(h->stream, "lwe_prepare_kernel");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+
+extern "C" int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t idx, uint32_t batch) {
+    int rc = check_call(h, batch, "rlwe_sample_extract"); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "rlwe_sample_extract: every modulus must be below 2^64");
+    if (!d_out || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: null argument");
+    if ((rc = check_aligned({d_c0, d_c1}, "rlwe_sample_extract"))) return rc;
+    if ((uintptr_t)d_out & 7) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: d_out must be 8-byte aligned");
+    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: n must be at least 8");
+    if (idx >= h->n) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: idx must be below n");
+    const size_t polys = (size_t)batch * h->L, in = polys * h->n * 32, out = polys * ((size_t)h->n + 1) * 8;
+    if (overlaps(d_out, out, d_c0, in) || overlaps(d_out, out, d_c1, in)) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: the output overlaps an input");
+    if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
+    using V = fhe_dev::v2u64;
+    const unsigned bx = (unsigned)std::min<size_t>(((size_t)h->n + 1 + 255) / 256, 64), by = (unsigned)std::min<size_t>(polys, 65535);
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::sample_extract_kernel<LimbT>), dim3(bx, by), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, idx, h->L, h->log_n, polys);
+        return post_launch(h->stream, "sample_extract_kernel");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}

@@ -17,6 +17,8 @@
 //                   and keys.hip with the small kernels of keygen.hip)
 //   encode.hip      batch encoder: slots <-> plaintexts (fused: encode.hip.h on the engine of the plaintext modulus; composed path: the small
 //                   kernels of encode.hip.h around do_inverse / do_forward)
+//   bootstrap.hip   around the blind-rotation loop: LWE ciphertexts -> accumulators and shift table, sample extraction (bootstrap.hip.h); the RGSW
+//                   rows of the loop come from keygen.hip (fhe_rgsw_keys_generate)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once
@@ -166,6 +168,11 @@ int with_word_field(const fhe_rns_ntt *h, Fn &&fn) {
         case FHE_WIDTH_64X: return fn(fhe_dev::F64X{});
         default: return fail(FHE_ERR_UNSUPPORTED, "width class " + std::to_string(h->width) + " has no word-sized field (compact polynomials and the field kernels exist on the word-sized classes only)");
     }
+}
+// every modulus below 2^64: a word-sized class, or FHE_WIDTH_256 chosen for the SIZE (n < 2^11 has no word-sized kernels), not for a wide modulus
+inline bool word_sized_moduli(const fhe_rns_ntt *h) {
+    for (const U256 &q : h->moduli) if (q.w[1] | q.w[2] | q.w[3]) return false;
+    return true;
 }
 inline size_t residue_bytes(const fhe_rns_ntt *h) { return h->residue_bytes; }   // of a compact polynomial's coefficient
 inline int lds_width_id(const fhe_rns_ntt *h) { return h->lds_id; }

@@ -1,4 +1,5 @@
-// keygen.hip -- key-switching key generation (fhe_keyswitch_keys_generate; the key sets themselves: keys.hip).
+// keygen.hip -- key-switching key generation (fhe_keyswitch_keys_generate; the key sets themselves: keys.hip) and, at the end, RGSW rows on the
+// same two paths (fhe_rgsw_keys_generate).
 // Fused path (plan_fused_keygen, a secret key with packed transforms, a cumulative table that fits the kernel; kernel: keygen.hip.h): the
 // packed tables of every set are allocated, a table of (tables, Galois element) per set is uploaded and ONE launch fills them all; the
 // Galois targets are gathered in the kernel from the packed transform of s.
@@ -42,6 +43,20 @@ keygen_gadget_kernel(u256 *__restrict__ kb, const u256 *__restrict__ tgt, const 
         for (uint32_t d = 0; d < k * w; d++) v = add_mod(v, v, q);
         u256 *at = kb + ((r * L + j) << log_n) + x;
         store_u256(at, add_mod(load_u256(at), v, q));
+    }
+}
+
+// tgt[l][x] = [mu]_{q_l} (by_s == 0: the constant polynomial mu, the same value at every NTT position) or [mu]_{q_l} sh[l][x] (by_s: mu s^), the
+// target of an RGSW component (fhe_rgsw_keys_generate, composed path); |mu| = mag by double-and-add, then the sign.  One lane per (limb, position)
+__global__ void __launch_bounds__(256)
+rgsw_target_kernel(u256 *__restrict__ tgt, const u256 *__restrict__ sh, const CrtLimb *__restrict__ limbs, uint32_t log_n, uint32_t mag, uint32_t neg,
+                   uint32_t by_s, size_t count /* L n */) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < count; o += stride) {
+        const u256 q = limbs[o >> log_n].q;
+        u256 v = by_s ? load_u256(sh + o) : u256_small(1), acc = u256_small(0);
+        for (uint32_t k = mag; k; k >>= 1) { if (k & 1) acc = add_mod(acc, v, q); v = add_mod(v, v, q); }
+        store_u256(tgt + o, neg ? sub_mod(u256_small(0), acc, q) : acc);
     }
 }
 
@@ -132,5 +147,80 @@ extern "C" int fhe_keyswitch_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_ke
         return rc;
     }
     for (uint32_t e = 0; e < num_sets; e++) out_sets[e] = sets[e];
+    return FHE_OK;
+}
+
+// RGSW ciphertexts of small messages (the bootstrapping key of a blind rotation): the same rows with the gadget term mu (component 0) or
+// mu s (component 1); half e = 2 i + c of the call is "set" e of the streams.  Fused where fhe_keyswitch_keys_generate is (ONE launch of the
+// sibling kernel, which reads s^ only); else generate_composed with target^ = mu at every position, or mu s^ (rgsw_target_kernel).
+extern "C" int fhe_rgsw_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t decomp_bits, const int32_t *mu, uint32_t num,
+                                      uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_relin_keys_t **out_rows_c0,
+                                      fhe_relin_keys_t **out_rows_c1) {
+    int rc = check_call(h, 1, "rgsw_keys_generate"); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "rgsw_keys_generate: every modulus must be below 2^64");
+    if (!sk || !mu || !seeds || !out_rows_c0 || !out_rows_c1) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: null argument");
+    if (out_rows_c0 == out_rows_c1) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: the two output arrays must be distinct");
+    if (sk->owner != h) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: the key was imported for a different engine");
+    if (!num) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: num must be at least 1");
+    if (decomp_bits < 1 || decomp_bits > 64) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: decomp_bits must be in [1, 64]");
+    for (uint32_t i = 0; i < num; i++)
+        if (mu[i] > (1 << 15) || mu[i] < -(1 << 15)) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: |mu| must not exceed 2^15");
+    if (!noise_scale) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: noise_scale must not be 0");
+    const uint32_t K = relin_digits(h, decomp_bits), LK = h->L * K;
+    if (2ull * num * LK * h->L > 0x7fffffffull) return fail(FHE_ERR_INVALID_ARG, "rgsw_keys_generate: num * num_primes^2 * digits too large");
+    if ((rc = ensure_cdt(h, sigma, "rgsw_keys_generate"))) return rc;
+    (void)hipGetLastError();
+
+    const bool packed = keys_get_packed(h, decomp_bits, K);
+    const bool fused = plan_fused_keygen(h, packed) && sk->d_packed && h->cdt_len <= fhe_dev::ENCRYPT_MAX_CDT;
+    const size_t S = (size_t)h->L * h->n * 32, table = LK * packed_row_bytes(h);
+    const uint32_t halves = 2 * num;
+    std::vector<fhe_relin_keys *> sets(halves, nullptr);          // [2 i + c]
+    Scratch scratch;
+    auto body = [&]() -> int {
+        for (uint32_t e = 0; e < halves; e++)
+            if (!(sets[e] = new_key_set(h, decomp_bits, K))) return fail(FHE_ERR_INVALID_ARG, "out of host memory");
+        if (fused) {
+            std::vector<fhe_dev::RgswSet> tab(halves);
+            for (uint32_t e = 0; e < halves; e++) {
+                HIP_TRY(hipMalloc(&sets[e]->d_pkb, table));
+                HIP_TRY(hipMalloc(&sets[e]->d_pka, table));
+                tab[e] = {sets[e]->d_pkb, sets[e]->d_pka, mu[e / 2], e & 1u};
+            }
+            void *d_tab = nullptr;
+            if (int r = scratch.get(&d_tab, halves * sizeof(fhe_dev::RgswSet))) return r;
+            HIP_TRY(hipMemcpy(d_tab, tab.data(), halves * sizeof(fhe_dev::RgswSet), hipMemcpyHostToDevice));
+            fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_RGSW_KEYGEN, {}, halves * LK * h->L);
+            A.a0 = d_tab; A.kb = sk->d_packed;
+            A.cdt = h->d_cdt; A.cdt_len = h->cdt_len; A.seeds[0] = seeds[0]; A.seeds[1] = seeds[1]; A.t = noise_scale; A.K = K; A.w = decomp_bits;
+            if (int r = lds_launch(h, A, "ntt_rgsw_keygen_kernel")) return r;
+            for (fhe_relin_keys *rk : sets) (void)finish_key_set(h, rk, packed);     // the kernel wrote the packed tables: K for fhe_rns_ntt_reserve only
+        } else {
+            if (int r = ensure_crt(h)) return r;
+            void *sh = nullptr, *tgt = nullptr, *prod = nullptr;
+            int r;
+            if ((r = scratch.get(&sh, S)) || (r = scratch.get(&tgt, S)) || (r = scratch.get(&prod, S * LK))) return r;
+            HIP_TRY(hipMemcpyAsync(sh, sk->d_s, S, hipMemcpyDeviceToDevice, h->stream));
+            if ((r = do_forward(h, sh, 1))) return r;
+            const size_t count = (size_t)h->L * h->n;
+            for (uint32_t e = 0; e < halves; e++) {
+                const int32_t m = mu[e / 2];
+                hipLaunchKernelGGL(fhe_dev::rgsw_target_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)tgt, (const fhe_dev::u256 *)sh,
+                                   (const fhe_dev::CrtLimb *)h->d_crt, h->log_n, m < 0 ? 0u - (uint32_t)m : (uint32_t)m, m < 0 ? 1u : 0u, e & 1u, count);
+                if ((r = post_launch(h->stream, "rgsw_target_kernel"))) return r;
+                if ((r = generate_composed(h, sets[e], sh, tgt, (char *)prod, (size_t)e * LK, noise_scale, seeds, packed))) return r;
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));     // the scratch is freed when the call returns; the keys are complete then
+        return FHE_OK;
+    };
+    rc = body();
+    if (rc) {
+        (void)hipStreamSynchronize(h->stream);
+        for (fhe_relin_keys *rk : sets) fhe_relin_keys_destroy(rk);
+        for (uint32_t i = 0; i < num; i++) out_rows_c0[i] = out_rows_c1[i] = nullptr;
+        return rc;
+    }
+    for (uint32_t i = 0; i < num; i++) { out_rows_c0[i] = sets[2 * i]; out_rows_c1[i] = sets[2 * i + 1]; }
     return FHE_OK;
 }

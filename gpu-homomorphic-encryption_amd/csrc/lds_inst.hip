@@ -137,6 +137,16 @@ static bool launch(const LdsArgs &A) {
         }
         return false;
     }
+    // RGSW key generation: the same, with the table of (tables, message, component) and the packed transformed s alone
+    if (A.op == LDS_RGSW_KEYGEN) {
+        if constexpr (lds_keygen(EB, LOGN)) {
+            if (in || out || !A.a0 || !A.kb || !A.cdt || !A.cdt_len || A.cdt_len > ENCRYPT_MAX_CDT || !A.K || !A.w || A.polys % (A.L * A.K * A.L)) return false;
+            hipLaunchKernelGGL((ntt_rgsw_keygen_kernel<F, LOGN, 2>), grid, block, 0, A.stream, (const RgswSet *)A.a0, (const E *)A.kb, A.cdt, A.cdt_len,
+                               A.seeds[0], A.seeds[1], A.t, limbs, A.L, A.K, A.w);
+            return true;
+        }
+        return false;
+    }
     // Batch encoder: this instance is the field of the plaintext modulus; slot words in, containers out / words or containers in, slot words out
     if (A.op == LDS_SLOTS_ENCODE || A.op == LDS_SLOTS_DECODE) {
         if constexpr (lds_slots(EB, LOGN)) {

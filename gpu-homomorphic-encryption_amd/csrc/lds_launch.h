@@ -11,13 +11,14 @@ namespace fhe_dev {
 // LDS_HOIST / LDS_HOIST_APPLY: hoisted rotations (hoist.hip.h), one form each.  LDS_HOIST_FWD / LDS_HOIST_LINCOMB: the two launches of the
 // hoisted linear transform (hoist_lincomb.hip.h), one form each.  LDS_ENCRYPT: public-key encryption with in-kernel sampling (encrypt.hip.h),
 // one kernel on two grids (LdsArgs::per_ct).  LDS_DECRYPT: the first launch of secret-key decryption (decrypt.hip.h), one form.
-// LDS_KEYGEN: key-switching key generation with in-kernel sampling (keygen.hip.h), one form.
+// LDS_KEYGEN: key-switching key generation with in-kernel sampling (keygen.hip.h), one form.  LDS_RGSW_KEYGEN: its sibling for RGSW rows
+// (the gadget term is mu or mu s instead of a Galois target), one form, wherever LDS_KEYGEN exists.
 // LDS_SLOTS_ENCODE / LDS_SLOTS_DECODE: the batch encoder (encode.hip.h), one form each, on the instance of the PLAINTEXT modulus' field.
 // The last five: transforms beyond the LDS range (N = 2^(13 + top), top = 1..3; served by the LOGN = 13 instances): the register-only pass
 // over the top stages and the sub-transforms of the 2^top blocks
 #define LDS_OPS(X) X(LDS_FORWARD, "forward") X(LDS_INVERSE, "inverse") X(LDS_MULTIPLY, "multiply") X(LDS_CT_MULTIPLY, "tensor product") \
     X(LDS_KEYSWITCH, "key switch") X(LDS_EXTPROD, "external product") X(LDS_HOIST, "hoist") X(LDS_HOIST_APPLY, "hoisted rotation") \
-    X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") X(LDS_ENCRYPT, "encryption") X(LDS_DECRYPT, "decryption") X(LDS_KEYGEN, "key generation") \
+    X(LDS_HOIST_FWD, "hoist-order forward") X(LDS_HOIST_LINCOMB, "hoisted linear transform") X(LDS_ENCRYPT, "encryption") X(LDS_DECRYPT, "decryption") X(LDS_KEYGEN, "key generation") X(LDS_RGSW_KEYGEN, "RGSW key generation") \
     X(LDS_SLOTS_ENCODE, "slot encoding") X(LDS_SLOTS_DECODE, "slot decoding") \
     X(LDS_PASS_FWD, "pass forward") X(LDS_PASS_INV, "pass inverse") X(LDS_SUB_FORWARD, "sub forward") X(LDS_SUB_INVERSE, "sub inverse") X(LDS_SUB_MULTIPLY, "sub multiply")
 #define LDS_ENUMERATOR(id, name) id,
@@ -123,6 +124,13 @@ struct KeygenSet {
     uint32_t g, _pad;
 };
 
+// One half of an RGSW ciphertext of an RGSW key-generation call (device table read by ntt_rgsw_keygen_kernel): the packed tables of the
+// component's rows, the message and the component (0: gadget term mu, 1: mu s)
+struct RgswSet {
+    void *kb, *ka;
+    int32_t mu; uint32_t comp;
+};
+
 // One launch request.  The host fills the members that are operands of ITS op, by name (lds_args of engine.h sets the common ones from the
 // engine and the plan); everything else keeps its default.
 struct LdsArgs {
@@ -163,6 +171,7 @@ struct LdsArgs {
     // nullptr (containers); kb / ka = the packed transformed s and s^2 ([L][n] residues each); polys = ciphertexts x limbs, out_compact set
     // LDS_KEYGEN: a0 = KeygenSet[polys / (L K L)] (device): both packed tables of every set are written; kb / ka = the packed transformed s and s^2;
     // cdt / cdt_len as LDS_ENCRYPT; seeds[0], seeds[1] = the streams of a and e; t = the noise scale; polys = sets x rows x limbs
+    // LDS_RGSW_KEYGEN: as LDS_KEYGEN with a0 = RgswSet[polys / (L K L)] (device) and kb = the packed transformed s alone
     // LDS_SLOTS_ENCODE: r0 = [polys][L][n] containers = the plaintexts of a0 = [polys][n] slot values (8-byte words: in_compact set); kb = the
     // position -> slot table (uint32_t[n]), ka = ModT[L], the reduction modulo the target's q_l (t == 0: none); limbs = the ONE limb of the
     // encoder's engine on (n, t); L = limbs of the TARGET engine; polys = plaintexts

@@ -71,6 +71,19 @@ struct GaloisKeys {                                           // include/fhe.cuh
     }
 };
 
+// The key of FHEContext::bootstrap / blind_rotate (include/fhe.cuh:119, 139, declared only): one RGSW encryption under the ring key per
+// element of the LWE secret, each two engine-side row sets (fhe_rgsw_keys_generate), in the order fhe_blind_rotate takes them
+struct BootstrapKey {
+    std::vector<fhe_relin_keys_t *> rows_c0, rows_c1;
+    uint32_t decomp_bits = 16;
+    const void *made_for = nullptr;        // the engine whose handles these are (FHEContext::blind_rotate_lwe refuses another context's key)
+    BootstrapKey() = default;
+    BootstrapKey(const BootstrapKey &) = delete;
+    BootstrapKey &operator=(const BootstrapKey &) = delete;
+    void clear() { for (auto *v : {&rows_c0, &rows_c1}) { for (fhe_relin_keys_t *k : *v) fhe_relin_keys_destroy(k); v->clear(); } }
+    ~BootstrapKey() { clear(); }
+};
+
 struct Plaintext {                                            // include/fhe.cuh:72-75
     Polynomial *poly = nullptr;
     bool is_ntt_form = false;
@@ -429,6 +442,48 @@ public:
         gal_keys.elements.insert(gal_keys.elements.end(), elts.begin(), elts.end());
         gal_keys.imported_for = params_.rns_ntt;
     }
+    // Programmable bootstrapping around fhe_blind_rotate (FHEContext::bootstrap / blind_rotate, include/fhe.cuh:119, 139, declared only).
+    // bootstrap_key_gen: RGSW encryptions of the LWE secret's bits under sk in ONE engine call; noise scale 1 (the blind rotation reads the
+    // phase modulo Q: there is no plaintext modulus for the noise to be a multiple of), sigma = security.sigma, seeds from the context generator.
+    void bootstrap_key_gen(BootstrapKey &bk, const SecretKey &sk, const std::vector<int32_t> &lwe_secret_bits, uint32_t decomp_bits = 16) {
+        if (lwe_secret_bits.empty()) throw std::runtime_error("FHEContext::bootstrap_key_gen: the LWE secret is empty");
+        for (int32_t b : lwe_secret_bits)
+            if (b != 0 && b != 1) throw std::runtime_error("FHEContext::bootstrap_key_gen: the LWE secret must be binary (a ternary secret needs two RGSW ciphertexts per element)");
+        const uint64_t seeds[2] = {rng_(), rng_()};
+        std::vector<fhe_relin_keys_t *> r0(lwe_secret_bits.size(), nullptr), r1(lwe_secret_bits.size(), nullptr);
+        check(fhe_rgsw_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, lwe_secret_bits.data(), (uint32_t)lwe_secret_bits.size(), 1,
+                                     (double)params_.security.sigma, seeds, r0.data(), r1.data()), "FHEContext::bootstrap_key_gen");
+        bk.clear();
+        bk.rows_c0 = std::move(r0); bk.rows_c1 = std::move(r1); bk.decomp_bits = decomp_bits; bk.made_for = params_.rns_ntt;
+    }
+    // lwe: [batch][n_lwe + 1] values below q_lwe, (a_0 .. a_{n_lwe-1}, b) with phase b + sum a_i z_i, n_lwe = the size of the key; test_vector: one
+    // top-level polynomial.  out_lwe: [batch][L][n + 1] residues, coefficient idx of X^(-phase~) test_vector as an LWE sample under the ring key
+    // (fhe_lwe_prepare_accumulator -> fhe_blind_rotate -> fhe_rlwe_sample_extract on buffers owned by the call).
+    void blind_rotate_lwe(std::vector<uint64_t> &out_lwe, const std::vector<uint64_t> &lwe, uint64_t q_lwe, const Polynomial &test_vector, const BootstrapKey &bk,
+                          uint32_t idx = 0) {
+        const uint32_t n_lwe = (uint32_t)bk.rows_c0.size(), n = params_.n, L = num_levels();
+        if (!n_lwe || bk.rows_c1.size() != n_lwe) throw std::runtime_error("FHEContext::blind_rotate_lwe: the bootstrapping key is empty");
+        if (bk.made_for != params_.rns_ntt) throw std::runtime_error("FHEContext::blind_rotate_lwe: the bootstrapping key was generated by another context");
+        if (lwe.empty() || lwe.size() % (n_lwe + 1)) throw std::runtime_error("FHEContext::blind_rotate_lwe: lwe must hold batch x (n_lwe + 1) values");
+        const uint32_t batch = (uint32_t)(lwe.size() / (n_lwe + 1));
+        const size_t poly = (size_t)L * n, acc = poly * batch;                             // containers
+        auto containers = [](size_t bytes) { return (bytes + sizeof(uint256_t) - 1) / sizeof(uint256_t); };
+        const size_t lwe_c = containers(lwe.size() * 8), sh_c = containers((size_t)n_lwe * batch * 4), out_c = containers((size_t)batch * L * (n + 1) * 8);
+        uint256_t *d = device_alloc(4 * acc + lwe_c + sh_c + out_c);
+        try {
+            uint256_t *a0 = d, *a1 = d + acc, *t0 = d + 2 * acc, *t1 = d + 3 * acc, *d_lwe = d + 4 * acc, *d_sh = d_lwe + lwe_c, *d_out = d_sh + sh_c;
+            fhe_rns_ntt_t *h = params_.rns_ntt->handle();
+            check(fhe_hip_memcpy_h2d(d_lwe, lwe.data(), lwe.size() * 8), "memcpy h2d");
+            check(fhe_lwe_prepare_accumulator(h, q_lwe, n_lwe, (const uint64_t *)d_lwe, test_vector.coeffs, a0, a1, (uint32_t *)d_sh, batch), "blind_rotate_lwe: prepare");
+            check(fhe_blind_rotate(h, bk.rows_c0.data(), bk.rows_c1.data(), n_lwe, a0, a1, (const uint32_t *)d_sh, t0, t1, batch), "blind_rotate_lwe: blind rotation");
+            check(fhe_rlwe_sample_extract(h, (uint64_t *)d_out, a0, a1, idx, batch), "blind_rotate_lwe: sample extraction");
+            device_synchronize();
+            out_lwe.resize((size_t)batch * L * (n + 1));
+            check(fhe_hip_memcpy_d2h(out_lwe.data(), d_out, out_lwe.size() * 8), "memcpy d2h");
+        } catch (...) { device_free(d); throw; }
+        device_free(d);
+    }
+
     void galoiskey_gen_fused(GaloisKeys &gal_keys, const SecretKey &sk) {                   // the default set of galoiskey_gen
         std::vector<int> steps;
         for (uint32_t s = 1; s < params_.n / 2; s <<= 1) { steps.push_back((int)s); steps.push_back(-(int)s); }

@@ -516,6 +516,52 @@ int fhe_keyswitch_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, ui
  * [num_keys][L][n] canonical containers in coefficient form (num_keys = L K; packed sets are unpacked first).  Outputs must be distinct. */
 int fhe_relin_keys_export(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, void *d_keys_b, void *d_keys_a);
 
+/* ---- programmable bootstrapping around the blind-rotation loop -----------------------------------------------------------------------
+ * FHEContext::bootstrap / blind_rotate / extract_lsb (include/fhe.cuh:119, 138-140, declared only; pipeline prose README.md:146-159): an LWE
+ * ciphertext in, fhe_blind_rotate over RGSW encryptions of the LWE secret's bits, one coefficient of the accumulator out as an LWE sample of
+ * f(m) under the ring key.  For moduli below 2^64 only: the word-sized width classes, and the sizes n < 2^11 that have no word-sized kernels (such
+ * an engine reports FHE_WIDTH_256 for its size; the streaming kernels and the composed key generation serve it).  An engine with a modulus of
+ * 2^64 or more gets FHE_ERR_UNSUPPORTED from all three calls, nothing launched.
+ *
+ * Phase.  Everything uses the library's phase c0 + c1 s.  An LWE ciphertext is n_lwe + 1 values (a_0 .. a_{n_lwe-1}, b), phase b + sum a_i z_i.
+ * Input LWE.  d_lwe is [batch][n_lwe + 1] uint64_t, every value below q_lwe, 2 <= q_lwe <= 2^48 (so v 2n + q_lwe/2 < 2^64).  The switch to
+ *   modulus 2n is ms(v) = floor((v 2n + floor(q_lwe / 2)) / q_lwe) mod 2n; b~ = ms(b), a~_i = ms(a_i).  A value >= q_lwe is the CALLER'S error,
+ *   as a non-canonical coefficient is everywhere else: the result is then unspecified (nothing is read or written out of bounds).
+ * Accumulator.  d_tv is ONE [L][n] canonical container polynomial shared by the batch, the test vector.  acc0[b] = X^(2n - b~_b) tv, negacyclic
+ *   and canonical: coefficient x comes from index i = (x + b~) mod 2n and is tv[i] if i < n, else (q - tv[i - n]) mod q.  acc1[b] = 0.
+ *   shifts[i][b] = (2n - a~_i) mod 2n, laid out [n_lwe][batch] as fhe_blind_rotate reads it.
+ * Result of the loop.  After fhe_blind_rotate with RGSW encryptions of z_i in {0, 1} the accumulator has phase X^(-phi~) tv + noise,
+ *   phi~ = (b~ + sum a~_i z_i) mod 2n: its constant coefficient is tv[phi~] for phi~ < n and -tv[phi~ - n] otherwise.
+ * Extraction at idx < n.  The output is [batch][L][n + 1] uint64_t residues, limb l modulo q_l: out[n] = c0[idx]; out[j] = c1[idx - j] for
+ *   j <= idx; out[j] = (q_l - c1[n + idx - j]) mod q_l for j > idx.  Hence out[n] + sum out[j] s_j = (c0 + c1 s)[idx] in every limb.
+ * RGSW rows.  The layout of fhe_blind_rotate's rows, with K, U_P, e_P and the "uniform taken as the NTT-domain value of a" convention of
+ *   fhe_keyswitch_keys_generate: message mu_i, component c in {0, 1}, polynomial index P = (2 i + c) L K + r, row r = j K + k,
+ *       b_P[l] = -a_P[l] (*) s[l] + [noise_scale e_P]_{q_l} + (l == j ? (2^(k w) mod q_j) T : 0),   T = mu_i (the constant polynomial) for c = 0,
+ *   T = mu_i s for c = 1 -- with a' = a + g mu this is exactly RLWE(0) + (0, g mu).  mu_i is a host int32_t, |mu_i| <= 2^15; a negative value
+ *   embeds as q - |mu|.
+ *
+ * fhe_rgsw_keys_generate: `num` RGSW ciphertexts, each two handles (out_rows_c0[i], out_rows_c1[i]) that are bit for bit what
+ * fhe_relin_keys_create returns for the rows above: fhe_blind_rotate, fhe_relin_keys_export and fhe_relin_keys_destroy take them unchanged.
+ * Where fhe_keyswitch_keys_generate is one launch (N = 2^11 .. 2^14, packed key sets, a secret key with packed transforms, sigma <= 85) this
+ * call is ONE launch too (for c = 0 the gadget term is a constant at every NTT position, for c = 1 it is mu 2^(k w) s^[y] read from the packed
+ * transform of s); everywhere else and under FHE_HIP_NO_FUSED_KEYGEN=1 it composes the samplers, transforms and element-wise kernels like
+ * fhe_keyswitch_keys_generate, through scratch of (L K + 2) S bytes freed before it returns.  Same bits on either path.
+ * FHE_ERR_INVALID_ARG with nothing launched, nothing allocated and the outputs untouched: a null argument; out_rows_c0 == out_rows_c1; a key
+ * of another engine; num == 0; decomp_bits outside [1, 64]; |mu_i| > 2^15; noise_scale == 0; a sigma fhe_gaussian_cdt rejects; ceil(12 sigma)
+ * not below the smallest modulus.  On a failure after that every handle made so far is destroyed and every output is NULL. */
+int fhe_rgsw_keys_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t decomp_bits, const int32_t *mu, uint32_t num,
+                           uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_relin_keys_t **out_rows_c0, fhe_relin_keys_t **out_rows_c1);
+/* The loop's inputs from `batch` LWE ciphertexts: d_acc0, d_acc1 ([batch][L][n] containers each) and d_shifts ([n_lwe][batch] uint32_t) as
+ * above.  ONE launch for any n >= 8, no workspace, nothing allocated (capturable into a hipGraph); tv is read through L2.  FHE_ERR_INVALID_ARG
+ * with nothing launched: a null pointer; d_tv / d_acc0 / d_acc1 not 16-byte, d_lwe not 8-byte or d_shifts not 4-byte aligned; outputs that
+ * overlap each other or an input; batch == 0; n_lwe == 0; q_lwe outside [2, 2^48]. */
+int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uint32_t n_lwe, const uint64_t *d_lwe, const void *d_tv, void *d_acc0, void *d_acc1,
+                                uint32_t *d_shifts, uint32_t batch);
+/* Coefficient idx of `batch` RLWE pairs (d_c0, d_c1: [batch][L][n] containers) as LWE samples, d_out = [batch][L][n + 1] uint64_t as above.
+ * ONE launch for any n >= 8, no workspace.  FHE_ERR_INVALID_ARG with nothing launched: a null pointer; misaligned d_c0 / d_c1 (16 bytes) or
+ * d_out (8 bytes); an output that overlaps an input; batch == 0; idx >= n. */
+int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t idx, uint32_t batch);
+
 /* ---- batch encoder: slot values <-> plaintext polynomials on the device --------------------------------------------------------------
  * FHEContext::encode / decode and BatchEncoder (include/fhe.cuh:89-90, 150-157).  With psi = fhe_find_psi(n, t) and e(i) the exponent of slot i:
  *   FHE_SLOTS_NATURAL  e(i) = 2 i + 1                                          (what the mirror's host encode / decode evaluate)
