@@ -47,8 +47,9 @@ def _outputs(v, t, scale):
     return m, bits
 
 
-def _expected(oracle, n, moduli, comps, s, t=T, scale=1):
-    """comps: 2 or 3 arrays [batch][L][n][4]; s: [L][n][4].  The definition, by the oracle's polymul and Python integers."""
+def _residues(oracle, n, moduli, comps, s):
+    """comps: 2 or 3 arrays [batch][L][n][4]; s: [L][n][4].  c0 + c1 s (+ c2 s^2) per limb as Python integers [batch][L][n], NOT reduced:
+    _crt_centred reduces them."""
     rp = oracle.RnsPlan(n, moduli)
     batch = comps[0].shape[0]
     sb = np.ascontiguousarray(np.broadcast_to(s[None], comps[1].shape))
@@ -58,7 +59,12 @@ def _expected(oracle, n, moduli, comps, s, t=T, scale=1):
         s2b = np.ascontiguousarray(np.broadcast_to(s2, comps[2].shape))
         res = res + _ints(rp.polymul(np.ascontiguousarray(comps[2]), s2b, threads=8))
     assert res.shape == (batch, len(moduli), n)
-    return _outputs(_crt_centred(res, moduli), t, scale)
+    return res
+
+
+def _expected(oracle, n, moduli, comps, s, t=T, scale=1):
+    """The definition, by the oracle's polymul and Python integers."""
+    return _outputs(_crt_centred(_residues(oracle, n, moduli, comps, s), moduli), t, scale)
 
 
 def _primes(bits, n, count):
