@@ -128,6 +128,13 @@ def lib():
         "fhe_rgsw_keys_generate": ([vp, vp, u32, P(ctypes.c_int32), u32, u64, ctypes.c_double, P(u64), P(vp), P(vp)], ci),
         "fhe_lwe_prepare_accumulator": ([vp, u64, u32, vp, vp, vp, vp, vp, u32], ci),
         "fhe_rlwe_sample_extract": ([vp, vp, vp, vp, u32, u32], ci),
+        "fhe_lwe_ksk_num_digits": ([vp, u32, P(u32)], ci),
+        "fhe_lwe_ksk_create": ([vp, P(vp), u32, u32, vp], ci),
+        "fhe_lwe_ksk_export": ([vp, vp, vp], ci),
+        "fhe_lwe_ksk_destroy": ([vp], ci),
+        "fhe_lwe_ksk_bytes": ([vp, P(u64)], ci),
+        "fhe_lwe_ksk_generate": ([vp, vp, u32, u32, P(ctypes.c_int32), u64, ctypes.c_double, P(u64), P(vp)], ci),
+        "fhe_lwe_keyswitch": ([vp, vp, u64, vp, vp, u32], ci),
         "fhe_batch_encoder_create": ([vp, P(vp), u64, ci], ci),
         "fhe_batch_encoder_destroy": ([vp], ci),
         "fhe_batch_encoder_reserve": ([vp, vp, u32], ci),
@@ -572,6 +579,35 @@ class RnsNttEngine:
         """Coefficient idx of (c0, c1) as LWE samples: d_out = device uint64 [batch][L][n + 1]."""
         _check(lib().fhe_rlwe_sample_extract(self.h, _ptr(d_out), _ptr(d_c0), _ptr(d_c1), idx, batch))
 
+    def lwe_ksk_num_digits(self, decomp_bits):
+        """K = ceil(bit_length(q_0) / decomp_bits): the LWE key-switching key of this engine has n K rows."""
+        k = ctypes.c_uint32(0); _check(lib().fhe_lwe_ksk_num_digits(self.h, decomp_bits, ctypes.byref(k))); return k.value
+
+    def import_lwe_ksk(self, decomp_bits, n_out, d_rows):
+        """d_rows: device uint64 [n K][n_out + 1], row j K + k = (a_0 .. a_{n_out-1}, b) encrypting s_j 2^(k w) under z.  Copied."""
+        out = ctypes.c_void_p()
+        _check(lib().fhe_lwe_ksk_create(self.h, ctypes.byref(out), decomp_bits, n_out, _ptr(d_rows)))
+        return LweKeySwitchKey(out, n_out)
+
+    def generate_lwe_ksk(self, sk, decomp_bits, z, noise_scale, sigma, seeds):
+        """The LWE key-switching key from the ring key `sk` (limb 0) to the small key z (integers, |z_i| <= 2^15), generated on the device
+        with seeds = (a, e).  Returns the key object, as import_lwe_ksk would for the same table."""
+        k = len(z)
+        zs = (ctypes.c_int32 * max(k, 1))(*[int(v) for v in z])
+        sd = (ctypes.c_uint64 * 2)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
+        out = ctypes.c_void_p()
+        _check(lib().fhe_lwe_ksk_generate(self.h, sk.h, decomp_bits, k, zs, noise_scale, sigma, sd, ctypes.byref(out)))
+        return LweKeySwitchKey(out, k)
+
+    def export_lwe_ksk(self, ksk, d_rows):
+        """The canonical table [n K][n_out + 1] of any LWE key-switching key (the inverse of import_lwe_ksk)."""
+        _check(lib().fhe_lwe_ksk_export(self.h, ksk.h, _ptr(d_rows)))
+
+    def lwe_keyswitch(self, ksk, d_out, d_in, q_out=0, batch=1):
+        """d_in: device uint64 [batch][n + 1] under the ring key -> d_out [batch][n_out + 1] under the small key; q_out != 0 also switches
+        the modulus to q_out (at most 2^48) with rounding."""
+        _check(lib().fhe_lwe_keyswitch(self.h, ksk.h, q_out, _ptr(d_out), _ptr(d_in), batch))
+
     def export_keys(self, rk, d_keys_b, d_keys_a):
         """The rows of any key set as [L*K][L][n] canonical containers in coefficient form (the inverse of import_relin_keys)."""
         _check(lib().fhe_relin_keys_export(self.h, rk.h, _ptr(d_keys_b), _ptr(d_keys_a)))
@@ -599,6 +635,26 @@ class RelinKeys:
     def close(self):
         if self.h:
             lib().fhe_relin_keys_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LweKeySwitchKey:
+    """An LWE key-switching key (ring key -> small LWE key), owned by the library; bound to (n, q_0, device), not to one engine."""
+
+    def __init__(self, h, n_out):
+        self.h, self.n_out = h, n_out
+
+    def nbytes(self):
+        b = ctypes.c_uint64(0); _check(lib().fhe_lwe_ksk_bytes(self.h, ctypes.byref(b))); return b.value
+
+    def close(self):
+        if self.h:
+            lib().fhe_lwe_ksk_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -19,6 +19,8 @@
 //                   kernels of encode.hip.h around do_inverse / do_forward)
 //   bootstrap.hip   around the blind-rotation loop: LWE ciphertexts -> accumulators and shift table, sample extraction (bootstrap.hip.h); the RGSW
 //                   rows of the loop come from keygen.hip (fhe_rgsw_keys_generate)
+//   lwe_keyswitch.hip  after the loop: the LWE key-switching key (its one key object, import / export / generation) and the key switch of an
+//                   extracted sample back to the small LWE key, with the optional modulus switch (lwe_keyswitch.hip.h)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once

@@ -72,15 +72,21 @@ struct GaloisKeys {                                           // include/fhe.cuh
 };
 
 // The key of FHEContext::bootstrap / blind_rotate (include/fhe.cuh:119, 139, declared only): one RGSW encryption under the ring key per
-// element of the LWE secret, each two engine-side row sets (fhe_rgsw_keys_generate), in the order fhe_blind_rotate takes them
+// element of the LWE secret, each two engine-side row sets (fhe_rgsw_keys_generate), in the order fhe_blind_rotate takes them, and the LWE
+// key-switching key from the ring key (first prime) back to the LWE secret (fhe_lwe_ksk_generate), which has a digit width of its own
 struct BootstrapKey {
     std::vector<fhe_relin_keys_t *> rows_c0, rows_c1;
     uint32_t decomp_bits = 16;
-    const void *made_for = nullptr;        // the engine whose handles these are (FHEContext::blind_rotate_lwe refuses another context's key)
+    fhe_lwe_ksk_t *lwe_ksk = nullptr;      // n K rows of n_lwe + 1 residues modulo the first prime (FHEContext::bootstrap_lwe)
+    uint32_t ks_decomp_bits = 8;
+    const void *made_for = nullptr;        // the engine whose handles these are (FHEContext::blind_rotate_lwe / bootstrap_lwe refuse another context's key)
     BootstrapKey() = default;
     BootstrapKey(const BootstrapKey &) = delete;
     BootstrapKey &operator=(const BootstrapKey &) = delete;
-    void clear() { for (auto *v : {&rows_c0, &rows_c1}) { for (fhe_relin_keys_t *k : *v) fhe_relin_keys_destroy(k); v->clear(); } }
+    void clear() {
+        for (auto *v : {&rows_c0, &rows_c1}) { for (fhe_relin_keys_t *k : *v) fhe_relin_keys_destroy(k); v->clear(); }
+        fhe_lwe_ksk_destroy(lwe_ksk); lwe_ksk = nullptr;
+    }
     ~BootstrapKey() { clear(); }
 };
 
@@ -445,16 +451,24 @@ public:
     // Programmable bootstrapping around fhe_blind_rotate (FHEContext::bootstrap / blind_rotate, include/fhe.cuh:119, 139, declared only).
     // bootstrap_key_gen: RGSW encryptions of the LWE secret's bits under sk in ONE engine call; noise scale 1 (the blind rotation reads the
     // phase modulo Q: there is no plaintext modulus for the noise to be a multiple of), sigma = security.sigma, seeds from the context generator.
-    void bootstrap_key_gen(BootstrapKey &bk, const SecretKey &sk, const std::vector<int32_t> &lwe_secret_bits, uint32_t decomp_bits = 16) {
+    // The LWE key-switching key back to the LWE secret comes from the same call, with its own digit width ks_decomp_bits (the RGSW width does
+    // not fit its noise: DESIGN 4.16) and its own pair of seeds, drawn after the RGSW pair.
+    void bootstrap_key_gen(BootstrapKey &bk, const SecretKey &sk, const std::vector<int32_t> &lwe_secret_bits, uint32_t decomp_bits = 16,
+                           uint32_t ks_decomp_bits = 8) {
         if (lwe_secret_bits.empty()) throw std::runtime_error("FHEContext::bootstrap_key_gen: the LWE secret is empty");
         for (int32_t b : lwe_secret_bits)
             if (b != 0 && b != 1) throw std::runtime_error("FHEContext::bootstrap_key_gen: the LWE secret must be binary (a ternary secret needs two RGSW ciphertexts per element)");
-        const uint64_t seeds[2] = {rng_(), rng_()};
-        std::vector<fhe_relin_keys_t *> r0(lwe_secret_bits.size(), nullptr), r1(lwe_secret_bits.size(), nullptr);
-        check(fhe_rgsw_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, lwe_secret_bits.data(), (uint32_t)lwe_secret_bits.size(), 1,
+        const uint64_t seeds[2] = {rng_(), rng_()}, ks_seeds[2] = {rng_(), rng_()};
+        const uint32_t n_lwe = (uint32_t)lwe_secret_bits.size();
+        std::vector<fhe_relin_keys_t *> r0(n_lwe, nullptr), r1(n_lwe, nullptr);
+        check(fhe_rgsw_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, lwe_secret_bits.data(), n_lwe, 1,
                                      (double)params_.security.sigma, seeds, r0.data(), r1.data()), "FHEContext::bootstrap_key_gen");
         bk.clear();
         bk.rows_c0 = std::move(r0); bk.rows_c1 = std::move(r1); bk.decomp_bits = decomp_bits; bk.made_for = params_.rns_ntt;
+        const int rc = fhe_lwe_ksk_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), ks_decomp_bits, n_lwe, lwe_secret_bits.data(), 1,
+                                            (double)params_.security.sigma, ks_seeds, &bk.lwe_ksk);
+        if (rc) { bk.clear(); bk.made_for = nullptr; check(rc, "FHEContext::bootstrap_key_gen: LWE key-switching key"); }
+        bk.ks_decomp_bits = ks_decomp_bits;
     }
     // lwe: [batch][n_lwe + 1] values below q_lwe, (a_0 .. a_{n_lwe-1}, b) with phase b + sum a_i z_i, n_lwe = the size of the key; test_vector: one
     // top-level polynomial.  out_lwe: [batch][L][n + 1] residues, coefficient idx of X^(-phase~) test_vector as an LWE sample under the ring key
@@ -479,6 +493,49 @@ public:
             check(fhe_rlwe_sample_extract(h, (uint64_t *)d_out, a0, a1, idx, batch), "blind_rotate_lwe: sample extraction");
             device_synchronize();
             out_lwe.resize((size_t)batch * L * (n + 1));
+            check(fhe_hip_memcpy_d2h(out_lwe.data(), d_out, out_lwe.size() * 8), "memcpy d2h");
+        } catch (...) { device_free(d); throw; }
+        device_free(d);
+    }
+
+    // FHEContext::bootstrap (include/fhe.cuh:119, declared only) as one chainable call: lwe is [batch][n_lwe + 1] values below q_lwe under the
+    // LWE secret of bk; out_lwe is [batch][n_lwe + 1] under the SAME secret, an LWE ciphertext of the test vector's entry at the input's phase,
+    // modulo the first prime q_0 (q_out == 0) or modulo q_out (2 <= q_out <= 2^48, rounded in the key-switch launch).  It can be the `lwe` of the
+    // next call (q_lwe = q_0 or q_out): give the test vector the half-slot offset Delta f + Delta / 2 so that the output sits mid-slot.  On
+    // buffers owned by the call: fhe_lwe_prepare_accumulator -> fhe_blind_rotate -> fhe_rns_rescale_drop_last of both accumulators down the level
+    // engines to one prime -> fhe_rlwe_sample_extract on the one-limb engine -> fhe_lwe_keyswitch.  Every engine of the context has a stream of
+    // its own, so the call synchronises the device where the work passes from one engine to the next.
+    void bootstrap_lwe(std::vector<uint64_t> &out_lwe, const std::vector<uint64_t> &lwe, uint64_t q_lwe, const Polynomial &test_vector, const BootstrapKey &bk,
+                       uint64_t q_out = 0, uint32_t idx = 0) {
+        const uint32_t n_lwe = (uint32_t)bk.rows_c0.size(), n = params_.n, L = num_levels();
+        if (!n_lwe || bk.rows_c1.size() != n_lwe || !bk.lwe_ksk) throw std::runtime_error("FHEContext::bootstrap_lwe: the bootstrapping key is empty");
+        if (bk.made_for != params_.rns_ntt) throw std::runtime_error("FHEContext::bootstrap_lwe: the bootstrapping key was generated by another context");
+        if (lwe.empty() || lwe.size() % (n_lwe + 1)) throw std::runtime_error("FHEContext::bootstrap_lwe: lwe must hold batch x (n_lwe + 1) values");
+        const uint32_t batch = (uint32_t)(lwe.size() / (n_lwe + 1));
+        const size_t poly = (size_t)L * n, acc = poly * batch;                             // containers
+        auto containers = [](size_t bytes) { return (bytes + sizeof(uint256_t) - 1) / sizeof(uint256_t); };
+        const size_t lwe_c = containers(lwe.size() * 8), sh_c = containers((size_t)n_lwe * batch * 4), ext_c = containers((size_t)batch * (n + 1) * 8);
+        uint256_t *d = device_alloc(4 * acc + 2 * lwe_c + sh_c + ext_c);
+        try {
+            uint256_t *cur0 = d, *cur1 = d + acc, *oth0 = d + 2 * acc, *oth1 = d + 3 * acc, *d_lwe = d + 4 * acc, *d_out = d_lwe + lwe_c, *d_sh = d_out + lwe_c,
+                      *d_ext = d_sh + sh_c;
+            fhe_rns_ntt_t *h = params_.rns_ntt->handle();
+            check(fhe_hip_memcpy_h2d(d_lwe, lwe.data(), lwe.size() * 8), "memcpy h2d");
+            check(fhe_lwe_prepare_accumulator(h, q_lwe, n_lwe, (const uint64_t *)d_lwe, test_vector.coeffs, cur0, cur1, (uint32_t *)d_sh, batch), "bootstrap_lwe: prepare");
+            check(fhe_blind_rotate(h, bk.rows_c0.data(), bk.rows_c1.data(), n_lwe, cur0, cur1, (const uint32_t *)d_sh, oth0, oth1, batch), "bootstrap_lwe: blind rotation");
+            for (uint32_t level = 0; level + 1 < L; level++) {                            // [batch][L - level][n] -> [batch][L - level - 1][n]
+                fhe_rns_ntt_t *hl = engine(level).handle();
+                if (level) device_synchronize();                                          // the previous level's engine wrote cur0 / cur1
+                check(fhe_rns_rescale_drop_last(hl, oth0, cur0, batch), "bootstrap_lwe: rescale");
+                check(fhe_rns_rescale_drop_last(hl, oth1, cur1, batch), "bootstrap_lwe: rescale");
+                std::swap(cur0, oth0); std::swap(cur1, oth1);
+            }
+            fhe_rns_ntt_t *h1 = engine(L - 1).handle();                                   // the one-limb engine (the context's own when L == 1)
+            if (L > 1) device_synchronize();
+            check(fhe_rlwe_sample_extract(h1, (uint64_t *)d_ext, cur0, cur1, idx, batch), "bootstrap_lwe: sample extraction");
+            check(fhe_lwe_keyswitch(h1, bk.lwe_ksk, q_out, (uint64_t *)d_out, (const uint64_t *)d_ext, batch), "bootstrap_lwe: key switch");
+            device_synchronize();
+            out_lwe.resize(lwe.size());
             check(fhe_hip_memcpy_d2h(out_lwe.data(), d_out, out_lwe.size() * 8), "memcpy d2h");
         } catch (...) { device_free(d); throw; }
         device_free(d);

@@ -562,6 +562,61 @@ int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uint32_t n_lwe
  * d_out (8 bytes); an output that overlaps an input; batch == 0; idx >= n. */
 int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t idx, uint32_t batch);
 
+/* ---- LWE key switch back to the small key: chainable bootstrapping -------------------------------------------------------------------
+ * The last step of FHEContext::bootstrap (include/fhe.cuh:119, declared only; README.md:146-159): the sample that fhe_rlwe_sample_extract
+ * leaves is under the RING key s (dimension n, modulus q); the next fhe_lwe_prepare_accumulator wants dimension n_lwe, the small key z and one
+ * modulus of at most 2^48.  This block switches the key, and optionally the modulus, in one launch.  Phase b + sum a_i z_i as above.  For
+ * moduli below 2^64: an engine with a wider modulus gets FHE_ERR_UNSUPPORTED from every call that takes one, nothing launched.
+ *
+ * Definitions.  q = the modulus of LIMB 0 of the engine (the level-0 engine and the one-limb level engine on the same first prime both do);
+ *   n_in = h->n; w = decomp_bits in [1, 32]; K = ceil(bit_length(q) / w) (fhe_lwe_ksk_num_digits); R = n_in K.  Row r = j K + k (j < n_in,
+ *   k < K) encrypts s_j 2^(k w) under z, an array of n_out small integers.
+ * Key object.  Canonical form: a row-major table [R][n_out + 1] of uint64_t below q, row r = (a_{r,0} .. a_{r,n_out-1}, b_r).  Inside the
+ *   object a row is padded with zeros to a multiple of 64 columns, so that one wave instruction of the apply kernel reads 512 consecutive
+ *   bytes of a row (fhe_lwe_ksk_bytes reports the padded size).  A key is bound to (n_in, q, device), not to one engine handle.
+ *
+ * fhe_lwe_ksk_create imports the canonical table from a device pointer, 8-byte aligned, and copies it (complete when the call returns);
+ *   values >= q are the caller's error, as non-canonical coefficients are everywhere else.  fhe_lwe_ksk_export is its inverse for a key
+ *   however it was made (enqueued on h's stream).  fhe_lwe_ksk_destroy(NULL) is FHE_OK.  FHE_ERR_INVALID_ARG with *out untouched: a null
+ *   argument, a misaligned pointer, decomp_bits outside [1, 32], n_out == 0 or n_out > 65536, (export) an engine that does not match the key.
+ *
+ * fhe_lwe_ksk_generate.  z is a HOST array of n_out int32_t, |z_i| <= 2^15; a negative value embeds as q - |z_i|.  s_j is coefficient j of
+ *   limb 0 of the secret key as imported, taken as a residue (nothing assumes it is small).  With the stream conventions of
+ *   fhe_keyswitch_keys_generate:
+ *       a_{r,i}  the uniform residue below q of element r n_out + i of stream seeds[0], drawn as fhe_rns_sample_uniform draws a one-word
+ *                modulus: word DRAW_UNIFORM + 4 t of the element, masked to bit_length(q), rejected until below q, top bit cleared after 64
+ *                rejections
+ *       e_r      the discrete Gaussian of element r of stream seeds[1] from the table of fhe_gaussian_cdt(sigma)
+ *       b_r      = (s_j (2^(k w) mod q) + [noise_scale e_r]_q - sum_i a_{r,i} z_i) mod q
+ *   The result is the handle fhe_lwe_ksk_create would return for that table, bit for bit: a function of (s, z, w, n_out, noise_scale, sigma,
+ *   seeds) only.  ONE launch after z is uploaded: one workgroup per row draws the row in registers, forms the inner product with z and writes
+ *   the row in the internal layout.  The key is complete when the call returns.  FHE_ERR_INVALID_ARG, with nothing launched or allocated and
+ *   *out untouched: a null argument; a key of another engine; n_out == 0 or n_out > 65536; decomp_bits outside [1, 32]; |z_i| > 2^15;
+ *   noise_scale == 0; a sigma fhe_gaussian_cdt rejects; ceil(12 sigma) >= q.  The noise comes from the engine's one cumulative table (shared with
+ *   fhe_rns_sample_gaussian, uploaded when sigma changes), which is kept for every limb: on an engine of several primes ceil(12 sigma) must
+ *   also be below the smallest of them.
+ *
+ * fhe_lwe_keyswitch.  d_in is [batch][n_in + 1] uint64_t below q (what fhe_rlwe_sample_extract writes on a one-limb engine), d_out is
+ *   [batch][n_out + 1].  With d_{j,k} = (in[b][j] >> (k w)) & (2^w - 1):
+ *       acc_i = sum_{j,k} d_{j,k} ksk[j K + k][i] mod q  for i <= n_out;     acc_{n_out} = (acc_{n_out} + in[b][n_in]) mod q
+ *   q_out == 0: out[b][i] = acc_i.  Otherwise 2 <= q_out <= 2^48 and out[b][i] = floor((acc_i q_out + floor(q / 2)) / q) mod q_out, the modulus
+ *   switch of the sample fused as the epilogue (needed when q > 2^48; q_out need not be prime).  The output phase under z equals the input
+ *   phase under s plus noise_scale sum d_{j,k} e_{j K + k}.  All arithmetic is exact: the same bits whatever the batch, the grid or the
+ *   accumulator form (a 64-bit accumulator where bit_length(q) + w + ceil(log2 R) <= 64, a 128-bit one elsewhere; chosen at key creation,
+ *   FHE_HIP_LWE_KSK_WIDE=1 read there forces the second).  Accepted engines: any h with h->n == n_in, limb-0 modulus q and the key's device;
+ *   the work runs on h's stream.  ONE launch, no workspace, nothing allocated: capturable into a hipGraph.  FHE_ERR_INVALID_ARG, with nothing
+ *   launched and nothing written: a null argument; a pointer not 8-byte aligned; an output overlapping the input; batch == 0; q_out outside
+ *   {0} u [2, 2^48]; an engine that does not match the key. */
+typedef struct fhe_lwe_ksk fhe_lwe_ksk_t;
+int fhe_lwe_ksk_num_digits(const fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t *digits);   /* K for h's limb-0 modulus */
+int fhe_lwe_ksk_create(fhe_rns_ntt_t *h, fhe_lwe_ksk_t **out, uint32_t decomp_bits, uint32_t n_out, const uint64_t *d_rows);
+int fhe_lwe_ksk_export(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t *d_rows);
+int fhe_lwe_ksk_destroy(fhe_lwe_ksk_t *ksk);
+int fhe_lwe_ksk_bytes(const fhe_lwe_ksk_t *ksk, uint64_t *bytes);                              /* device bytes of the key table */
+int fhe_lwe_ksk_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t decomp_bits, uint32_t n_out, const int32_t *z,
+                         uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_lwe_ksk_t **out);
+int fhe_lwe_keyswitch(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t q_out, uint64_t *d_out, const uint64_t *d_in, uint32_t batch);
+
 /* ---- batch encoder: slot values <-> plaintext polynomials on the device --------------------------------------------------------------
  * FHEContext::encode / decode and BatchEncoder (include/fhe.cuh:89-90, 150-157).  With psi = fhe_find_psi(n, t) and e(i) the exponent of slot i:
  *   FHE_SLOTS_NATURAL  e(i) = 2 i + 1                                          (what the mirror's host encode / decode evaluate)
