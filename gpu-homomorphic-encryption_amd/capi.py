@@ -143,6 +143,12 @@ def lib():
         "fhe_slots_encode": ([vp, vp, vp, vp, u32], ci),
         "fhe_slots_decode": ([vp, vp, vp, vp, u32], ci),
         "fhe_slots_decode_poly": ([vp, vp, vp, vp, u32], ci),
+        "fhe_ckks_encoder_create": ([vp, P(vp)], ci),
+        "fhe_ckks_encoder_destroy": ([vp], ci),
+        "fhe_ckks_slot_table": ([u32, P(u32), P(ctypes.c_uint8)], ci),
+        "fhe_ckks_encode": ([vp, vp, vp, vp, vp, ctypes.c_double, u32], ci),
+        "fhe_ckks_decode": ([vp, vp, vp, vp, u64, ctypes.c_double, u32], ci),
+        "fhe_ckks_decode_poly": ([vp, vp, vp, vp, ctypes.c_double, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -756,6 +762,47 @@ class BatchEncoder:
     def close(self):
         if self.h:
             lib().fhe_batch_encoder_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ckks_slot_table(n):
+    """(a(k), c(k)) of the CKKS slots k < n/2, built on the host (no device needed): numpy uint32 [n/2] and uint8 [n/2]."""
+    a, c = np.zeros(max(n // 2, 1), dtype=np.uint32), np.zeros(max(n // 2, 1), dtype=np.uint8)
+    _check(lib().fhe_ckks_slot_table(n, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    return a[:n // 2], c[:n // 2]
+
+
+class CkksEncoder:
+    """Complex slots <-> plaintext polynomials of the engine `eng` through the canonical embedding (FP64), on the device."""
+
+    def __init__(self, eng):
+        self.h = None
+        self.eng = eng
+        out = ctypes.c_void_p()
+        _check(lib().fhe_ckks_encoder_create(eng.h, ctypes.byref(out)))
+        self.h = out
+
+    def encode(self, d_out, d_slots, scale, batch=1, d_coeff_bits=None):
+        """d_out[b][l][j] = rne(scale m_b[j]) mod q_l ([batch][L][n] containers) for the [batch][n/2][2] doubles in d_slots; d_coeff_bits
+        ([batch] uint32, optional) receives the bit length of the largest |coefficient|."""
+        _check(lib().fhe_ckks_encode(self.eng.h, self.h, _ptr(d_out), None if d_coeff_bits is None else _ptr(d_coeff_bits), _ptr(d_slots), scale, batch))
+
+    def decode(self, d_slots, d_m, t, scale, batch=1):
+        """d_slots[b][k] = the slots of the [batch][n] uint64 words in d_m, centred modulo t (t = 0: two's complement), over scale."""
+        _check(lib().fhe_ckks_decode(self.eng.h, self.h, _ptr(d_slots), _ptr(d_m), t, scale, batch))
+
+    def decode_poly(self, d_slots, d_poly, scale, batch=1):
+        """The same from [batch][L][n] containers (limb 0 is read, centred modulo q_0)."""
+        _check(lib().fhe_ckks_decode_poly(self.eng.h, self.h, _ptr(d_slots), _ptr(d_poly), scale, batch))
+
+    def close(self):
+        if self.h:
+            lib().fhe_ckks_encoder_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

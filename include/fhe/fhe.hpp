@@ -7,6 +7,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <complex>
 #include <memory>
 #include <random>
 #include <vector>
@@ -104,6 +105,7 @@ struct Ciphertext {                                           // include/fhe.cuh
     uint64_t correction = 1;
     float noise_budget = 0.f;
     bool is_ntt_form = false;
+    double scale = 1.0;                    // CKKS (encrypt_ckks, rescale_to_next, decrypt_ckks): the plaintext is scale * m; the exact calls leave it alone
 };
 
 struct SchemeParams {                                         // include/fhe.cuh:24-38 (the parts that are used)
@@ -900,6 +902,121 @@ public:
         return (float)std::max(0, bit_length(Q) - 2 - (int)bits);
     }
 
+    // ---- CKKS: approximate arithmetic on the same ciphertexts (fhe_ckks_encode / fhe_ckks_decode; class CKKSEncoder below) -------------------
+    // multiply, relinearize, rotate_rows and the level engines are used as they are; they do not look at `scale`, so after a multiply the
+    // caller sets result.scale = a.scale * b.scale.  Keys carry noise t e (keygen, relinkey_gen): a CKKS context sets the plaintext modulus to 2
+    // BEFORE key generation, the smallest the engine calls accept.
+    void set_plain_modulus(uint64_t t) {
+        if (t < 2) throw std::runtime_error("FHEContext::set_plain_modulus: t must be at least 2");
+        params_.t = t; encoders_.clear();
+    }
+    // One fhe_ct_encrypt with t = 2 (its contract is t >= 2): c0 + c1 s = pt + 2 e, one bit more noise than e alone.  pt is a level-0 plaintext
+    // of CKKSEncoder::encode at `scale`, which the ciphertext records.
+    void encrypt_ckks(Ciphertext &ct, const Plaintext &pt, double scale, const PublicKey &pk) {
+        if (!pt.poly || pt.poly->num_limbs != num_levels()) throw std::runtime_error("FHEContext::encrypt_ckks: a level-0 plaintext is needed");
+        ensure_components(ct, 2, 0);
+        fhe_rns_ntt_t *h = params_.rns_ntt->handle();
+        if (!pk.imported || pk.imported_for != params_.rns_ntt) {
+            fhe_public_key_t *k = nullptr;
+            check(fhe_public_key_create(h, &k, pk.pk0->coeffs, pk.pk1->coeffs), "encrypt_ckks: public key import");
+            pk.imported.reset(k, [](fhe_public_key_t *p) { fhe_public_key_destroy(p); });
+            pk.imported_for = params_.rns_ntt;
+        }
+        const uint64_t seeds[3] = {rng_(), rng_(), rng_()};
+        check(fhe_ct_encrypt(h, pk.imported.get(), 2, (double)params_.security.sigma, seeds, ct.components[0]->coeffs, ct.components[1]->coeffs,
+                             pt.poly->coeffs, 1), "encrypt_ckks");
+        device_synchronize();
+        ct.level = 0; ct.correction = 1; ct.noise_budget = 0; ct.is_ntt_form = false; ct.scale = scale;
+    }
+    // The CKKS rescale: fhe_rns_rescale_drop_last (the rounded division by the last prime of ct's level) on every component onto the next
+    // level's engine; scale /= q_last.
+    void rescale_to_next(Ciphertext &ct) {
+        const uint32_t L = num_levels();
+        if (ct.level + 1 >= L) throw std::runtime_error("FHEContext::rescale_to_next: the ciphertext is at the last level");
+        const uint64_t q_last = params_.rns_moduli[L - 1 - ct.level].limbs[0];
+        for (Polynomial *&c : ct.components) {
+            Polynomial *out = new_polynomial(ct.level + 1);
+            try { engine(ct.level).rescale_drop_last(out->coeffs, c->coeffs); device_synchronize(); } catch (...) { delete out; throw; }
+            delete c; c = out;
+        }
+        ct.level += 1;
+        ct.scale /= (double)q_last;
+    }
+    // fhe_ct_decrypt on the engine of ct's level with t = 2^63 and scale 1 (no |v| < 2^62 wraps), then fhe_ckks_decode at ct.scale: the n/2
+    // slots.  `coeffs` (optional) receives the n centred integers v of c0 + c1 s (+ c2 s^2) that were decoded.
+    void decrypt_ckks(std::vector<std::complex<double>> &values, const Ciphertext &ct, const SecretKey &sk, std::vector<int64_t> *coeffs = nullptr) {
+        const uint32_t n = params_.n, Ll = num_levels() - ct.level;
+        const uint64_t t63 = 1ull << 63;
+        if (ct.components.size() != 2 && ct.components.size() != 3) throw std::runtime_error("FHEContext::decrypt_ckks: a ciphertext of 2 or 3 components is needed");
+        for (const Polynomial *c : ct.components)
+            if (c->num_limbs != Ll) throw std::runtime_error("FHEContext::decrypt_ckks: ciphertext components do not have the limbs of its level");
+        const fhe_secret_key_t *key = secret_key_at(sk, ct.level);
+        std::vector<const uint256_t *> comps;
+        for (const Polynomial *c : ct.components) comps.push_back(c->coeffs);
+        uint256_t *d_m = device_alloc(slot_words()), *d_z = nullptr;
+        values.assign(n / 2, std::complex<double>());
+        try {
+            d_z = device_alloc(slot_words());
+            engine(ct.level).decrypt(key, t63, 1, reinterpret_cast<uint64_t *>(d_m), nullptr, comps.data(), (uint32_t)comps.size());
+            check(fhe_ckks_decode(engine(ct.level).handle(), ckks_encoder_at(ct.level), reinterpret_cast<double *>(d_z), reinterpret_cast<const uint64_t *>(d_m), t63,
+                                  ct.scale, 1), "decrypt_ckks: decode");
+            device_synchronize();
+            check(fhe_hip_memcpy_d2h(values.data(), d_z, (size_t)n * sizeof(double)), "decrypt_ckks: download");
+            if (coeffs) {
+                std::vector<uint64_t> w(n);
+                check(fhe_hip_memcpy_d2h(w.data(), d_m, (size_t)n * sizeof(uint64_t)), "decrypt_ckks: download");
+                coeffs->resize(n);
+                for (uint32_t i = 0; i < n; i++) (*coeffs)[i] = w[i] > (t63 >> 1) ? -(int64_t)(t63 - w[i]) : (int64_t)w[i];
+            }
+        } catch (...) { device_free(d_m); device_free(d_z); throw; }
+        device_free(d_m); device_free(d_z);
+    }
+
+private:
+    friend class CKKSEncoder;
+    // the CKKS encoder of a level, created on first use and kept (n = 2^11 .. 2^14, primes below 2^64; the library refuses anything else)
+    const fhe_ckks_encoder_t *ckks_encoder_at(uint32_t level) {
+        if (ckks_encoders_.size() < num_levels()) ckks_encoders_.resize(num_levels());
+        std::shared_ptr<fhe_ckks_encoder_t> &e = ckks_encoders_[level];
+        if (!e) {
+            fhe_ckks_encoder_t *p = nullptr;
+            check(fhe_ckks_encoder_create(engine(level).handle(), &p), "FHEContext: CKKS encoder");
+            e.reset(p, [](fhe_ckks_encoder_t *q) { fhe_ckks_encoder_destroy(q); });
+        }
+        return e.get();
+    }
+    void ckks_encode(Plaintext &pt, const std::vector<std::complex<double>> &values, double scale, uint32_t level) {
+        const uint32_t n = params_.n;
+        if (values.size() > n / 2) throw std::runtime_error("CKKSEncoder::encode: more values than slots");
+        std::vector<std::complex<double>> v(n / 2);
+        std::copy(values.begin(), values.end(), v.begin());
+        if (pt.poly && pt.poly->num_limbs != num_levels() - level) { delete pt.poly; pt.poly = nullptr; }
+        if (!pt.poly) pt.poly = new_polynomial(level);
+        uint256_t *d_v = device_alloc(slot_words());
+        try {
+            check(fhe_hip_memcpy_h2d(d_v, v.data(), (size_t)n * sizeof(double)), "CKKSEncoder::encode: upload");
+            check(fhe_ckks_encode(engine(level).handle(), ckks_encoder_at(level), pt.poly->coeffs, nullptr, reinterpret_cast<const double *>(d_v), scale, 1),
+                  "CKKSEncoder::encode");
+            device_synchronize();
+        } catch (...) { device_free(d_v); throw; }
+        device_free(d_v);
+        pt.is_ntt_form = false;
+    }
+    void ckks_decode(std::vector<std::complex<double>> &values, const Plaintext &pt, double scale) {
+        const uint32_t n = params_.n;
+        if (!pt.poly) throw std::runtime_error("CKKSEncoder::decode: empty plaintext");
+        const uint32_t level = num_levels() - pt.poly->num_limbs;
+        uint256_t *d_v = device_alloc(slot_words());
+        values.assign(n / 2, std::complex<double>());
+        try {
+            check(fhe_ckks_decode_poly(engine(level).handle(), ckks_encoder_at(level), reinterpret_cast<double *>(d_v), pt.poly->coeffs, scale, 1), "CKKSEncoder::decode");
+            device_synchronize();
+            check(fhe_hip_memcpy_d2h(values.data(), d_v, (size_t)n * sizeof(double)), "CKKSEncoder::decode: download");
+        } catch (...) { device_free(d_v); throw; }
+        device_free(d_v);
+    }
+
+public:
     const SchemeParams &params() const { return params_; }
 
 private:
@@ -908,6 +1025,7 @@ private:
     bool device_sampling_ = false;
     std::vector<std::unique_ptr<RNS_NTTEngine>> level_engines_;   // index = level; entry 0 unused (params_.rns_ntt)
     std::vector<std::shared_ptr<fhe_batch_encoder_t>> encoders_;  // index = 2 level + slot order (encoder_at)
+    std::vector<std::shared_ptr<fhe_ckks_encoder_t>> ckks_encoders_;   // index = level (ckks_encoder_at)
     size_t slot_words() const { return ((size_t)params_.n * sizeof(uint64_t) + sizeof(uint256_t) - 1) / sizeof(uint256_t); }   // n 8-byte words in containers
 
     // c0 + c1*s (+ c2*s^2) of a ciphertext at its level as integers in [0, Q_l); Q = Q_l and half = floor(Q_l / 2) as 256-bit integers
@@ -1173,6 +1291,21 @@ public:
     explicit BatchEncoder(FHEContext &context) : ctx_(context), slot_count_(context.params().n) {}
     void encode(Plaintext &pt, const std::vector<uint64_t> &values) { ctx_.encode_slots(pt, values, FHE_SLOTS_ROWS); }
     void decode(std::vector<uint64_t> &values, const Plaintext &pt) { ctx_.decode_slots(values, pt, FHE_SLOTS_ROWS); }
+    uint32_t slot_count() const { return slot_count_; }
+
+private:
+    FHEContext &ctx_;
+    uint32_t slot_count_;
+};
+
+// CKKS encoder: n / 2 complex slots in the order of rotate_rows (a rotation by r is a cyclic left shift, the Galois element 2n - 1 conjugates),
+// encoded and decoded on the device (fhe_ckks_encode / fhe_ckks_decode_poly).  encode writes round(scale m) mod q_l at `level`; decode reads limb 0
+// centred modulo q_0, so it is the round trip of a plaintext whose coefficients stay below q_0 / 2.  The context is not const: it keeps the encoders.
+class CKKSEncoder {
+public:
+    explicit CKKSEncoder(FHEContext &context) : ctx_(context), slot_count_(context.params().n / 2) {}
+    void encode(Plaintext &pt, const std::vector<std::complex<double>> &values, double scale, uint32_t level = 0) { ctx_.ckks_encode(pt, values, scale, level); }
+    void decode(std::vector<std::complex<double>> &values, const Plaintext &pt, double scale) { ctx_.ckks_decode(values, pt, scale); }
     uint32_t slot_count() const { return slot_count_; }
 
 private:

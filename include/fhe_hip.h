@@ -655,6 +655,44 @@ int fhe_slots_encode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, void *d_o
 int fhe_slots_decode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, uint64_t *d_values, const uint64_t *d_m, uint32_t batch);
 int fhe_slots_decode_poly(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, uint64_t *d_values, const void *d_poly, uint32_t batch);
 
+/* ---- CKKS encoder: complex slots <-> RNS plaintexts on the device ------------------------------------------------------------------------
+ * Approximate arithmetic on the scheme-agnostic calls above (fhe_ct_encrypt, fhe_ct_multiply_relin, fhe_rns_rescale_drop_last = the CKKS
+ * rescale, fhe_ct_apply_galois, fhe_ct_decrypt): the canonical embedding in FP64.  With h = n/2, zeta = exp(i pi / n), omega = zeta^4:
+ *   slot k < h has the exponent e(k) = 3^k mod 2n (the generator of fhe_galois_element): fhe_galois_element(n, r) is a cyclic LEFT rotation of
+ *   the h complex slots by r, the element 2n - 1 conjugates them.  The plaintext of z in C^h is the REAL polynomial m of degree < n with
+ *   m(zeta^e(k)) = z_k (and so m(zeta^-e(k)) = conj(z_k)).  Exactly one of e(k), 2n - e(k) is 4 a + 1: that a is a(k), and c(k) = 1 says it was
+ *   the second (fhe_ckks_slot_table, host only).  With u_j = m_j + i m_(j+h) and w_a(k) = z_k, or conj(z_k) where c(k):
+ *       encode  u_j = zeta^-j (1/h) sum_a w_a omega^(-a j)           decode  w_a = sum_j (u_j zeta^j) omega^(a j)
+ * encode       d_slots is [batch][n/2][2] doubles (re, im).  c_j = round-to-nearest-even(scale m_j) as a signed 64-bit integer;
+ *              d_out[b][l][j] = c_j mod q_l in [0, q_l) (a negative c as q_l - (|c| mod q_l), 0 stays 0) as canonical containers, [batch][L][n]:
+ *              the d_m of fhe_ct_encrypt, and one [L][n] slice is a plaintext of fhe_linear_transform_create.  The reduction is division-free,
+ *              one table entry per limb prepared at creation.  d_coeff_bits ([batch], may be NULL) receives bit_length(max_j |c_j|), written
+ *              by the same launch (nothing to zero first, the call stays capturable).  The contract is exact for d_coeff_bits[b] <= 62; above
+ *              that the residues are unspecified and the reported value says so (as d_noise_bits of fhe_ct_decrypt does).
+ * decode       d_m is [batch][n] uint64_t in [0, t), what fhe_ct_decrypt(.., t, scale = 1, ..) writes: each word is centred (w > t/2 -> w - t),
+ *              converted to double and multiplied by 1/scale, then transformed; d_slots is [batch][n/2][2].  t == 0: the words already are
+ *              two's-complement int64.  Take t = 2^63, so that no |v| < 2^62 wraps.  "Does not wrap" is not "exact": the centred integer is
+ *              converted to double first, so a magnitude above 2^53 is rounded to 53 bits (relative error 2^-53) before the transform.
+ * decode_poly  the same from [batch][L][n] containers, reading limb 0 centred modulo q_0: valid for |c| < q_0 / 2 (the round trip without keys).
+ * The twiddles come from tables built on the host in long double and rounded once; the device evaluates no sine or cosine.  For a given build
+ * the result is a function of (inputs, n, scale, moduli) only, never of the batch size, the position in the batch or the grid.
+ *
+ * fhe_ckks_encoder_create: n = 2^11 .. 2^14 and every modulus below 2^64; another n or a full-width engine is FHE_ERR_UNSUPPORTED with *out
+ * untouched (a two-pass form for n >= 2^15 does not exist).  Every call is ONE launch, one workgroup per plaintext, no workspace, nothing
+ * allocated after create: capturable into a hipGraph.  Work is enqueued on h's stream.  FHE_ERR_INVALID_ARG, with nothing launched and nothing
+ * written: a null handle, encoder or buffer (d_coeff_bits excepted); an encoder of another engine; batch == 0; a container pointer not 16-byte
+ * aligned, a double or uint64_t pointer not 8-byte aligned, d_coeff_bits not 4-byte aligned; an output overlapping an input; a scale that is
+ * not finite and > 0.  fhe_ckks_encoder_destroy(NULL) is FHE_OK.  An encoder refers to its engine (every call reads h's stream and limb count) and
+ * owns only its tables: destroy it BEFORE the engine, and order all calls that use it on the engine's stream, as for the batch encoder.  fhe_ckks_slot_table needs no device: n a power of two in [2, 2^30]. */
+typedef struct fhe_ckks_encoder fhe_ckks_encoder_t;
+int fhe_ckks_encoder_create(fhe_rns_ntt_t *h, fhe_ckks_encoder_t **out);
+int fhe_ckks_encoder_destroy(fhe_ckks_encoder_t *enc);
+int fhe_ckks_slot_table(uint32_t n, uint32_t *a_of_slot, uint8_t *conj_of_slot);   /* host: a(k), c(k), k < n/2 */
+int fhe_ckks_encode(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, void *d_out, uint32_t *d_coeff_bits, const double *d_slots, double scale,
+                    uint32_t batch);
+int fhe_ckks_decode(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, double *d_slots, const uint64_t *d_m, uint64_t t, double scale, uint32_t batch);
+int fhe_ckks_decode_poly(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, double *d_slots, const void *d_poly, double scale, uint32_t batch);
+
 /* Scan a [batch][L][n] buffer for coefficients that are not canonical (>= q_limb, or non-zero
  * upper limbs on the narrow paths).  Synchronises.  FHE_OK or FHE_ERR_NONCANONICAL. */
 int fhe_rns_check_canonical(fhe_rns_ntt_t *h, const void *d_data, uint32_t batch);
