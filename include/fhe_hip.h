@@ -668,7 +668,10 @@ int fhe_slots_decode_poly(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc, uint
  *              the d_m of fhe_ct_encrypt, and one [L][n] slice is a plaintext of fhe_linear_transform_create.  The reduction is division-free,
  *              one table entry per limb prepared at creation.  d_coeff_bits ([batch], may be NULL) receives bit_length(max_j |c_j|), written
  *              by the same launch (nothing to zero first, the call stays capturable).  The contract is exact for d_coeff_bits[b] <= 62; above
- *              that the residues are unspecified and the reported value says so (as d_noise_bits of fhe_ct_decrypt does).
+ *              that the residues are unspecified and the reported value says so (as d_noise_bits of fhe_ct_decrypt does), and the containers
+ *              stay canonical, each in [0, q_l): 63 for 2^62 <= max |c| < 2^63; 64 where a |scale m_j| reaches 2^63 or is not finite (an
+ *              infinite or NaN slot makes every coefficient of its plaintext so), saturated and not an error.  Other plaintexts of the batch
+ *              are not affected.
  * decode       d_m is [batch][n] uint64_t in [0, t), what fhe_ct_decrypt(.., t, scale = 1, ..) writes: each word is centred (w > t/2 -> w - t),
  *              converted to double and multiplied by 1/scale, then transformed; d_slots is [batch][n/2][2].  t == 0: the words already are
  *              two's-complement int64.  Take t = 2^63, so that no |v| < 2^62 wraps.  "Does not wrap" is not "exact": the centred integer is

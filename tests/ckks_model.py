@@ -101,6 +101,35 @@ def evaluate_at(m, k):
     return complex(np.sum(m * np.cos(ang))), complex(np.sum(m * np.sin(ang)))
 
 
+def family_slots(n, x, y):
+    """The exact family: z_k = x + i y where c(k) = 0 and x - i y where c(k) = 1, as complex128.  Its plaintext is m = x + y X^(n/2): every
+    w_a is x + i y, so each butterfly of the encode transform adds two equal values or multiplies a zero, and the only twiddles that meet a
+    non-zero value are omega^0 = 1 and zeta^0 = 1.  Nothing is rounded in either direction, in any precision."""
+    c = slot_table(n)[1]
+    z = np.empty(n // 2, dtype=np.complex128)
+    z.real = x
+    z.imag = np.where(c == 1, -np.float64(y), np.float64(y))
+    return z
+
+
+def impulse_plaintext(n, k, zk):
+    """m of the slots z = zk delta_k in closed form: m_j = (2/n) Re(zk zeta^(-j e(k))) (n roots zeta^(+-e(k')), m real), in long double with the
+    angle index reduced mod 2n first, as evaluate_at does."""
+    e = pow(3, k, 2 * n)
+    idx = (e * np.arange(n, dtype=np.int64)) % (2 * n)
+    ang = _pi(LD) * idx.astype(LD) / LD(n)
+    return (LD(np.real(zk)) * np.cos(ang) + LD(np.imag(zk)) * np.sin(ang)) * LD(2) / LD(n)
+
+
+def impulse_slots(n, j, v):
+    """The slots of m = v X^j in closed form: z_k = v zeta^(j e(k)), in long double, the angle index reduced mod 2n first."""
+    idx = np.array([(j * e) % (2 * n) for e in exponents(n)], dtype=np.int64)
+    ang = _pi(LD) * idx.astype(LD) / LD(n)
+    out = np.empty(n // 2, dtype=CLD)
+    out.real = LD(v) * np.cos(ang); out.imag = LD(v) * np.sin(ang)
+    return out
+
+
 def spot_check(m, z, seed, tol):
     """The fast transform against direct evaluation at 8 random slots: |m(zeta^e(k)) - z_k| <= tol."""
     n = len(m)

@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from ckks_model import CKKS_NAMES, CKKS_SYMBOLS, CLD, LD, ROOT, decode, encode, slot_table, spot_check
+from ckks_model import CKKS_NAMES, CKKS_SYMBOLS, CLD, LD, ROOT, decode, encode, family_slots, impulse_plaintext, impulse_slots, slot_table, spot_check
 from test_hoisted import CSRC, HIPCC, RES_FLAGS, _resource_remarks
 
 
@@ -48,6 +48,50 @@ def test_integer_polynomials_are_recovered_exactly_by_the_model():
         m = encode(z, n, cdtype)
         assert float(np.max(np.abs(m.astype(LD) - m0.astype(LD)))) < 2.0 ** -10
         assert np.array_equal(np.rint(m.astype(np.float64)).astype(np.int64), m0)
+
+
+FAMILY_XY = ((0.5, -1.5), (-0.0, 0.0), (2.0 ** 53 - 1, 1.0), (2.0 ** 62 - 512, -2.0 ** 61), (2.0 ** 63, -2.0 ** 63), (1e300, -5e-324))
+
+
+@pytest.mark.parametrize("n", [2048, 4096, 8192, 16384])
+def test_the_exact_family_passes_through_the_model_without_one_rounding(n):
+    """Premise of test_ckks_edges.py: z_k = x + i y (x - i y where c(k)) encodes to m = x + y X^(n/2) and back with np.array_equal, in long
+    double and in float64 alike, so what the device is compared with has no error of its own."""
+    for x, y in FAMILY_XY:
+        z = family_slots(n, x, y)
+        want = np.zeros(n)
+        want[0], want[n // 2] = x, y
+        for cdtype in (CLD, np.complex128):
+            m = encode(z, n, cdtype)
+            assert np.array_equal(m, want.astype(m.dtype)), (n, x, y, cdtype)
+            assert np.array_equal(decode(want, cdtype), z.astype(cdtype)), (n, x, y, cdtype)
+
+
+@pytest.mark.parametrize("n", [2048, 16384])
+def test_impulse_closed_forms_agree_with_the_model(n):
+    """m_j = (2/n) Re(z_k zeta^(-j e(k))) for one unit slot, z_k = v zeta^(j e(k)) for one coefficient: the model's transform has
+    log2(n/2) + 1 <= 14 roundings per value on top of its twiddles', so 16 eps of long double times the magnitude bounds the difference."""
+    eps = float(np.finfo(LD).eps)
+    for k in (0, 1, n // 4, n // 2 - 1):
+        for zk in (1.0, 1j):
+            z = np.zeros(n // 2, dtype=np.complex128)
+            z[k] = zk
+            assert float(np.max(np.abs(encode(z, n) - impulse_plaintext(n, k, zk)))) <= 16 * eps * 2 / n, (n, k, zk)
+    for j in (1, 15, 16, n // 2 - 1, n // 2 + 1, n - 1):
+        m = np.zeros(n, dtype=LD)
+        m[j] = LD(2.0 ** 21)
+        assert float(np.max(np.abs(decode(m) - impulse_slots(n, j, m[j])))) <= 16 * eps * 2.0 ** 21, (n, j)
+
+
+@pytest.mark.parametrize("n", [2048, 16384])
+def test_generic_slots_at_scale_2_to_61_stay_inside_the_exact_contract(n):
+    """Premise of the 2^61 case of test_ckks_edges.py: max |round(scale m)| < 2^62 (about 2^60: m_0 is the mean of the unit square's real parts)."""
+    from test_ckks_encoder import generic_case
+    z, m, E = generic_case(n)
+    for b in range(len(m)):
+        top = max(abs(int(x)) for x in np.rint(LD(2.0 ** 61) * m[b]))
+        print(f"n={n} b={b}: max |round(2^61 m)| = 2^{np.log2(float(top)):.3f}")
+        assert top < 1 << 62, (n, b)
 
 
 def test_slot_table_of_the_library_matches_python(pkg):
