@@ -135,6 +135,10 @@ def lib():
         "fhe_lwe_ksk_bytes": ([vp, P(u64)], ci),
         "fhe_lwe_ksk_generate": ([vp, vp, u32, u32, P(ctypes.c_int32), u64, ctypes.c_double, P(u64), P(vp)], ci),
         "fhe_lwe_keyswitch": ([vp, vp, u64, vp, vp, u32], ci),
+        "fhe_lwe_pack_galois_elements": ([u32, P(u32)], ci),
+        "fhe_lwe_to_rlwe": ([vp, vp, vp, vp, u32], ci),
+        "fhe_lwe_pack": ([vp, P(vp), vp, vp, vp, u32, ci, ci, u32], ci),
+        "fhe_lwe_pack_reserve": ([vp, P(vp), u32, ci, u32], ci),
         "fhe_batch_encoder_create": ([vp, P(vp), u64, ci], ci),
         "fhe_batch_encoder_destroy": ([vp], ci),
         "fhe_batch_encoder_reserve": ([vp, vp, u32], ci),
@@ -199,6 +203,13 @@ def find_psi(n, q):
 def galois_element(n, steps):
     """3^(steps mod n/2) mod 2n: the Galois element of a row rotation by `steps` slots (host only)."""
     e = ctypes.c_uint32(0); _check(lib().fhe_galois_element(n, steps, ctypes.byref(e))); return e.value
+
+
+def lwe_pack_galois_elements(n):
+    """[2^j + 1 for j = 1 .. log2 n]: the Galois elements whose keys fhe_lwe_pack takes, in the order of its key array (host only)."""
+    if not 0 < int(n) < 1 << 32:
+        raise FheError(-1, "lwe_pack_galois_elements: n must be a power of two in [8, 2^30]")
+    out = (ctypes.c_uint32 * 32)(); _check(lib().fhe_lwe_pack_galois_elements(n, out)); return [int(out[j]) for j in range(int(n).bit_length() - 1)]
 
 
 def device_count():
@@ -584,6 +595,26 @@ class RnsNttEngine:
     def sample_extract(self, d_out, d_c0, d_c1, idx, batch=1):
         """Coefficient idx of (c0, c1) as LWE samples: d_out = device uint64 [batch][L][n + 1]."""
         _check(lib().fhe_rlwe_sample_extract(self.h, _ptr(d_out), _ptr(d_c0), _ptr(d_c1), idx, batch))
+
+    lwe_pack_galois_elements = staticmethod(lwe_pack_galois_elements)
+
+    def lwe_to_rlwe(self, d_c0, d_c1, d_lwe, batch=1):
+        """The RLWE embedding of LWE samples under the ring key: d_lwe = device uint64 [batch][L][n + 1] -> (d_c0, d_c1) [batch][L][n] containers,
+        the inverse of sample_extract at idx = 0."""
+        _check(lib().fhe_lwe_to_rlwe(self.h, _ptr(d_c0), _ptr(d_c1), _ptr(d_lwe), batch))
+
+    @staticmethod
+    def _pack_keys(keys):
+        return (ctypes.c_void_p * max(len(keys), 1))(*[None if k is None else k.h for k in keys])
+
+    def lwe_pack(self, keys, d_out0, d_out1, d_lwe, count, trace=True, normalize=True, batch=1):
+        """d_lwe = device uint64 [batch][count][L][n + 1] -> one RLWE ciphertext per batch element whose coefficient i (n / count) carries the
+        phase of sample i.  keys[j - 1]: the Galois keys of 2^j + 1 (lwe_pack_galois_elements), None where the call does not use them."""
+        _check(lib().fhe_lwe_pack(self.h, self._pack_keys(keys), _ptr(d_out0), _ptr(d_out1), _ptr(d_lwe), count, int(bool(trace)), int(bool(normalize)), batch))
+
+    def lwe_pack_reserve(self, keys, count, trace=True, batch=1):
+        """Pre-size what lwe_pack needs for this shape (its own scratch and the key switch's): afterwards a call allocates nothing."""
+        _check(lib().fhe_lwe_pack_reserve(self.h, self._pack_keys(keys), count, int(bool(trace)), batch))
 
     def lwe_ksk_num_digits(self, decomp_bits):
         """K = ceil(bit_length(q_0) / decomp_bits): the LWE key-switching key of this engine has n K rows."""

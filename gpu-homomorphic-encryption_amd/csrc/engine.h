@@ -21,6 +21,8 @@
 //                   rows of the loop come from keygen.hip (fhe_rgsw_keys_generate)
 //   lwe_keyswitch.hip  after the loop: the LWE key-switching key (its one key object, import / export / generation) and the key switch of an
 //                   extracted sample back to the small LWE key, with the optional modulus switch (lwe_keyswitch.hip.h)
+//   lwe_pack.hip    the way back: LWE samples under the ring key into one RLWE ciphertext, merge levels and trace around fhe_ct_apply_galois
+//                   (lwe_pack.hip.h)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 #pragma once
@@ -118,6 +120,9 @@ struct fhe_rns_ntt {
     // fhe_ct_decrypt, a seventh allocation.  Fused path: the residues of c0 + c1 s + c2 s^2 as compact polynomials between the two launches;
     // composed path: c1 s (and c2 s^2) as containers
     void *d_dec = nullptr; size_t dec_bytes = 0;
+    // fhe_lwe_pack, an eighth allocation.  Fused path: three regions that rotate as (P, G, free) over the merge levels; composed path: the
+    // embedded ciphertexts and the operands of one level as containers
+    void *d_pack = nullptr; size_t pack_bytes = 0;
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)

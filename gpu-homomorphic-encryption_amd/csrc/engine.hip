@@ -16,6 +16,7 @@ void destroy_impl(fhe_rns_ntt *h) {
     if (h->d_lin) (void)hipFree(h->d_lin);
     if (h->d_enc) (void)hipFree(h->d_enc);
     if (h->d_dec) (void)hipFree(h->d_dec);
+    if (h->d_pack) (void)hipFree(h->d_pack);
     if (h->d_cdt) (void)hipFree(h->d_cdt);
     if (h->d_flag) (void)hipFree(h->d_flag);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
@@ -358,7 +359,7 @@ extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
 }
 extern "C" int fhe_rns_ntt_workspace_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {
     if (!h || !bytes) return fail(FHE_ERR_INVALID_ARG, "workspace_bytes: null argument");
-    *bytes = (uint64_t)h->ws_bytes + h->ws2_bytes + h->ws3_bytes + h->lin_bytes + h->enc_bytes + h->dec_bytes;
+    *bytes = (uint64_t)h->ws_bytes + h->ws2_bytes + h->ws3_bytes + h->lin_bytes + h->enc_bytes + h->dec_bytes + h->pack_bytes;
     return FHE_OK;
 }
 extern "C" int fhe_rns_ntt_width_class(const fhe_rns_ntt_t *h) { return h ? h->width : fail(FHE_ERR_INVALID_ARG, "null handle"); }

@@ -1,0 +1,221 @@
+// lwe_pack.hip -- the way back from bootstrapping: LWE samples under the ring key (what fhe_rlwe_sample_extract writes) into one RLWE ciphertext
+// (fhe_lwe_to_rlwe, fhe_lwe_pack*; contract and algorithm: include/fhe_hip.h).  The ring packing of Chen, Dai, Kim and Song: log2(count) merge
+// levels and, with the trace, log2(n / count) more automorphisms, every one a batched fhe_ct_apply_galois.
+// Fused path (kernels: lwe_pack.hip.h): per level one streaming launch and one key switch.  The first level reads the samples themselves, a later
+// one forms the "P + G" of the level before in registers; three regions of the packing workspace d_pack rotate as (P, G, free).
+// Composed path (FHE_HIP_NO_FUSED_PACK=1, read per call): the literal composition of entry points through container scratch in d_pack -- the
+// embedding, fhe_rns_monomial_mul_sub, fhe_rns_poly_add / sub, fhe_ct_apply_galois -- one batch element at a time where the pairs are strided.
+#include "engine.h"
+
+#include <type_traits>
+
+#include "lwe_pack.hip.h"
+
+static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+static bool pack_composed_env() { const char *e = std::getenv("FHE_HIP_NO_FUSED_PACK"); return e && e[0] == '1'; }
+
+extern "C" int fhe_lwe_pack_galois_elements(uint32_t n, uint32_t *elts) {
+    if (!elts) return fail(FHE_ERR_INVALID_ARG, "lwe_pack_galois_elements: null argument");
+    if (n < 8 || n > (1u << 30) || (n & (n - 1))) return fail(FHE_ERR_INVALID_ARG, "lwe_pack_galois_elements: n must be a power of two in [8, 2^30]");
+    for (uint32_t j = 1; (1u << j) <= n; j++) elts[j - 1] = (1u << j) + 1;
+    return FHE_OK;
+}
+
+// the embedding (PAIR = false) or the first merge level (PAIR = true) of `entries` output ciphertexts
+template <bool PAIR>
+static int launch_embed(fhe_rns_ntt *h, void *o0, void *o1, void *d0, void *d1, const uint64_t *d_lwe, uint32_t half, uint32_t halvings, size_t entries) {
+    using V = fhe_dev::v2u64;
+    const size_t halves = entries * h->L * h->n * 2;
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::lwe_embed_merge_kernel<LimbT, PAIR>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1, d_lwe, limbs,
+                           half, halvings, h->L, h->log_n, halves);
+        return post_launch(h->stream, PAIR ? "lwe_embed_merge_kernel (first level)" : "lwe_embed_merge_kernel (embedding)");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+static int launch_merge(fhe_rns_ntt *h, char *np0, char *np1, char *nd0, char *nd1, const char *p0, const char *p1, const char *g0, const char *g1, uint32_t half,
+                        uint32_t m, size_t entries) {
+    using V = fhe_dev::v2u64;
+    const size_t halves = entries * h->L * h->n * 2;
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::lwe_merge_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)np0, (V *)np1, (V *)nd0, (V *)nd1, (const V *)p0,
+                           (const V *)p1, (const V *)g0, (const V *)g1, limbs, half, m, h->L, h->log_n, halves);
+        return post_launch(h->stream, "lwe_merge_kernel");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+static int launch_sum(fhe_rns_ntt *h, void *o0, void *o1, const void *a0, const void *a1, const void *b0, const void *b1, size_t entries) {
+    using V = fhe_dev::v2u64;
+    const size_t halves = entries * h->L * h->n * 2;
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::lwe_pack_sum_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (const V *)a0, (const V *)a1,
+                           (const V *)b0, (const V *)b1, limbs, h->L, h->log_n, halves);
+        return post_launch(h->stream, "lwe_pack_sum_kernel");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+
+// what every packing entry point checks of the engine and the sizes
+static int check_pack_engine(const fhe_rns_ntt *h, uint32_t batch, const char *what) {
+    int rc = check_call(h, batch, what); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": every modulus must be below 2^64");
+    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": n must be at least 8");
+    return FHE_OK;
+}
+
+extern "C" int fhe_lwe_to_rlwe(fhe_rns_ntt_t *h, void *d_c0, void *d_c1, const uint64_t *d_lwe, uint32_t batch) {
+    int rc = check_pack_engine(h, batch, "lwe_to_rlwe"); if (rc) return rc;
+    if (!d_c0 || !d_c1 || !d_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: null argument");
+    if ((rc = check_aligned({d_c0, d_c1}, "lwe_to_rlwe"))) return rc;
+    if ((uintptr_t)d_lwe & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: d_lwe must be 8-byte aligned");
+    const size_t polys = (size_t)batch * h->L, out = polys * h->n * 32, in = polys * ((size_t)h->n + 1) * 8;
+    if (overlaps(d_c0, out, d_c1, out)) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: the outputs must not overlap");
+    if (overlaps(d_c0, out, d_lwe, in) || overlaps(d_c1, out, d_lwe, in)) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: an output overlaps the input");
+    return launch_embed<false>(h, d_c0, d_c1, nullptr, nullptr, d_lwe, 0, 0, batch);
+}
+
+// ---- the packing call ----------------------------------------------------------------------------------------------------------------
+namespace {
+struct PackShape {
+    uint32_t k = 0;            // log2 count: merge levels
+    uint32_t first_trace = 0, last_trace = 0;   // trace steps j = first .. last (none when first > last)
+    uint32_t K = 0; bool packed = false;        // of the key sets the call uses (0: it uses none)
+    uint32_t galois_batch = 0; // the largest batch of an fhe_ct_apply_galois of the call
+};
+}
+// count, batch and the key sets of a call: everything fhe_lwe_pack and fhe_lwe_pack_reserve check alike
+static int check_pack_shape(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch, const char *what, PackShape *S) {
+    const std::string w(what);
+    if (!count || (count & (count - 1)) || count > h->n) return fail(FHE_ERR_INVALID_ARG, w + ": count must be a power of two in [1, n]");
+    if ((uint64_t)batch * count > 0xffffffffull) return fail(FHE_ERR_INVALID_ARG, w + ": batch * count overflows 32 bits");
+    if ((uint64_t)batch * count * h->L > 0x7fffffffull) return fail(FHE_ERR_INVALID_ARG, w + ": batch * count * num_primes too large");
+    while ((1u << S->k) < count) S->k++;
+    S->first_trace = S->k + 1; S->last_trace = trace ? h->log_n : S->k;
+    if (S->last_trace >= 1 && !gks) return fail(FHE_ERR_INVALID_ARG, w + ": null key-set array");
+    for (uint32_t j = 1; j <= S->last_trace; j++) {
+        const fhe_relin_keys_t *gk = gks[j - 1];
+        if (!gk) return fail(FHE_ERR_INVALID_ARG, w + ": the key set of 2^" + std::to_string(j) + " + 1 is needed and null");
+        if (gk->owner != h) return fail(FHE_ERR_INVALID_ARG, w + ": keys were imported for a different engine");
+        if (S->K && gk->decomp_bits != gks[0]->decomp_bits) return fail(FHE_ERR_INVALID_ARG, w + ": the key sets differ in decomp_bits");
+        S->K = gk->K; S->packed = gk->d_pkb != nullptr;
+    }
+    S->galois_batch = S->k ? batch * (count / 2) : (S->last_trace ? batch : 0);
+    return FHE_OK;
+}
+// bytes of d_pack for a call.  Fused: three regions of batch count S (S = L n 32; a region holds both components of batch count / 2
+// ciphertexts), or the trace's pair alone for count = 1.  Composed: R (batch count ciphertexts), X, P, D (half as many each) and the shift words.
+static size_t pack_bytes(const fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch, bool composed) {
+    const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count;
+    if (!S.k) return S.last_trace ? 2 * batch * poly : 0;
+    return composed ? 5 * bc * poly + 2 * bc : 3 * bc * poly;
+}
+static int ensure_pack(fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch, bool composed) {
+    int rc = grow_ws(h, &h->d_pack, &h->pack_bytes, pack_bytes(h, S, count, batch, composed)); if (rc) return rc;
+    return S.galois_batch ? ensure_need(h, need_apply_galois(h, S.galois_batch, S.K, S.packed)) : FHE_OK;
+}
+
+extern "C" int fhe_lwe_pack_reserve(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch) {
+    int rc = check_pack_engine(h, batch, "lwe_pack_reserve"); if (rc) return rc;
+    PackShape S;
+    if ((rc = check_pack_shape(h, gks, count, trace, batch, "lwe_pack_reserve", &S))) return rc;
+    return ensure_pack(h, S, count, batch, pack_composed_env());
+}
+
+// ct <- ct + sigma_{2^j + 1}(ct) on the outputs, j = first_trace .. last_trace; (t0, t1): scratch for `batch` ciphertexts
+static int pack_trace(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, char *t0, char *t1, uint32_t batch, bool composed) {
+    int rc;
+    for (uint32_t j = S.first_trace; j <= S.last_trace; j++) {
+        if ((rc = fhe_ct_apply_galois(h, gks[j - 1], (1u << j) + 1, t0, t1, d_out0, d_out1, batch))) return rc;
+        if (!composed) { if ((rc = launch_sum(h, d_out0, d_out1, d_out0, d_out1, t0, t1, batch))) return rc; continue; }
+        if ((rc = fhe_rns_poly_add(h, d_out0, d_out0, t0, batch)) || (rc = fhe_rns_poly_add(h, d_out1, d_out1, t1, batch))) return rc;
+    }
+    return FHE_OK;
+}
+
+static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count,
+                      uint32_t halvings, uint32_t batch) {
+    const size_t poly = (size_t)h->L * h->n * 32, region = (size_t)batch * count * poly;
+    char *base = (char *)h->d_pack;
+    int rc;
+    if (!S.k) {
+        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, d_lwe, 0, halvings, batch))) return rc;
+        return pack_trace(h, gks, S, d_out0, d_out1, base, base + batch * poly, batch, false);
+    }
+    char *reg_p = base, *reg_g = base + 2 * region, *reg_free = base + region;
+    size_t e = (size_t)batch * (count / 2);                                   // ciphertexts the level writes
+    // level 1: P -> reg_p, D -> reg_free, G = key-switched sigma_3(D) -> reg_g
+    if ((rc = launch_embed<true>(h, reg_p, reg_p + e * poly, reg_free, reg_free + e * poly, d_lwe, count / 2, halvings, e))) return rc;
+    if ((rc = fhe_ct_apply_galois(h, gks[0], 3, reg_g, reg_g + e * poly, reg_free, reg_free + e * poly, (uint32_t)e))) return rc;
+    const char *p0 = reg_p, *p1 = reg_p + e * poly, *g0 = reg_g, *g1 = reg_g + e * poly;
+    for (uint32_t l = 2; l <= S.k; l++) {
+        const uint32_t half = count >> l;
+        e = (size_t)batch * half;
+        char *np0 = reg_free, *np1 = np0 + e * poly, *nd0 = np1 + e * poly, *nd1 = nd0 + e * poly;   // 4 e <= batch count: inside the region
+        if ((rc = launch_merge(h, np0, np1, nd0, nd1, p0, p1, g0, g1, half, h->n >> l, e))) return rc;
+        char *ng0 = reg_p, *ng1 = reg_p + e * poly;                           // the P of the level before is consumed: its region takes the new G
+        if ((rc = fhe_ct_apply_galois(h, gks[l - 1], (1u << l) + 1, ng0, ng1, nd0, nd1, (uint32_t)e))) return rc;
+        char *old_g = reg_g;
+        reg_g = reg_p; reg_p = reg_free; reg_free = old_g;
+        p0 = np0; p1 = np1; g0 = ng0; g1 = ng1;
+    }
+    if ((rc = launch_sum(h, d_out0, d_out1, p0, p1, g0, g1, batch))) return rc;      // e == batch here
+    return pack_trace(h, gks, S, d_out0, d_out1, reg_free, reg_free + batch * poly, batch, false);
+}
+
+static int pack_composed(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count,
+                         uint32_t halvings, uint32_t batch) {
+    const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count, hb = bc / 2 * poly;
+    char *base = (char *)h->d_pack;
+    int rc;
+    if (!S.k) {
+        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, d_lwe, 0, halvings, batch))) return rc;
+        return pack_trace(h, gks, S, d_out0, d_out1, base, base + batch * poly, batch, true);
+    }
+    char *R[2] = {base, base + bc * poly}, *X[2] = {base + 2 * bc * poly, base + 2 * bc * poly + hb}, *P[2] = {X[1] + hb, X[1] + 2 * hb}, *D[2] = {P[1] + hb, P[1] + 2 * hb};
+    uint32_t *shifts = (uint32_t *)(D[1] + hb);
+    if ((rc = launch_embed<false>(h, R[0], R[1], nullptr, nullptr, d_lwe, 0, halvings, bc))) return rc;       // fhe_lwe_to_rlwe of F^-1 times the samples
+    for (uint32_t l = 1, cur = count; l <= S.k; l++, cur /= 2) {
+        const uint32_t half = cur / 2, e = batch * half;
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)shifts, (int)(h->n >> l), half, h->stream));
+        for (uint32_t b = 0; b < batch; b++)
+            for (int c = 0; c < 2; c++) {
+                const char *E = R[c] + (size_t)b * cur * poly, *O = E + (size_t)half * poly;
+                char *x = X[c] + (size_t)b * half * poly;
+                if ((rc = fhe_rns_monomial_mul_sub(h, x, O, shifts, half))) return rc;                        // (X^m - 1) O
+                if ((rc = fhe_rns_poly_add(h, x, x, O, half))) return rc;                                     // X^m O
+                if ((rc = fhe_rns_poly_add(h, P[c] + (size_t)b * half * poly, E, x, half))) return rc;
+                if ((rc = fhe_rns_poly_sub(h, D[c] + (size_t)b * half * poly, E, x, half))) return rc;
+            }
+        if ((rc = fhe_ct_apply_galois(h, gks[l - 1], (1u << l) + 1, X[0], X[1], D[0], D[1], e))) return rc;   // G over X^m O, which is consumed
+        void *dst[2] = {l == S.k ? d_out0 : (void *)R[0], l == S.k ? d_out1 : (void *)R[1]};
+        for (int c = 0; c < 2; c++) if ((rc = fhe_rns_poly_add(h, dst[c], P[c], X[c], e))) return rc;
+    }
+    return pack_trace(h, gks, S, d_out0, d_out1, X[0], X[1], batch, true);
+}
+
+extern "C" int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count, int trace,
+                            int normalize, uint32_t batch) {
+    int rc = check_pack_engine(h, batch, "lwe_pack"); if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: null argument");
+    if ((rc = check_aligned({d_out0, d_out1}, "lwe_pack"))) return rc;
+    if ((uintptr_t)d_lwe & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: d_lwe must be 8-byte aligned");
+    PackShape S;
+    if ((rc = check_pack_shape(h, gks, count, trace, batch, "lwe_pack", &S))) return rc;
+    const size_t out = (size_t)batch * h->L * h->n * 32, in = (size_t)batch * count * h->L * ((size_t)h->n + 1) * 8;
+    if (overlaps(d_out0, out, d_out1, out)) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: the outputs must not overlap");
+    if (overlaps(d_out0, out, d_lwe, in) || overlaps(d_out1, out, d_lwe, in)) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: an output overlaps the input");
+    const bool composed = pack_composed_env();
+    if ((rc = ensure_pack(h, S, count, batch, composed))) return rc;              // (no-op after fhe_lwe_pack_reserve)
+    const uint32_t halvings = normalize ? (trace ? h->log_n : S.k) : 0;           // F = n with the trace, count without
+    return composed ? pack_composed(h, gks, S, d_out0, d_out1, d_lwe, count, halvings, batch)
+                    : pack_fused(h, gks, S, d_out0, d_out1, d_lwe, count, halvings, batch);
+}

@@ -91,6 +91,18 @@ struct BootstrapKey {
     ~BootstrapKey() { clear(); }
 };
 
+// The Galois keys of 2^j + 1, j = 1 .. log2 n, that pack LWE samples back into one ciphertext (FHEContext::packing_key_gen / pack_lwes)
+struct PackingKeys {
+    std::vector<fhe_relin_keys_t *> sets;  // sets[j - 1]: the keys of 2^j + 1
+    uint32_t decomp_bits = 16;
+    const void *made_for = nullptr;        // the engine whose handles these are (FHEContext::pack_lwes refuses another context's keys)
+    PackingKeys() = default;
+    PackingKeys(const PackingKeys &) = delete;
+    PackingKeys &operator=(const PackingKeys &) = delete;
+    void clear() { for (fhe_relin_keys_t *k : sets) fhe_relin_keys_destroy(k); sets.clear(); }
+    ~PackingKeys() { clear(); }
+};
+
 struct Plaintext {                                            // include/fhe.cuh:72-75
     Polynomial *poly = nullptr;
     bool is_ntt_form = false;
@@ -498,6 +510,40 @@ public:
             check(fhe_hip_memcpy_d2h(out_lwe.data(), d_out, out_lwe.size() * 8), "memcpy d2h");
         } catch (...) { device_free(d); throw; }
         device_free(d);
+    }
+
+    // The way back from LWE samples to a ciphertext (fhe_lwe_pack; the last step of the declared FHEContext::bootstrap(Ciphertext&), which this
+    // does not build).  packing_key_gen: the log2(n) Galois key sets of 2^j + 1 in ONE engine call, noise scale t like every key of the context.
+    void packing_key_gen(PackingKeys &pk, const SecretKey &sk, uint32_t decomp_bits = 16) {
+        uint32_t log_n = 0; while ((1u << log_n) < params_.n) log_n++;
+        std::vector<uint32_t> elts(log_n);
+        check(fhe_lwe_pack_galois_elements(params_.n, elts.data()), "FHEContext::packing_key_gen");
+        std::vector<fhe_relin_keys_t *> sets(log_n, nullptr);
+        generate_key_sets(sk, decomp_bits, elts.data(), log_n, sets.data());
+        pk.clear();
+        pk.sets = std::move(sets); pk.decomp_bits = decomp_bits; pk.made_for = params_.rns_ntt;
+    }
+    // lwe: [count][L][n + 1] residues, samples under the ring key at level 0 (what blind_rotate_lwe or fhe_rlwe_sample_extract leaves).  out is a
+    // level-0 ciphertext whose coefficient i (n / count) carries the phase of sample i: exactly with normalize (correction 1), times F = n (trace) or
+    // count (no trace) without, which out.correction records as F mod t, so that decrypt_fused divides it out.  With the trace every other
+    // coefficient is 0.
+    void pack_lwes(Ciphertext &out, const PackingKeys &pk, const std::vector<uint64_t> &lwe, uint32_t count, bool trace = true, bool normalize = true) {
+        const uint32_t n = params_.n, L = num_levels();
+        if (pk.made_for != params_.rns_ntt) throw std::runtime_error("FHEContext::pack_lwes: the packing keys were generated by another context");
+        if (!count || lwe.size() != (size_t)count * L * (n + 1)) throw std::runtime_error("FHEContext::pack_lwes: lwe must hold count x L x (n + 1) values");
+        const uint64_t F = normalize ? 1 : (trace ? n : count);
+        if (F % params_.t == 0) throw std::runtime_error("FHEContext::pack_lwes: the factor F is 0 modulo t; pack with normalize");
+        ensure_components(out, 2, 0);
+        const size_t lwe_c = (lwe.size() * 8 + sizeof(uint256_t) - 1) / sizeof(uint256_t);
+        uint256_t *d = device_alloc(lwe_c);
+        try {
+            check(fhe_hip_memcpy_h2d(d, lwe.data(), lwe.size() * 8), "memcpy h2d");
+            check(fhe_lwe_pack(params_.rns_ntt->handle(), pk.sets.data(), out.components[0]->coeffs, out.components[1]->coeffs, (const uint64_t *)d, count,
+                               trace ? 1 : 0, normalize ? 1 : 0, 1), "FHEContext::pack_lwes");
+            device_synchronize();
+        } catch (...) { device_free(d); throw; }
+        device_free(d);
+        out.level = 0; out.correction = F % params_.t; out.noise_budget = 0; out.is_ntt_form = false;
     }
 
     // FHEContext::bootstrap (include/fhe.cuh:119, declared only) as one chainable call: lwe is [batch][n_lwe + 1] values below q_lwe under the

@@ -617,6 +617,55 @@ int fhe_lwe_ksk_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t 
                          uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_lwe_ksk_t **out);
 int fhe_lwe_keyswitch(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t q_out, uint64_t *d_out, const uint64_t *d_in, uint32_t batch);
 
+/* ---- pack LWE samples into one RLWE ciphertext: the way back from bootstrapping -------------------------------------------------------
+ * The last step of FHEContext::bootstrap(Ciphertext&) (include/fhe.cuh:119, declared only; README.md:146-159): the refreshed coefficients are LWE
+ * samples under the RING key, and the ring operations want one RLWE ciphertext.  The ring packing of Chen, Dai, Kim and Song ("Efficient
+ * homomorphic conversion between (ring) LWE ciphertexts": PackLWEs and the field trace): log2(n) automorphism key switches and streaming merges.
+ * Phase c0 + c1 s.  For moduli below 2^64, the rule of the bootstrapping block: an engine with a modulus of 2^64 or more gets
+ * FHE_ERR_UNSUPPORTED from every call that takes one, nothing launched.  Any n >= 8 the engine accepts.
+ *
+ * Embedding.  An LWE sample under the ring key is [L][n + 1] uint64_t, limb l holding (a_0 .. a_{n-1}, b) below q_l: what fhe_rlwe_sample_extract
+ *   writes.  Its RLWE embedding is the inverse of extraction at idx = 0: c0 = (b, 0, .., 0), c1[0] = a_0, c1[i] = (q_l - a_{n-i}) mod q_l for i >= 1.
+ *   Coefficient 0 of c0 + c1 s is b + sum a_j s_j; the other coefficients are unspecified.
+ * Merge.  For a list of c = 2^l RLWE ciphertexts, c >= 2, m = n / c:  E = Pack(entries 0, 2, 4, ..), O = Pack(entries 1, 3, 5, ..),
+ *   P = E + X^m O, D = E - X^m O (negacyclic, per component, per limb, canonical), Pack = P + fhe_ct_apply_galois(D, g = c + 1).  Pack of one
+ *   entry is the entry.  Unrolled by level l = 1 .. log2(count): the count / 2^(l-1) results R of the level before merge in pairs,
+ *   R_l[r] = merge(R_(l-1)[r], R_(l-1)[r + count / 2^l]) with m = n / 2^l and g = 2^l + 1, all batch count / 2^l pairs in one step.
+ * Trace.  With k = log2(count): for j = k+1, k+2, .., log2(n) in this order, ct <- ct + fhe_ct_apply_galois(ct, g = 2^j + 1).
+ * Normalisation.  F = n with the trace, F = count without.  With normalize != 0 every embedded value is multiplied by F^-1 mod q_l before the
+ *   first merge: exact, F is a power of two and q_l is odd (log2 F halvings in the kernel, no table).
+ * Result.  Coefficient i (n / count) of the output has phase F phi_i without normalisation, phi_i exactly with it, plus key-switch noise, phi_i the
+ *   phase of sample i.  With the trace every other coefficient has phase 0 plus noise; without it the others are unspecified.
+ * All arithmetic is exact and fhe_ct_apply_galois is deterministic: the output is a function of (samples, keys, count, trace, normalize) only, and
+ * every path gives the bits of the composition above written out with fhe_lwe_to_rlwe, fhe_rns_monomial_mul_sub, fhe_rns_poly_add / sub and
+ * fhe_ct_apply_galois.  Values >= q_l are the caller's error, as everywhere else.
+ *
+ * Per level the library runs ONE streaming launch and one batched fhe_ct_apply_galois.  The first level reads the pair of samples as 8-byte
+ * words and writes P and D of both components (the batch count embedded ciphertexts, 4 x the bytes of the samples, are never written); a later
+ * level reads (P_E, G_E, P_O, G_O), G the key-switched D of the level before, forms E = P_E + G_E and O = P_O + G_O in registers and writes the next
+ * P and D; the last sum and the sums of the trace go straight into the outputs.  FHE_HIP_NO_FUSED_PACK=1, read per call, runs the literal
+ * composition through container scratch instead (same bits).  Work goes on h's stream.
+ * Workspace.  The call's scratch is an allocation of the engine's own, which fhe_rns_ntt_workspace_bytes counts.  With S = L n 32 bytes:
+ *     3 batch count S                      count >= 2  (three regions, each both components of batch count / 2 ciphertexts)
+ *     2 batch S                            count == 1 with the trace;  nothing for count == 1 without
+ *     5 batch count S + 2 batch count      count >= 2 under FHE_HIP_NO_FUSED_PACK=1
+ *   beside what fhe_ct_apply_galois needs at the largest level batch, batch count / 2 (batch for count == 1).  fhe_lwe_pack_reserve sizes both (for
+ *   the path the environment selects when it is called); after it a call allocates nothing and can be captured into a hipGraph. */
+/* host only: elts[j-1] = 2^j + 1, j = 1 .. log2 n.  n a power of two, 8 <= n <= 2^30. */
+int fhe_lwe_pack_galois_elements(uint32_t n, uint32_t *elts);
+/* the embedding above for `batch` samples: d_lwe [batch][L][n+1] uint64_t -> d_c0, d_c1 [batch][L][n] containers.  fhe_rlwe_sample_extract(idx = 0)
+ * of the result gives d_lwe back bit for bit.  ONE launch, no workspace. */
+int fhe_lwe_to_rlwe(fhe_rns_ntt_t *h, void *d_c0, void *d_c1, const uint64_t *d_lwe, uint32_t batch);
+/* d_lwe [batch][count][L][n+1] -> (d_out0, d_out1) [batch][L][n].  gks: HOST array of log2(n) key-set handles, gks[j-1] the Galois keys of 2^j + 1
+ * (from fhe_keyswitch_keys_generate or fhe_relin_keys_create on h, one decomp_bits for all); an entry the call does not use (j > log2(count)
+ * without the trace) may be NULL.  fhe_lwe_pack and fhe_lwe_to_rlwe return FHE_ERR_INVALID_ARG, with nothing launched and nothing written: a null
+ * handle, output, input or needed key set; keys of another engine, or key sets of differing decomp_bits; a count that is zero, not a power of
+ * two, or above n; batch == 0, or batch count overflowing uint32_t (or batch count L above 2^31 - 1); a container pointer not 16-byte aligned, or
+ * d_lwe not 8-byte aligned; outputs overlapping each other or the input. */
+int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count, int trace,
+                 int normalize, uint32_t batch);
+int fhe_lwe_pack_reserve(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch);
+
 /* ---- batch encoder: slot values <-> plaintext polynomials on the device --------------------------------------------------------------
  * FHEContext::encode / decode and BatchEncoder (include/fhe.cuh:89-90, 150-157).  With psi = fhe_find_psi(n, t) and e(i) the exponent of slot i:
  *   FHE_SLOTS_NATURAL  e(i) = 2 i + 1                                          (what the mirror's host encode / decode evaluate)

@@ -1,0 +1,380 @@
+"""Packing LWE samples under the ring key into one RLWE ciphertext (fhe_lwe_to_rlwe, fhe_lwe_pack; definitions: include/fhe_hip.h).
+
+Everything is exact modular arithmetic, so every comparison is bit for bit: the embedding against numpy and against fhe_rlwe_sample_extract, the
+one-call packing against the same call under FHE_HIP_NO_FUSED_PACK=1 (a fresh child process) and against the composition written out here through
+capi in the level order of tests/lwe_pack_model.py, a round trip through fhe_ct_encrypt / fhe_rlwe_sample_extract / fhe_ct_decrypt, and the
+samples a bootstrap leaves."""
+import ctypes
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import lwe_pack_model as M
+import memcheck
+import ntt_math as nm
+from test_encrypt import _containers, _decrypt, _embed, _ints, _keygen
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIGMA, KEY_SEEDS = 3.2, (0x51, 0x52)
+INVALID, UNSUPPORTED = -1, -5
+W_OF = {30: 16, 40: 22, 64: 32}
+
+
+def _primes(bits, n, count):
+    return nm.largest_ntt_primes(bits, n, count) if bits == 64 else nm.ntt_primes(bits, n, count)
+
+
+def _samples(moduli, n, entries, seed):
+    """[entries][L][n + 1] uint64 below q_l, with 0 and q_l - 1 at a_0, a_{n-1} and b of the first samples."""
+    rng = np.random.default_rng(seed)
+    out = np.stack([rng.integers(0, q, (entries, n + 1), dtype=np.uint64) for q in moduli], axis=1)
+    for e, val in enumerate((0, -1)):
+        for l, q in enumerate(moduli):
+            out[e % entries, l, [0, n - 1, n]] = 0 if val == 0 else q - 1
+    return out
+
+
+def _embed_np(lwe, moduli):
+    """the definition: c0 = (b, 0, ..), c1[0] = a_0, c1[i] = -a_{n-i}; [entries][L][n + 1] -> two [entries][L][n][4]"""
+    n = lwe.shape[-1] - 1
+    c0 = np.zeros(lwe.shape[:2] + (n, 4), np.uint64); c1 = np.zeros_like(c0)
+    c0[:, :, 0, 0] = lwe[:, :, n]
+    c1[:, :, 0, 0] = lwe[:, :, 0]
+    for l, q in enumerate(moduli):
+        a = lwe[:, l, 1:n][:, ::-1]                     # a_{n-1} .. a_1 at i = 1 .. n-1
+        c1[:, l, 1:, 0] = np.where(a == 0, np.uint64(0), np.uint64(q) - a)
+    return c0, c1
+
+
+# ------------------------------------------------------------------------------------------------ embedding
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,bits", [(64, 30), (2048, 30), (2048, 40), (2048, 64)])
+def test_the_embedding_matches_numpy_and_inverts_extraction(pkg, n, bits):
+    L, batch = 2, 3
+    moduli = _primes(bits, n, L)
+    eng = pkg.RnsNttEngine(n, moduli)
+    if bits == 64:
+        assert eng.width_class == pkg.WIDTH_64X
+    lwe = _samples(moduli, n, batch, 5)
+    d_lwe = pkg.DeviceBuffer.from_numpy(lwe)
+    c0, c1 = pkg.DeviceBuffer(batch * L * n * 32), pkg.DeviceBuffer(batch * L * n * 32)
+    memcheck.poison(pkg, c0); memcheck.poison(pkg, c1)
+    eng.lwe_to_rlwe(c0, c1, d_lwe, batch)
+    w0, w1 = _embed_np(lwe, moduli)
+    assert np.array_equal(c0.download((batch, L, n, 4)), w0) and np.array_equal(c1.download((batch, L, n, 4)), w1)
+    back = pkg.DeviceBuffer(lwe.nbytes)
+    eng.sample_extract(back, c0, c1, 0, batch)
+    assert np.array_equal(back.download(lwe.shape), lwe)
+
+
+# ------------------------------------------------------------------------------------------------ bit identity
+# (n, bits, count, trace, normalize, batch): n = 2048 reaches the LDS-resident 4-byte and 8-byte key switches, n = 64 the streaming one; count = 64
+# at n = 64 runs every merge level and no trace step, count = 1 with the trace no merge level
+CASES = ([(2048, 30, c, tr, nz, b) for c in (1, 2, 8) for tr in (0, 1) for nz in (0, 1) for b in (1, 3)]
+         + [(2048, 40, 4, 1, 1, 2), (2048, 40, 4, 0, 0, 1), (64, 30, 64, 0, 1, 2), (64, 30, 64, 0, 0, 1), (64, 30, 1, 1, 1, 2), (64, 30, 1, 1, 0, 1)])
+_ctx, _fused = {}, {}
+
+
+def _context(pkg, n, bits):
+    """engine, ternary ring key and the log2(n) Galois key sets of 2^j + 1, once per (n, bits)"""
+    if (n, bits) not in _ctx:
+        moduli = _primes(bits, n, 2)
+        eng = pkg.RnsNttEngine(n, moduli)
+        s = np.random.default_rng(9).integers(-1, 2, n).astype(object)
+        ds = pkg.DeviceBuffer.from_numpy(_embed(s[None], moduli)[0])
+        sk = eng.import_secret_key(ds)
+        keys = eng.generate_keyswitch_keys(sk, W_OF[bits], pkg.capi.lwe_pack_galois_elements(n), 1, SIGMA, KEY_SEEDS)
+        _ctx[(n, bits)] = dict(moduli=moduli, eng=eng, keep=(ds, sk), keys=keys, s=s)
+    return _ctx[(n, bits)]
+
+
+def _case_samples(case):
+    n, bits, count, trace, normalize, batch = case
+    return _samples(_primes(bits, n, 2), n, batch * count, 100 + count + 7 * batch)
+
+
+def _pack(pkg, case, reserve=False):
+    """the one call, outputs poisoned first: (out0, out1) as [batch][L][n][4]"""
+    n, bits, count, trace, normalize, batch = case
+    C = _context(pkg, n, bits)
+    eng, nbytes = C["eng"], batch * 2 * n * 32
+    d_lwe = pkg.DeviceBuffer.from_numpy(_case_samples(case))
+    o0, o1 = pkg.DeviceBuffer(nbytes), pkg.DeviceBuffer(nbytes)
+    memcheck.poison(pkg, o0); memcheck.poison(pkg, o1)
+    if reserve:
+        eng.lwe_pack_reserve(C["keys"], count, trace, batch)
+    eng.lwe_pack(C["keys"], o0, o1, d_lwe, count, trace, normalize, batch)
+    return o0.download((batch, 2, n, 4)), o1.download((batch, 2, n, 4))
+
+
+def _fused_result(pkg, case):
+    if case not in _fused:
+        _fused[case] = _pack(pkg, case)
+    return _fused[case]
+
+
+def _compose(pkg, case):
+    """The definition through capi: fhe_lwe_to_rlwe, then per level fhe_rns_monomial_mul_sub + fhe_rns_poly_add (X^m O), poly_add / poly_sub (P, D),
+    fhe_ct_apply_galois (G) and poly_add (P + G); then the trace.  F^-1 is applied in numpy before the upload."""
+    n, bits, count, trace, normalize, batch = case
+    C = _context(pkg, n, bits)
+    eng, moduli, keys, L = C["eng"], C["moduli"], C["keys"], 2
+    lwe = _case_samples(case)
+    if normalize:
+        F = n if trace else count
+        lwe = np.stack([((lwe[:, l].astype(object) * pow(F, -1, q)) % q).astype(np.uint64) for l, q in enumerate(moduli)], axis=1)
+    S = L * n * 32
+    buf = lambda cts: (pkg.DeviceBuffer(cts * S), pkg.DeviceBuffer(cts * S))
+    R = buf(batch * count)
+    eng.lwe_to_rlwe(R[0], R[1], pkg.DeviceBuffer.from_numpy(lwe), batch * count)
+    cur = count
+    for _, half, c, g in M.merge_levels(count):
+        X, P, D, G, Rn = (buf(batch * half) for _ in range(5))
+        sh = pkg.DeviceBuffer.from_numpy(np.full(half, n // c, np.uint32))
+        for b in range(batch):
+            for k in range(2):
+                E = R[k].ptr + b * cur * S; O = E + half * S; at = b * half * S
+                eng.monomial_mul_sub(X[k].ptr + at, O, sh, half)
+                eng.poly_add(X[k].ptr + at, X[k].ptr + at, O, half)
+                eng.poly_add(P[k].ptr + at, E, X[k].ptr + at, half)
+                eng.poly_sub(D[k].ptr + at, E, X[k].ptr + at, half)
+        eng.apply_galois(keys[c.bit_length() - 2], g, G[0], G[1], D[0], D[1], batch * half)
+        for k in range(2):
+            eng.poly_add(Rn[k], P[k], G[k], batch * half)
+        pkg.capi.sync()
+        R, cur = Rn, half
+    if trace:
+        for j in range(count.bit_length(), n.bit_length()):
+            T, U = buf(batch), buf(batch)
+            eng.apply_galois(keys[j - 1], (1 << j) + 1, T[0], T[1], R[0], R[1], batch)
+            for k in range(2):
+                eng.poly_add(U[k], R[k], T[k], batch)
+            pkg.capi.sync()
+            R = U
+    return R[0].download((batch, L, n, 4)), R[1].download((batch, L, n, 4))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "n%d_b%d_c%d_t%d_z%d_x%d" % c)
+def test_the_call_equals_the_composition_written_through_capi(pkg, case):
+    got, want = _fused_result(pkg, case), _compose(pkg, case)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert not memcheck.is_poison(got[0][..., 0]) and (got[0][..., 1:] == 0).all() and (got[1][..., 1:] == 0).all()
+
+
+CHILD = """import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import importlib
+import numpy as np
+pkg = importlib.import_module("gpu-homomorphic-encryption_amd")
+import test_lwe_pack as T
+out = {{}}
+for i, case in enumerate(T.CASES):
+    out["a%d" % i], out["b%d" % i] = T._pack(pkg, case)
+    n, bits, count, trace, normalize, batch = case
+    if count >= 2:      # the composed path's container scratch: 5 batch count S and the shift words
+        assert T._context(pkg, n, bits)["eng"].workspace_bytes() >= 5 * batch * count * 2 * n * 32, case
+np.savez(sys.argv[1], **out)
+"""
+
+
+@pytest.mark.gpu
+def test_the_composed_path_in_a_child_process_gives_the_same_bits(pkg, tmp_path):
+    """FHE_HIP_NO_FUSED_PACK=1 for every case, in a fresh process so that the switch stays out of this one."""
+    (tmp_path / "child.py").write_text(CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests")))
+    env = dict(os.environ, FHE_HIP_NO_FUSED_PACK="1")
+    res = subprocess.run([sys.executable, str(tmp_path / "child.py"), str(tmp_path / "out.npz")], capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    got = np.load(tmp_path / "out.npz")
+    for i, case in enumerate(CASES):
+        want = _fused_result(pkg, case)
+        assert np.array_equal(got["a%d" % i], want[0]) and np.array_equal(got["b%d" % i], want[1]), case
+
+
+# ------------------------------------------------------------------------------------------------ round trips
+@pytest.mark.gpu
+def test_round_trip_through_the_ring(pkg, oracle):
+    """encrypt -> extract 8 coefficients -> pack (trace) -> decrypt: the 8 coefficients come back and every other one is 0, exactly.  Key-switch
+    noise: d_noise_bits is printed; it measured 40 bits against Q / 2 of 58 bits (two 30-bit primes), 18 bits to spare, so two primes stay."""
+    n, L, t, count = 2048, 2, 257, 8
+    moduli = _primes(30, n, L)
+    s, pk0, pk1 = _keygen(oracle, n, moduli, t, 31)
+    eng = pkg.RnsNttEngine(n, moduli)
+    src = (pkg.DeviceBuffer.from_numpy(pk0), pkg.DeviceBuffer.from_numpy(pk1))
+    pk = eng.import_public_key(*src)
+    ds = pkg.DeviceBuffer.from_numpy(_embed(s[None], moduli)[0])
+    sk = eng.import_secret_key(ds)
+    keys = eng.generate_keyswitch_keys(sk, 16, pkg.capi.lwe_pack_galois_elements(n), t, SIGMA, KEY_SEEDS)
+    msg = np.random.default_rng(4).integers(0, t, (1, n)).astype(object)
+    S = L * n * 32
+    c0, c1 = pkg.DeviceBuffer(S), pkg.DeviceBuffer(S)
+    eng.encrypt(pk, t, SIGMA, (11, 22, 33), c0, c1, pkg.DeviceBuffer.from_numpy(_embed(msg, moduli)), 1)
+    d_lwe = pkg.DeviceBuffer(count * L * (n + 1) * 8)
+    step = n // count
+    for i in range(count):
+        eng.sample_extract(d_lwe.ptr + i * L * (n + 1) * 8, c0, c1, i * step, 1)
+    want = np.zeros(n, dtype=object); want[::step] = msg[0, ::step]
+    Qbits = math.prod(moduli).bit_length()
+    for normalize, factor in ((True, 1), (False, n)):
+        p0, p1 = pkg.DeviceBuffer(S), pkg.DeviceBuffer(S)
+        eng.lwe_pack(keys, p0, p1, d_lwe, count, True, normalize, 1)
+        dm, dn = pkg.DeviceBuffer(n * 8), pkg.DeviceBuffer(4)
+        eng.decrypt(sk, t, 1, dm, dn, [p0, p1], 1)
+        bits = int(dn.download((1,), np.uint32)[0])
+        print(f"lwe_pack round trip: normalize={normalize} d_noise_bits={bits}, Q has {Qbits} bits")
+        assert np.array_equal(dm.download((1, n))[0], ((want * factor) % t).astype(np.uint64)), normalize
+    _ = src
+
+
+@pytest.mark.gpu
+def test_packing_the_output_of_a_bootstrap(pkg, oracle):
+    """The four samples test_bootstrap_end_to_end.py extracts (all L limbs), packed with count = 4: coefficient i n / 4 of the packed ciphertext
+    has the phase Delta f(m_i) up to noise below Delta / 2."""
+    import test_bootstrap_end_to_end as be
+    st = be._setup(pkg)
+    moduli, f, n = st["moduli"], be.TABLES["table"], be.N
+    Q, delta, tv = be._test_vector(moduli, f)
+    lwe = be._device(pkg, st, tv)                                        # [4][L][n + 1]
+    eng, sk = st["eng"], st["keep"][1]
+    keys = eng.generate_keyswitch_keys(sk, be.W, pkg.capi.lwe_pack_galois_elements(n), 1, SIGMA, KEY_SEEDS)
+    S = be.L * n * 32
+    p0, p1 = pkg.DeviceBuffer(S), pkg.DeviceBuffer(S)
+    eng.lwe_pack(keys, p0, p1, pkg.DeviceBuffer.from_numpy(lwe), 4, True, True, 1)
+    v = _decrypt(oracle, n, moduli, 1, np.array(st["s"], dtype=object), p0.download((1, be.L, n, 4)), p1.download((1, be.L, n, 4)))[0]
+    worst = 0
+    for i, m in enumerate(be.MSGS):
+        err = abs(int(v[i * n // 4]) - delta * f[m]); worst = max(worst, err)
+        assert err < delta // 2, (i, m, err.bit_length(), delta.bit_length())
+    others = max(abs(int(x)) for k, x in enumerate(v) if k % (n // 4))
+    assert others < delta // 2
+    print(f"packed bootstrap: noise {worst.bit_length()} bits at the targets, {others.bit_length()} bits elsewhere, Delta / 2 is {(delta // 2).bit_length()} bits")
+
+
+# ------------------------------------------------------------------------------------------------ arguments, workspace
+@pytest.mark.gpu
+def test_rejections_leave_guarded_poisoned_outputs_untouched(pkg):
+    n, bits, count, batch, L = 2048, 30, 4, 2, 2
+    C = _context(pkg, n, bits)
+    eng, keys, lib = C["eng"], C["keys"], pkg.lib()
+    other = _context(pkg, 2048, 40)
+    S = L * n * 32
+    lwe = _samples(C["moduli"], n, batch * count, 3)
+    arena = memcheck.GuardedArena(pkg, [("o0", batch * S), ("o1", batch * S), ("lwe", lwe.nbytes)], S)
+    arena["lwe"].upload(lwe); arena["o0"].poison(); arena["o1"].poison()
+    h, o0, o1, dl = eng.h, arena["o0"].ptr, arena["o1"].ptr, arena["lwe"].ptr
+    ka = lambda ks: (ctypes.c_void_p * len(ks))(*[None if k is None else k.h for k in ks])
+    good = ka(keys)
+    w8 = eng.generate_keyswitch_keys(C["keep"][1], 8, [5], 1, SIGMA, KEY_SEEDS)[0]
+    pack = lambda *a: lib.fhe_lwe_pack(*a)
+    bad = {
+        "null handle": (None, good, o0, o1, dl, count, 1, 1, batch),
+        "null output": (h, good, None, o1, dl, count, 1, 1, batch),
+        "null output 1": (h, good, o0, None, dl, count, 1, 1, batch),
+        "null input": (h, good, o0, o1, None, count, 1, 1, batch),
+        "null key array": (h, None, o0, o1, dl, count, 1, 1, batch),
+        "null merge key": (h, ka([keys[0], None] + keys[2:]), o0, o1, dl, count, 0, 1, batch),
+        "null trace key": (h, ka(keys[:-1] + [None]), o0, o1, dl, count, 1, 1, batch),
+        "keys of another engine": (h, ka(other["keys"]), o0, o1, dl, count, 1, 1, batch),
+        "differing decomp_bits": (h, ka([keys[0], w8] + keys[2:]), o0, o1, dl, count, 1, 1, batch),
+        "count 0": (h, good, o0, o1, dl, 0, 1, 1, batch),
+        "count 3": (h, good, o0, o1, dl, 3, 1, 1, batch),
+        "count above n": (h, good, o0, o1, dl, 2 * n, 1, 1, batch),
+        "batch 0": (h, good, o0, o1, dl, count, 1, 1, 0),
+        "batch count overflow": (h, good, o0, o1, dl, 1024, 1, 1, 1 << 22),
+        "misaligned output": (h, good, o0 + 8, o1, dl, count, 1, 1, batch),
+        "misaligned input": (h, good, o0, o1, dl + 4, count, 1, 1, batch),
+        "outputs overlap": (h, good, o0, o0 + S, dl, count, 1, 1, batch),
+        "output overlaps input": (h, good, dl + 32, o1, dl, count, 1, 1, batch),
+    }
+    for name, args in bad.items():
+        assert pack(*args) == INVALID, name
+    assert lib.fhe_lwe_pack(h, ka(keys[:2] + [None] * (len(keys) - 2)), o0, o1, dl, count, 0, 1, 0) == INVALID
+    embed_bad = {
+        "null handle": (None, o0, o1, dl, batch), "null output": (h, None, o1, dl, batch), "null input": (h, o0, o1, None, batch),
+        "batch 0": (h, o0, o1, dl, 0), "misaligned output": (h, o0, o1 + 16 - 8, dl, batch), "misaligned input": (h, o0, o1, dl + 4, batch),
+        "outputs overlap": (h, o0, o0 + S, dl, batch), "output overlaps input": (h, o0, dl, dl, batch),
+    }
+    for name, args in embed_bad.items():
+        assert lib.fhe_lwe_to_rlwe(*args) == INVALID, name
+    arena.verify(inputs=("lwe",))
+    assert memcheck.is_poison(arena["o0"].download((-1,))) and memcheck.is_poison(arena["o1"].download((-1,)))
+    # unused key sets may be null: count = 4 without the trace uses keys[0] and keys[1] only
+    assert lib.fhe_lwe_pack(h, ka(keys[:2] + [None] * (len(keys) - 2)), o0, o1, dl, count, 0, 1, batch) == 0
+    arena.verify(inputs=("lwe",))
+    got = arena["o0"].download((batch, L, n, 4)), arena["o1"].download((batch, L, n, 4))
+    d = pkg.DeviceBuffer.from_numpy(lwe); q0, q1 = pkg.DeviceBuffer(batch * S), pkg.DeviceBuffer(batch * S)
+    eng.lwe_pack(keys, q0, q1, d, count, False, True, batch)
+    assert np.array_equal(got[0], q0.download((batch, L, n, 4))) and np.array_equal(got[1], q1.download((batch, L, n, 4)))
+
+
+@pytest.mark.gpu
+def test_a_full_width_engine_is_unsupported(pkg):
+    n = 2048
+    eng = pkg.RnsNttEngine(n, nm.ntt_primes(120, n, 2))
+    S = 2 * n * 32
+    o0, o1, d = pkg.DeviceBuffer(S), pkg.DeviceBuffer(S), pkg.DeviceBuffer(2 * (n + 1) * 8)
+    memcheck.poison(pkg, o0)
+    keys = (ctypes.c_void_p * 11)()
+    lib = pkg.lib()
+    assert lib.fhe_lwe_pack(eng.h, keys, o0.ptr, o1.ptr, d.ptr, 1, 0, 0, 1) == UNSUPPORTED
+    assert lib.fhe_lwe_to_rlwe(eng.h, o0.ptr, o1.ptr, d.ptr, 1) == UNSUPPORTED
+    assert lib.fhe_lwe_pack_reserve(eng.h, keys, 1, 0, 1) == UNSUPPORTED
+    assert memcheck.is_poison(o0.download((-1,)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count,trace", [(8, True), (1, True), (4, False)])
+def test_after_the_reserve_a_call_leaves_the_workspace_alone(pkg, count, trace):
+    n, L, batch = 2048, 2, 3
+    C = _context(pkg, n, 30)
+    eng = pkg.RnsNttEngine(n, C["moduli"])                               # a fresh engine: nothing has grown yet
+    ds = pkg.DeviceBuffer.from_numpy(_embed(C["s"][None], C["moduli"])[0])
+    sk = eng.import_secret_key(ds)
+    keys = eng.generate_keyswitch_keys(sk, 16, pkg.capi.lwe_pack_galois_elements(n), 1, SIGMA, KEY_SEEDS)
+    before = eng.workspace_bytes()
+    eng.lwe_pack_reserve(keys, count, trace, batch)
+    reserved = eng.workspace_bytes()
+    own = 3 * batch * count * L * n * 32 if count >= 2 else 2 * batch * L * n * 32
+    assert reserved - before >= own
+    case = (n, 30, count, int(trace), 1, batch)
+    d = pkg.DeviceBuffer.from_numpy(_case_samples(case))
+    o0, o1 = pkg.DeviceBuffer(batch * L * n * 32), pkg.DeviceBuffer(batch * L * n * 32)
+    eng.lwe_pack(keys, o0, o1, d, count, trace, True, batch)
+    assert eng.workspace_bytes() == reserved
+    if case in CASES:                                                    # same keys (seeds) and samples as the shared context: same bits
+        want = _fused_result(pkg, case)
+        assert np.array_equal(o0.download((batch, L, n, 4)), want[0]) and np.array_equal(o1.download((batch, L, n, 4)), want[1])
+
+
+# ------------------------------------------------------------------------------------------------ capture
+CAP_SRC = os.path.join(ROOT, "tests", "cpp", "test_lwe_pack_capture.cpp")
+CAP_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_lwe_pack_capture")
+
+
+def _build_capture(pkg):
+    pkg.build_library()
+    lib_dir = os.path.dirname(pkg.library_path())
+    os.makedirs(os.path.dirname(CAP_EXE), exist_ok=True)
+    deps = [CAP_SRC, os.path.join(ROOT, "include", "fhe_hip.h")]
+    if os.path.exists(CAP_EXE) and all(os.path.getmtime(CAP_EXE) >= os.path.getmtime(d) for d in deps):
+        return CAP_EXE
+    cmd = ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), CAP_SRC, "-L", lib_dir, "-lfhe_hip", f"-Wl,-rpath,{lib_dir}", "-o", CAP_EXE]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    return CAP_EXE
+
+
+def test_lwe_pack_capture_test_compiles(pkg):
+    _build_capture(pkg)
+
+
+@pytest.mark.gpu
+def test_a_captured_call_replays_the_eager_bits_as_a_linear_chain(pkg):
+    res = subprocess.run([_build_capture(pkg)], capture_output=True, text=True, timeout=300)
+    print(res.stdout)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "lwe pack capture ok" in res.stdout
