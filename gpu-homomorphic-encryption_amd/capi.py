@@ -128,6 +128,7 @@ def lib():
         "fhe_rgsw_keys_generate": ([vp, vp, u32, P(ctypes.c_int32), u32, u64, ctypes.c_double, P(u64), P(vp), P(vp)], ci),
         "fhe_lwe_prepare_accumulator": ([vp, u64, u32, vp, vp, vp, vp, vp, u32], ci),
         "fhe_rlwe_sample_extract": ([vp, vp, vp, vp, u32, u32], ci),
+        "fhe_rlwe_sample_extract_strided": ([vp, vp, vp, vp, u32, u32], ci),
         "fhe_lwe_ksk_num_digits": ([vp, u32, P(u32)], ci),
         "fhe_lwe_ksk_create": ([vp, P(vp), u32, u32, vp], ci),
         "fhe_lwe_ksk_export": ([vp, vp, vp], ci),
@@ -139,6 +140,7 @@ def lib():
         "fhe_lwe_to_rlwe": ([vp, vp, vp, vp, u32], ci),
         "fhe_lwe_pack": ([vp, P(vp), vp, vp, vp, u32, ci, ci, u32], ci),
         "fhe_lwe_pack_reserve": ([vp, P(vp), u32, ci, u32], ci),
+        "fhe_rlwe_pack": ([vp, P(vp), vp, vp, vp, vp, u32, ci, ci, u32], ci),
         "fhe_batch_encoder_create": ([vp, P(vp), u64, ci], ci),
         "fhe_batch_encoder_destroy": ([vp], ci),
         "fhe_batch_encoder_reserve": ([vp, vp, u32], ci),
@@ -596,6 +598,11 @@ class RnsNttEngine:
         """Coefficient idx of (c0, c1) as LWE samples: d_out = device uint64 [batch][L][n + 1]."""
         _check(lib().fhe_rlwe_sample_extract(self.h, _ptr(d_out), _ptr(d_c0), _ptr(d_c1), idx, batch))
 
+    def sample_extract_strided(self, d_out, d_c0, d_c1, count, batch=1):
+        """Coefficients i n / count, i < count, of (c0, c1) as LWE samples in one launch: d_out = device uint64 [batch][count][L][n + 1], row
+        (b, i, l) what sample_extract writes at idx = i n / count.  The d_lwe of lwe_pack; on a one-limb engine the d_in of lwe_keyswitch."""
+        _check(lib().fhe_rlwe_sample_extract_strided(self.h, _ptr(d_out), _ptr(d_c0), _ptr(d_c1), count, batch))
+
     lwe_pack_galois_elements = staticmethod(lwe_pack_galois_elements)
 
     def lwe_to_rlwe(self, d_c0, d_c1, d_lwe, batch=1):
@@ -615,6 +622,12 @@ class RnsNttEngine:
     def lwe_pack_reserve(self, keys, count, trace=True, batch=1):
         """Pre-size what lwe_pack needs for this shape (its own scratch and the key switch's): afterwards a call allocates nothing."""
         _check(lib().fhe_lwe_pack_reserve(self.h, self._pack_keys(keys), count, int(bool(trace)), batch))
+
+    def rlwe_pack(self, keys, d_out0, d_out1, d_c0, d_c1, count, trace=True, normalize=True, batch=1):
+        """lwe_pack of coefficient 0 of batch * count RLWE pairs, (d_c0, d_c1) = [batch][count][L][n] containers as blind_rotate leaves them,
+        without the samples in between: the bits of sample_extract(idx = 0) + lwe_pack.  lwe_pack_reserve sizes the scratch of both."""
+        _check(lib().fhe_rlwe_pack(self.h, self._pack_keys(keys), _ptr(d_out0), _ptr(d_out1), _ptr(d_c0), _ptr(d_c1), count, int(bool(trace)),
+                                   int(bool(normalize)), batch))
 
     def lwe_ksk_num_digits(self, decomp_bits):
         """K = ceil(bit_length(q_0) / decomp_bits): the LWE key-switching key of this engine has n K rows."""

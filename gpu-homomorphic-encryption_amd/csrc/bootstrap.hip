@@ -1,6 +1,7 @@
 // bootstrap.hip -- what stands around the blind-rotation loop (fhe_blind_rotate, keyswitch.hip): an LWE ciphertext into the loop's inputs
-// (fhe_lwe_prepare_accumulator) and one coefficient of the result out as an LWE sample (fhe_rlwe_sample_extract).  One launch each, no
-// workspace, nothing allocated: both can be captured into a hipGraph with the loop.  Kernels: bootstrap.hip.h.  (The RGSW rows the loop
+// (fhe_lwe_prepare_accumulator), one coefficient of the result out as an LWE sample (fhe_rlwe_sample_extract), and `count` evenly spaced
+// coefficients of a ciphertext out in the layout the key switch and the packer read (fhe_rlwe_sample_extract_strided).  One launch each, no
+// workspace, nothing allocated: all can be captured into a hipGraph with the loop.  Kernels: bootstrap.hip.h.  (The RGSW rows the loop
 // consumes: fhe_rgsw_keys_generate, keygen.hip.)
 #include "engine.h"
 
@@ -59,6 +60,37 @@ extern "C" int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const 
         using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
         hipLaunchKernelGGL((fhe_dev::sample_extract_kernel<LimbT>), dim3(bx, by), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, idx, h->L, h->log_n, polys);
         return post_launch(h->stream, "sample_extract_kernel");
+    };
+    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+
+extern "C" int fhe_rlwe_sample_extract_strided(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t count, uint32_t batch) {
+    int rc = check_call(h, batch, "rlwe_sample_extract_strided"); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "rlwe_sample_extract_strided: every modulus must be below 2^64");
+    if (!d_out || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: null argument");
+    if ((rc = check_aligned({d_c0, d_c1}, "rlwe_sample_extract_strided"))) return rc;
+    if ((uintptr_t)d_out & 7) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: d_out must be 8-byte aligned");
+    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: n must be at least 8");
+    if (!count || (count & (count - 1)) || count > h->n) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: count must be a power of two in [1, n]");
+    if ((uint64_t)batch * count > 0xffffffffull || (uint64_t)batch * count * h->L > 0x7fffffffull)                   // what fhe_lwe_pack accepts
+        return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: batch * count * num_primes too large");
+    const size_t polys = (size_t)batch * h->L, in = polys * h->n * 32, out = polys * count * ((size_t)h->n + 1) * 8;
+    if (overlaps(d_out, out, d_c0, in) || overlaps(d_out, out, d_c1, in)) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: the output overlaps an input");
+    if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
+    using V = fhe_dev::v2u64;
+    uint32_t log_count = 0; while ((1u << log_count) < count) log_count++;
+    // x: the positions of a row; y: the polynomials; z: runs of rows, as many as it takes to reach ~4096 workgroups (16 per CU) where x and y
+    // alone give fewer, each run at least 8 rows long so that a loaded coefficient is stored 8 times or more
+    const unsigned bx = (unsigned)std::min<size_t>(((size_t)h->n + 255) / 256, 64), by = (unsigned)std::min<size_t>(polys, 65535);
+    const size_t want = (4096 + (size_t)bx * by - 1) / ((size_t)bx * by);
+    const uint32_t runs = (uint32_t)std::max<size_t>(1, std::min<size_t>(want, std::max<uint32_t>(1, count / 8)));
+    const uint32_t rows_per_block = (count + runs - 1) / runs, bz = (count + rows_per_block - 1) / rows_per_block;
+    auto launch = [&](auto *limbs) {
+        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        hipLaunchKernelGGL((fhe_dev::sample_extract_strided_kernel<LimbT>), dim3(bx, by, bz), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, log_count,
+                           rows_per_block, h->L, h->log_n, polys);
+        return post_launch(h->stream, "sample_extract_strided_kernel");
     };
     if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
     return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });

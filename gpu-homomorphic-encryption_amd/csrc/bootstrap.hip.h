@@ -1,6 +1,7 @@
-// bootstrap.hip.h -- the two streaming kernels around the blind-rotation loop (fhe_lwe_prepare_accumulator, fhe_rlwe_sample_extract;
-// contract: include/fhe_hip.h), for moduli below 2^64.  No transform, no workspace: one pass over HBM each, launched by bootstrap.hip only.
-// Neither kernel multiplies: a residue below 2^64 is the low 8 bytes of its container in every width class (the upper 24 bytes are zero), so
+// bootstrap.hip.h -- the streaming kernels around the blind-rotation loop (fhe_lwe_prepare_accumulator, fhe_rlwe_sample_extract and its
+// strided form fhe_rlwe_sample_extract_strided; contract: include/fhe_hip.h), for moduli below 2^64.  No transform, no workspace: one pass
+// over HBM each, launched by bootstrap.hip only.
+// No kernel here multiplies: a residue below 2^64 is the low 8 bytes of its container in every width class (the upper 24 bytes are zero), so
 // one instance per limb-table type serves every field -- LimbT = Limb<F> of the word-sized classes, Limb256 of an engine whose size has no
 // word-sized kernels (n < 2^11) but whose moduli fit a word.
 #pragma once
@@ -75,6 +76,41 @@ sample_extract_kernel(uint64_t *__restrict__ out, const v2u64 *__restrict__ c0, 
                 if (j > idx && v) v = q - v;
             }
             __builtin_nontemporal_store(v, row + j);
+        }
+    }
+}
+
+// Sample extraction at the `count` coefficients idx_i = i n / count of every pair in ONE launch: row (b, i, l) of out, [batch][count][L][n + 1],
+// is what sample_extract_kernel writes for polynomial p = b L + l at idx_i.  Row i is row 0 rotated by idx_i, so a lane is bound to ONE source
+// coefficient, x = -j0 mod n, j0 its position in row 0: it loads c1[p][x] once, keeps v and q_l - v in registers, and stores one of the two at
+// j = (j0 + idx_i) mod n of every row of its block -- the negated value where j0 != 0 and j0 + idx_i < n (then j > idx_i: the source index
+// wrapped).  The discipline of the kernel above holds: for one row a wave stores 64 consecutive 8-byte words in lane order (non-temporal; rows
+// are n + 1 words long, so their starts alternate between 16- and 8-byte alignment and nothing wider than a word is stored), and the reversal
+// is on the load side.  blockIdx.y strides over the polynomials, blockIdx.z splits the rows of one polynomial into runs of `rows_per_block`
+// (more workgroups where batch L n alone cannot fill the device): c1 comes from HBM once per ciphertext and is re-read by the gridDim.z - 1
+// other blocks of the polynomial through L2, hence the TEMPORAL load.  Lane j0 = i also writes b of row i, c0[p][idx_i].
+template <class LimbT>
+__global__ void __launch_bounds__(256)
+sample_extract_strided_kernel(uint64_t *__restrict__ out, const v2u64 *__restrict__ c0, const v2u64 *__restrict__ c1, const LimbT *__restrict__ limbs,
+                              uint32_t log_count, uint32_t rows_per_block, uint32_t L, uint32_t log_n, size_t polys) {
+    const uint32_t n = 1u << log_n, count = 1u << log_count, sh = log_n - log_count;
+    const size_t row_len = (size_t)n + 1;
+    const uint32_t i_lo = blockIdx.z * rows_per_block, i_hi = min(count, i_lo + rows_per_block);
+    for (size_t p = blockIdx.y; p < polys; p += gridDim.y) {
+        const size_t b = p / L;
+        const uint32_t l = (uint32_t)(p - b * L);
+        const uint64_t q = limb_q64(limbs[l]);
+        uint64_t *rows = out + ((b << log_count) * L + l) * row_len;            // row (b, 0, l); row (b, i, l) is i L row_len words further
+        for (uint32_t j0 = blockIdx.x * blockDim.x + threadIdx.x; j0 < n; j0 += gridDim.x * blockDim.x) {
+            const uint64_t v = *reinterpret_cast<const uint64_t *>(c1 + ((p << log_n) + ((n - j0) & (n - 1))) * 2);
+            const uint64_t vn = (j0 && v) ? q - v : v;
+            for (uint32_t i = i_lo; i < i_hi; i++) {
+                const uint32_t j = j0 + (i << sh);
+                __builtin_nontemporal_store(j < n ? vn : v, rows + (size_t)i * L * row_len + (j & (n - 1)));
+            }
+            if (j0 >= i_lo && j0 < i_hi)
+                __builtin_nontemporal_store(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(c0 + ((p << log_n) + ((size_t)j0 << sh)) * 2)),
+                                            rows + (size_t)j0 * L * row_len + n);
         }
     }
 }

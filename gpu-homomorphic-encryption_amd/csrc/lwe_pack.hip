@@ -1,10 +1,12 @@
 // lwe_pack.hip -- the way back from bootstrapping: LWE samples under the ring key (what fhe_rlwe_sample_extract writes) into one RLWE ciphertext
-// (fhe_lwe_to_rlwe, fhe_lwe_pack*; contract and algorithm: include/fhe_hip.h).  The ring packing of Chen, Dai, Kim and Song: log2(count) merge
+// (fhe_lwe_to_rlwe, fhe_lwe_pack*; contract and algorithm: include/fhe_hip.h), and the same from coefficient 0 of RLWE pairs, the blind rotation's
+// accumulators, without the samples in between (fhe_rlwe_pack).  The ring packing of Chen, Dai, Kim and Song: log2(count) merge
 // levels and, with the trace, log2(n / count) more automorphisms, every one a batched fhe_ct_apply_galois.
-// Fused path (kernels: lwe_pack.hip.h): per level one streaming launch and one key switch.  The first level reads the samples themselves, a later
+// Fused path (kernels: lwe_pack.hip.h): per level one streaming launch and one key switch.  The first level reads the samples (or the pairs) themselves, a later
 // one forms the "P + G" of the level before in registers; three regions of the packing workspace d_pack rotate as (P, G, free).
 // Composed path (FHE_HIP_NO_FUSED_PACK=1, read per call): the literal composition of entry points through container scratch in d_pack -- the
-// embedding, fhe_rns_monomial_mul_sub, fhe_rns_poly_add / sub, fhe_ct_apply_galois -- one batch element at a time where the pairs are strided.
+// embedding, fhe_rns_monomial_mul_sub, fhe_rns_poly_add / sub, fhe_ct_apply_galois -- one batch element at a time where the pairs are strided;
+// fhe_rlwe_pack runs fhe_rlwe_sample_extract(idx = 0) into sample scratch at the end of d_pack first.
 #include "engine.h"
 
 #include <type_traits>
@@ -24,13 +26,22 @@ extern "C" int fhe_lwe_pack_galois_elements(uint32_t n, uint32_t *elts) {
     return FHE_OK;
 }
 
+// what a packing call packs: LWE samples (fhe_lwe_pack), or coefficient 0 of RLWE pairs (fhe_rlwe_pack; lwe == nullptr)
+struct PackSource { const uint64_t *lwe; const void *c0, *c1; };
+
 // the embedding (PAIR = false) or the first merge level (PAIR = true) of `entries` output ciphertexts
 template <bool PAIR>
-static int launch_embed(fhe_rns_ntt *h, void *o0, void *o1, void *d0, void *d1, const uint64_t *d_lwe, uint32_t half, uint32_t halvings, size_t entries) {
+static int launch_embed(fhe_rns_ntt *h, void *o0, void *o1, void *d0, void *d1, const PackSource &src, uint32_t half, uint32_t halvings, size_t entries) {
     using V = fhe_dev::v2u64;
     const size_t halves = entries * h->L * h->n * 2;
+    const uint64_t *d_lwe = src.lwe;
     auto launch = [&](auto *limbs) {
         using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
+        if (!d_lwe) {
+            hipLaunchKernelGGL((fhe_dev::rlwe_embed_merge_kernel<LimbT, PAIR>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1,
+                               (const V *)src.c0, (const V *)src.c1, limbs, half, halvings, h->L, h->log_n, halves);
+            return post_launch(h->stream, PAIR ? "rlwe_embed_merge_kernel (first level)" : "rlwe_embed_merge_kernel (embedding)");
+        }
         hipLaunchKernelGGL((fhe_dev::lwe_embed_merge_kernel<LimbT, PAIR>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1, d_lwe, limbs,
                            half, halvings, h->L, h->log_n, halves);
         return post_launch(h->stream, PAIR ? "lwe_embed_merge_kernel (first level)" : "lwe_embed_merge_kernel (embedding)");
@@ -80,7 +91,7 @@ extern "C" int fhe_lwe_to_rlwe(fhe_rns_ntt_t *h, void *d_c0, void *d_c1, const u
     const size_t polys = (size_t)batch * h->L, out = polys * h->n * 32, in = polys * ((size_t)h->n + 1) * 8;
     if (overlaps(d_c0, out, d_c1, out)) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: the outputs must not overlap");
     if (overlaps(d_c0, out, d_lwe, in) || overlaps(d_c1, out, d_lwe, in)) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: an output overlaps the input");
-    return launch_embed<false>(h, d_c0, d_c1, nullptr, nullptr, d_lwe, 0, 0, batch);
+    return launch_embed<false>(h, d_c0, d_c1, nullptr, nullptr, PackSource{d_lwe, nullptr, nullptr}, 0, 0, batch);
 }
 
 // ---- the packing call ----------------------------------------------------------------------------------------------------------------
@@ -112,11 +123,19 @@ static int check_pack_shape(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, 
     return FHE_OK;
 }
 // bytes of d_pack for a call.  Fused: three regions of batch count S (S = L n 32; a region holds both components of batch count / 2
-// ciphertexts), or the trace's pair alone for count = 1.  Composed: R (batch count ciphertexts), X, P, D (half as many each) and the shift words.
+// ciphertexts), or the trace's pair alone for count = 1.  Composed: R (batch count ciphertexts), X, P, D (half as many each) and the shift words,
+// then, from a 16-byte boundary (composed_samples_at), the batch count samples that fhe_rlwe_pack extracts first: fhe_lwe_pack_reserve cannot know
+// which of the two entries follows, so the composed size covers both.
+static size_t composed_samples_at(const fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch) {
+    const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count;
+    const size_t own = S.k ? 5 * bc * poly + 2 * bc : (S.last_trace ? 2 * batch * poly : 0);
+    return (own + 15) & ~(size_t)15;
+}
 static size_t pack_bytes(const fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch, bool composed) {
     const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count;
+    if (composed) return composed_samples_at(h, S, count, batch) + bc * h->L * ((size_t)h->n + 1) * 8;
     if (!S.k) return S.last_trace ? 2 * batch * poly : 0;
-    return composed ? 5 * bc * poly + 2 * bc : 3 * bc * poly;
+    return 3 * bc * poly;
 }
 static int ensure_pack(fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch, bool composed) {
     int rc = grow_ws(h, &h->d_pack, &h->pack_bytes, pack_bytes(h, S, count, batch, composed)); if (rc) return rc;
@@ -141,19 +160,19 @@ static int pack_trace(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const 
     return FHE_OK;
 }
 
-static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count,
+static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const PackSource &src, uint32_t count,
                       uint32_t halvings, uint32_t batch) {
     const size_t poly = (size_t)h->L * h->n * 32, region = (size_t)batch * count * poly;
     char *base = (char *)h->d_pack;
     int rc;
     if (!S.k) {
-        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, d_lwe, 0, halvings, batch))) return rc;
+        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, src, 0, halvings, batch))) return rc;
         return pack_trace(h, gks, S, d_out0, d_out1, base, base + batch * poly, batch, false);
     }
     char *reg_p = base, *reg_g = base + 2 * region, *reg_free = base + region;
     size_t e = (size_t)batch * (count / 2);                                   // ciphertexts the level writes
     // level 1: P -> reg_p, D -> reg_free, G = key-switched sigma_3(D) -> reg_g
-    if ((rc = launch_embed<true>(h, reg_p, reg_p + e * poly, reg_free, reg_free + e * poly, d_lwe, count / 2, halvings, e))) return rc;
+    if ((rc = launch_embed<true>(h, reg_p, reg_p + e * poly, reg_free, reg_free + e * poly, src, count / 2, halvings, e))) return rc;
     if ((rc = fhe_ct_apply_galois(h, gks[0], 3, reg_g, reg_g + e * poly, reg_free, reg_free + e * poly, (uint32_t)e))) return rc;
     const char *p0 = reg_p, *p1 = reg_p + e * poly, *g0 = reg_g, *g1 = reg_g + e * poly;
     for (uint32_t l = 2; l <= S.k; l++) {
@@ -171,18 +190,23 @@ static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const 
     return pack_trace(h, gks, S, d_out0, d_out1, reg_free, reg_free + batch * poly, batch, false);
 }
 
-static int pack_composed(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count,
+static int pack_composed(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, PackSource src, uint32_t count,
                          uint32_t halvings, uint32_t batch) {
     const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count, hb = bc / 2 * poly;
     char *base = (char *)h->d_pack;
     int rc;
+    if (!src.lwe) {                                                             // fhe_rlwe_pack: the literal extraction at idx = 0 of every pair first
+        uint64_t *samples = (uint64_t *)(base + composed_samples_at(h, S, count, batch));
+        if ((rc = fhe_rlwe_sample_extract(h, samples, src.c0, src.c1, 0, (uint32_t)bc))) return rc;
+        src = PackSource{samples, nullptr, nullptr};
+    }
     if (!S.k) {
-        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, d_lwe, 0, halvings, batch))) return rc;
+        if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, src, 0, halvings, batch))) return rc;
         return pack_trace(h, gks, S, d_out0, d_out1, base, base + batch * poly, batch, true);
     }
     char *R[2] = {base, base + bc * poly}, *X[2] = {base + 2 * bc * poly, base + 2 * bc * poly + hb}, *P[2] = {X[1] + hb, X[1] + 2 * hb}, *D[2] = {P[1] + hb, P[1] + 2 * hb};
     uint32_t *shifts = (uint32_t *)(D[1] + hb);
-    if ((rc = launch_embed<false>(h, R[0], R[1], nullptr, nullptr, d_lwe, 0, halvings, bc))) return rc;       // fhe_lwe_to_rlwe of F^-1 times the samples
+    if ((rc = launch_embed<false>(h, R[0], R[1], nullptr, nullptr, src, 0, halvings, bc))) return rc;       // fhe_lwe_to_rlwe of F^-1 times the samples
     for (uint32_t l = 1, cur = count; l <= S.k; l++, cur /= 2) {
         const uint32_t half = cur / 2, e = batch * half;
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)shifts, (int)(h->n >> l), half, h->stream));
@@ -216,6 +240,25 @@ extern "C" int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks
     const bool composed = pack_composed_env();
     if ((rc = ensure_pack(h, S, count, batch, composed))) return rc;              // (no-op after fhe_lwe_pack_reserve)
     const uint32_t halvings = normalize ? (trace ? h->log_n : S.k) : 0;           // F = n with the trace, count without
-    return composed ? pack_composed(h, gks, S, d_out0, d_out1, d_lwe, count, halvings, batch)
-                    : pack_fused(h, gks, S, d_out0, d_out1, d_lwe, count, halvings, batch);
+    const PackSource src{d_lwe, nullptr, nullptr};
+    return composed ? pack_composed(h, gks, S, d_out0, d_out1, src, count, halvings, batch) : pack_fused(h, gks, S, d_out0, d_out1, src, count, halvings, batch);
+}
+
+extern "C" int fhe_rlwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, uint32_t count,
+                             int trace, int normalize, uint32_t batch) {
+    int rc = check_pack_engine(h, batch, "rlwe_pack"); if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_pack: null argument");
+    if ((rc = check_aligned({d_out0, d_out1, d_c0, d_c1}, "rlwe_pack"))) return rc;
+    PackShape S;
+    if ((rc = check_pack_shape(h, gks, count, trace, batch, "rlwe_pack", &S))) return rc;
+    const size_t out = (size_t)batch * h->L * h->n * 32, in = out * count;
+    if (overlaps(d_out0, out, d_out1, out)) return fail(FHE_ERR_INVALID_ARG, "rlwe_pack: the outputs must not overlap");
+    for (const void *o : {(const void *)d_out0, (const void *)d_out1})
+        if (overlaps(o, out, d_c0, in) || overlaps(o, out, d_c1, in)) return fail(FHE_ERR_INVALID_ARG, "rlwe_pack: an output overlaps an input");
+    const bool composed = pack_composed_env();
+    if ((rc = ensure_pack(h, S, count, batch, composed))) return rc;              // (no-op after fhe_lwe_pack_reserve: the scratch is fhe_lwe_pack's)
+    if ((rc = check_inputs(h, {d_c1}, batch * count))) return rc;
+    const uint32_t halvings = normalize ? (trace ? h->log_n : S.k) : 0;
+    const PackSource src{nullptr, d_c0, d_c1};
+    return composed ? pack_composed(h, gks, S, d_out0, d_out1, src, count, halvings, batch) : pack_fused(h, gks, S, d_out0, d_out1, src, count, halvings, batch);
 }

@@ -1,5 +1,5 @@
-// lwe_pack.hip.h -- the streaming kernels of the LWE -> RLWE ring packing (fhe_lwe_to_rlwe, fhe_lwe_pack; contract: include/fhe_hip.h), for
-// moduli below 2^64.  No transform, one pass over HBM each, launched by lwe_pack.hip only.  As in bootstrap.hip.h no kernel multiplies by a
+// lwe_pack.hip.h -- the streaming kernels of the LWE -> RLWE ring packing (fhe_lwe_to_rlwe, fhe_lwe_pack, fhe_rlwe_pack; contract:
+// include/fhe_hip.h), for moduli below 2^64.  No transform, one pass over HBM each, launched by lwe_pack.hip only.  As in bootstrap.hip.h no kernel multiplies by a
 // table entry: a residue below 2^64 is the low 8 bytes of its container in every width class (the upper 24 bytes are zero), so one instance
 // per limb-table type serves every field, and the one product of the algorithm -- by F^-1, F a power of two, q odd -- is log2 F exact halvings.
 // One 16-byte half container of every output per lane: the even halves carry the residue, the odd halves are zero and read nothing.
@@ -49,6 +49,48 @@ lwe_embed_merge_kernel(v2u64 *__restrict__ o0, v2u64 *__restrict__ o1, v2u64 *__
                 const uint32_t y = (x - m) & (n - 1);                            // (X^m O)[x] = O[x - m], negated where x < m
                 uint64_t r1 = pk_halve(pk_embed_c1(rowO, y, n, q), q, halvings);
                 uint64_t r0 = y ? 0 : pk_halve(__builtin_nontemporal_load(rowO + n), q, halvings);
+                if (x < m) { r1 = pk_neg(r1, q); r0 = pk_neg(r0, q); }
+                p0 = pk_add(e0, r0, q); p1 = pk_add(e1, r1, q);
+                q0 = pk_sub(e0, r0, q); q1 = pk_sub(e1, r1, q);
+            } else { p0 = e0; p1 = e1; }
+        }
+        const v2u64 a = {p0, 0ull}, b = {p1, 0ull};
+        __builtin_nontemporal_store(a, o0 + g);
+        __builtin_nontemporal_store(b, o1 + g);
+        if (PAIR) {
+            const v2u64 c = {q0, 0ull}, d = {q1, 0ull};
+            __builtin_nontemporal_store(c, d0 + g);
+            __builtin_nontemporal_store(d, d1 + g);
+        }
+    }
+}
+
+// The same two forms straight from RLWE pairs (fhe_rlwe_pack): in0, in1 are [entries or 2 entries][L][n] containers, and what is packed is
+// coefficient 0 of each pair.  Extraction at idx = 0 followed by the embedding is the identity on c1 and keeps c0[0] alone, so c1 is read in
+// place, ascending and not negated, and c0 contributes its container 0: the bits of lwe_embed_merge_kernel on the extracted samples, which are
+// never written.  The rest of c0 is not read.
+template <class LimbT, bool PAIR>
+__global__ void __launch_bounds__(256)
+rlwe_embed_merge_kernel(v2u64 *__restrict__ o0, v2u64 *__restrict__ o1, v2u64 *__restrict__ d0, v2u64 *__restrict__ d1, const v2u64 *__restrict__ in0,
+                        const v2u64 *__restrict__ in1, const LimbT *__restrict__ limbs, uint32_t half, uint32_t halvings, uint32_t L, uint32_t log_n,
+                        size_t halves /* entries L n 2 */) {
+    const uint32_t n = 1u << log_n, m = n >> 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < halves; g += stride) {
+        uint64_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
+        if (!(g & 1)) {
+            const size_t c = g >> 1, poly = c >> log_n, e = poly / L;            // container, polynomial e L + l, output entry
+            const uint32_t x = (uint32_t)(c & (n - 1)), l = (uint32_t)(poly - e * L);
+            const uint64_t q = limb_q64(limbs[l]);
+            const size_t se = PAIR ? (e / half) * 2 * half + e % half : e;      // input pair of E
+            const size_t atE = ((se * L + l) << log_n) * 2;                      // its container 0, in halves
+            const uint64_t e1 = pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in1 + atE + (size_t)x * 2)), q, halvings);
+            const uint64_t e0 = x ? 0 : pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in0 + atE)), q, halvings);
+            if (PAIR) {
+                const size_t atO = (((se + half) * L + l) << log_n) * 2;
+                const uint32_t y = (x - m) & (n - 1);                            // (X^m O)[x] = O[x - m], negated where x < m
+                uint64_t r1 = pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in1 + atO + (size_t)y * 2)), q, halvings);
+                uint64_t r0 = y ? 0 : pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in0 + atO)), q, halvings);
                 if (x < m) { r1 = pk_neg(r1, q); r0 = pk_neg(r0, q); }
                 p0 = pk_add(e0, r0, q); p1 = pk_add(e1, r1, q);
                 q0 = pk_sub(e0, r0, q); q1 = pk_sub(e1, r1, q);

@@ -512,8 +512,8 @@ public:
         device_free(d);
     }
 
-    // The way back from LWE samples to a ciphertext (fhe_lwe_pack; the last step of the declared FHEContext::bootstrap(Ciphertext&), which this
-    // does not build).  packing_key_gen: the log2(n) Galois key sets of 2^j + 1 in ONE engine call, noise scale t like every key of the context.
+    // The way back from LWE samples to a ciphertext (fhe_lwe_pack; the last step of FHEContext::bootstrap(Ciphertext&) below, which packs
+    // straight from the accumulators).  packing_key_gen: the log2(n) Galois key sets of 2^j + 1 in ONE engine call, noise scale t like every key of the context.
     void packing_key_gen(PackingKeys &pk, const SecretKey &sk, uint32_t decomp_bits = 16) {
         uint32_t log_n = 0; while ((1u << log_n) < params_.n) log_n++;
         std::vector<uint32_t> elts(log_n);
@@ -587,6 +587,61 @@ public:
             check(fhe_hip_memcpy_d2h(out_lwe.data(), d_out, out_lwe.size() * 8), "memcpy d2h");
         } catch (...) { device_free(d); throw; }
         device_free(d);
+    }
+
+    // FHEContext::bootstrap(Ciphertext&) (include/fhe.cuh:119, declared only): refresh `count` evenly spaced coefficients of a ciphertext and apply
+    // a table to them.  The reference declares bootstrap(Ciphertext&, const SecretKey&) with no keys: a refresh that reads the secret key is a
+    // decryption, so the evaluation keys made FROM it are the arguments instead (bootstrap_key_gen, packing_key_gen), as pack_lwes did for the last
+    // step.  Scaled (MSB) encoding, that of bootstrap_lwe: with Q_level the product of the primes of ct's level and Delta = floor(Q_level / (2p)),
+    // coefficient i n / count of ct has phase Delta m_i + Delta / 2 + e; the other coefficients are ignored.  test_vector is one top-level
+    // polynomial, tv[j] the value for a phase in slice j of the n slices of [0, Q / 2).  On buffers owned by the call, ct untouched until the end:
+    // fhe_rns_rescale_drop_last of both components down the level engines to the one-limb engine -> fhe_rlwe_sample_extract_strided ->
+    // fhe_lwe_keyswitch with q_out = q_lwe (2 <= q_lwe <= 2^48) -> fhe_lwe_prepare_accumulator -> fhe_blind_rotate at level 0 with batch = count
+    // -> fhe_rlwe_pack with the trace and the normalisation.  The result replaces ct: level 0, correction 1, coefficient i n / count of phase
+    // tv[phase~_i] plus noise and every other coefficient of phase 0 plus noise.  Keys: the packing keys carry noise t e like every key of the
+    // context, which the scaled encoding sees in full: a context that bootstraps sets the plaintext modulus to 2 before key generation, as a CKKS
+    // context does.  Every engine of the context has a stream of its own, so the call synchronises the device where the work passes from one
+    // engine to the next, as bootstrap_lwe does.
+    void bootstrap(Ciphertext &ct, const Polynomial &test_vector, const BootstrapKey &bk, const PackingKeys &pk, uint32_t count, uint64_t q_lwe) {
+        const uint32_t n_lwe = (uint32_t)bk.rows_c0.size(), n = params_.n, L = num_levels();
+        if (!n_lwe || bk.rows_c1.size() != n_lwe || !bk.lwe_ksk) throw std::runtime_error("FHEContext::bootstrap: the bootstrapping key is empty");
+        if (bk.made_for != params_.rns_ntt) throw std::runtime_error("FHEContext::bootstrap: the bootstrapping key was generated by another context");
+        if (pk.made_for != params_.rns_ntt || pk.sets.empty()) throw std::runtime_error("FHEContext::bootstrap: the packing keys were generated by another context");
+        if (ct.components.size() != 2) throw std::runtime_error("FHEContext::bootstrap: 2-component ciphertext expected (relinearize first)");
+        if (ct.level >= L) throw std::runtime_error("FHEContext::bootstrap: no such level");
+        if (!count || (count & (count - 1)) || count > n) throw std::runtime_error("FHEContext::bootstrap: count must be a power of two in [1, n]");
+        if (test_vector.num_limbs != L) throw std::runtime_error("FHEContext::bootstrap: a top-level test vector is needed");
+        const size_t poly = (size_t)L * n, acc = poly * count;                              // containers
+        auto containers = [](size_t bytes) { return (bytes + sizeof(uint256_t) - 1) / sizeof(uint256_t); };
+        const size_t low_c = (size_t)(L - ct.level) * n, ext_c = containers((size_t)count * (n + 1) * 8), ks_c = containers((size_t)count * (n_lwe + 1) * 8),
+                     sh_c = containers((size_t)n_lwe * count * 4);
+        std::unique_ptr<Polynomial> o0(new_polynomial()), o1(new_polynomial());
+        uint256_t *d = device_alloc(4 * acc + 4 * low_c + ext_c + ks_c + sh_c);
+        try {
+            uint256_t *a0 = d, *a1 = d + acc, *t0 = d + 2 * acc, *t1 = d + 3 * acc, *r0 = d + 4 * acc, *r1 = r0 + low_c, *u0 = r1 + low_c, *u1 = u0 + low_c,
+                      *d_ext = u1 + low_c, *d_ks = d_ext + ext_c, *d_sh = d_ks + ks_c;
+            const uint256_t *cur0 = ct.components[0]->coeffs, *cur1 = ct.components[1]->coeffs;
+            for (uint32_t level = ct.level; level + 1 < L; level++) {                       // [L - level][n] -> [L - level - 1][n]; ct itself is only read
+                fhe_rns_ntt_t *hl = engine(level).handle();
+                if (level > ct.level) device_synchronize();                                // the previous level's engine wrote cur0 / cur1
+                check(fhe_rns_rescale_drop_last(hl, r0, cur0, 1), "bootstrap: rescale");
+                check(fhe_rns_rescale_drop_last(hl, r1, cur1, 1), "bootstrap: rescale");
+                cur0 = r0; cur1 = r1; std::swap(r0, u0); std::swap(r1, u1);
+            }
+            fhe_rns_ntt_t *h1 = engine(L - 1).handle(), *h = params_.rns_ntt->handle();     // the one-limb engine (the context's own when L == 1)
+            device_synchronize();
+            check(fhe_rlwe_sample_extract_strided(h1, (uint64_t *)d_ext, cur0, cur1, count, 1), "bootstrap: sample extraction");
+            check(fhe_lwe_keyswitch(h1, bk.lwe_ksk, q_lwe, (uint64_t *)d_ks, (const uint64_t *)d_ext, count), "bootstrap: LWE key switch");
+            if (L > 1) device_synchronize();
+            check(fhe_lwe_prepare_accumulator(h, q_lwe, n_lwe, (const uint64_t *)d_ks, test_vector.coeffs, a0, a1, (uint32_t *)d_sh, count), "bootstrap: prepare");
+            check(fhe_blind_rotate(h, bk.rows_c0.data(), bk.rows_c1.data(), n_lwe, a0, a1, (const uint32_t *)d_sh, t0, t1, count), "bootstrap: blind rotation");
+            check(fhe_rlwe_pack(h, pk.sets.data(), o0->coeffs, o1->coeffs, a0, a1, count, 1, 1, 1), "bootstrap: packing");
+            device_synchronize();
+        } catch (...) { device_free(d); throw; }
+        device_free(d);
+        free_components(ct);
+        ct.components.push_back(o0.release()); ct.components.push_back(o1.release());
+        ct.level = 0; ct.correction = 1; ct.noise_budget = 0; ct.is_ntt_form = false;
     }
 
     void galoiskey_gen_fused(GaloisKeys &gal_keys, const SecretKey &sk) {                   // the default set of galoiskey_gen

@@ -561,6 +561,16 @@ int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uint32_t n_lwe
  * ONE launch for any n >= 8, no workspace.  FHE_ERR_INVALID_ARG with nothing launched: a null pointer; misaligned d_c0 / d_c1 (16 bytes) or
  * d_out (8 bytes); an output that overlaps an input; batch == 0; idx >= n. */
 int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t idx, uint32_t batch);
+/* The `count` evenly spaced coefficients i n / count, i < count, of `batch` RLWE pairs at once: the way INTO the LWE side of
+ * FHEContext::bootstrap(Ciphertext&).  d_c0, d_c1: [batch][L][n] containers; d_out: [batch][count][L][n + 1] uint64_t, row (b, i, l) exactly what
+ * fhe_rlwe_sample_extract(h, ., d_c0, d_c1, idx = i n / count, .) writes for polynomial (b, l): bit-identical to `count` single calls scattered
+ * into that layout, which is the d_lwe of fhe_lwe_pack and, on a one-limb engine, the [batch count][n + 1] d_in of fhe_lwe_keyswitch.
+ * count is a power of two, 1 <= count <= n.  ONE launch for any n >= 8, no workspace, nothing allocated: capturable.  Row i is row 0 rotated
+ * by i n / count, so every coefficient of c1 is loaded once and stored `count` times (from HBM once per ciphertext, not once per row).
+ * FHE_ERR_INVALID_ARG with nothing launched: a null pointer; misaligned d_c0 / d_c1 (16 bytes) or d_out (8 bytes); an output that overlaps an
+ * input; batch == 0; n < 8; a count that is zero, not a power of two, or above n; batch count overflowing uint32_t or batch count L above
+ * 2^31 - 1 (the range of fhe_lwe_pack). */
+int fhe_rlwe_sample_extract_strided(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t count, uint32_t batch);
 
 /* ---- LWE key switch back to the small key: chainable bootstrapping -------------------------------------------------------------------
  * The last step of FHEContext::bootstrap (include/fhe.cuh:119, declared only; README.md:146-159): the sample that fhe_rlwe_sample_extract
@@ -648,7 +658,8 @@ int fhe_lwe_keyswitch(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t q_out
  * Workspace.  The call's scratch is an allocation of the engine's own, which fhe_rns_ntt_workspace_bytes counts.  With S = L n 32 bytes:
  *     3 batch count S                      count >= 2  (three regions, each both components of batch count / 2 ciphertexts)
  *     2 batch S                            count == 1 with the trace;  nothing for count == 1 without
- *     5 batch count S + 2 batch count      count >= 2 under FHE_HIP_NO_FUSED_PACK=1
+ *     5 batch count S + 2 batch count      count >= 2 under FHE_HIP_NO_FUSED_PACK=1; under that switch every shape also holds, from the next
+ *                                          16-byte boundary, batch count L (n + 1) 8 bytes of sample scratch for fhe_rlwe_pack
  *   beside what fhe_ct_apply_galois needs at the largest level batch, batch count / 2 (batch for count == 1).  fhe_lwe_pack_reserve sizes both (for
  *   the path the environment selects when it is called); after it a call allocates nothing and can be captured into a hipGraph. */
 /* host only: elts[j-1] = 2^j + 1, j = 1 .. log2 n.  n a power of two, 8 <= n <= 2^30. */
@@ -665,6 +676,18 @@ int fhe_lwe_to_rlwe(fhe_rns_ntt_t *h, void *d_c0, void *d_c1, const uint64_t *d_
 int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count, int trace,
                  int normalize, uint32_t batch);
 int fhe_lwe_pack_reserve(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch);
+/* The same packing straight from RLWE pairs: the way OUT of the LWE side of FHEContext::bootstrap(Ciphertext&).  d_c0, d_c1: [batch][count][L][n]
+ * containers, batch count accumulators in the order fhe_blind_rotate leaves them, whose coefficient 0 carries the refreshed value.  The
+ * result is fhe_lwe_pack applied to fhe_rlwe_sample_extract(idx = 0) of every input pair, the same bits on every path.  Extraction at 0
+ * followed by the embedding is the identity on c1 and keeps c0[0] alone, so the first merge level (for count == 1 the embedding) reads c1 and
+ * container 0 of c0 in place: the batch count L (n + 1) 8 bytes of samples are neither written nor read back, and their buffer never
+ * exists.  Nothing else of c0 is read.  Every later level, the trace, the normalisation and the scratch are fhe_lwe_pack's: the SAME
+ * fhe_lwe_pack_reserve(h, gks, count, trace, batch) serves both entries, after which a call allocates nothing and can be captured.
+ * FHE_HIP_NO_FUSED_PACK=1, read per call, runs fhe_rlwe_sample_extract(idx = 0) into the sample scratch of the table above and then the
+ * composed path of fhe_lwe_pack.  FHE_ERR_INVALID_ARG as fhe_lwe_pack (every container pointer 16-byte aligned), and for an output that
+ * overlaps an input. */
+int fhe_rlwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, uint32_t count,
+                  int trace, int normalize, uint32_t batch);
 
 /* ---- batch encoder: slot values <-> plaintext polynomials on the device --------------------------------------------------------------
  * FHEContext::encode / decode and BatchEncoder (include/fhe.cuh:89-90, 150-157).  With psi = fhe_find_psi(n, t) and e(i) the exponent of slot i:
