@@ -5,25 +5,16 @@
 // consumes: fhe_rgsw_keys_generate, keygen.hip.)
 #include "engine.h"
 
-#include <type_traits>
-
 #include "bootstrap.hip.h"
-
-static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 
 extern "C" int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uint32_t n_lwe, const uint64_t *d_lwe, const void *d_tv, void *d_acc0,
                                            void *d_acc1, uint32_t *d_shifts, uint32_t batch) {
-    int rc = check_call(h, batch, "lwe_prepare_accumulator"); if (rc) return rc;
-    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "lwe_prepare_accumulator: every modulus must be below 2^64");
+    int rc = check_word_call(h, batch, "lwe_prepare_accumulator", true); if (rc) return rc;
     if (!d_lwe || !d_tv || !d_acc0 || !d_acc1 || !d_shifts) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: null argument");
     if ((rc = check_aligned({d_tv, d_acc0, d_acc1}, "lwe_prepare_accumulator"))) return rc;
     if (((uintptr_t)d_lwe & 7) || ((uintptr_t)d_shifts & 3)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: d_lwe must be 8-byte, d_shifts 4-byte aligned");
     if (!n_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: n_lwe must be at least 1");
     if (q_lwe < 2 || q_lwe > (1ull << 48)) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: q_lwe must be in [2, 2^48]");
-    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: n must be at least 8");
     const size_t S = (size_t)h->L * h->n * 32, acc = S * batch, sh = (size_t)n_lwe * batch * 4, lw = ((size_t)n_lwe + 1) * batch * 8;
     if (overlaps(d_acc0, acc, d_acc1, acc) || overlaps(d_acc0, acc, d_shifts, sh) || overlaps(d_acc1, acc, d_shifts, sh))
         return fail(FHE_ERR_INVALID_ARG, "lwe_prepare_accumulator: the outputs must not overlap");
@@ -33,48 +24,36 @@ extern "C" int fhe_lwe_prepare_accumulator(fhe_rns_ntt_t *h, uint64_t q_lwe, uin
     if ((rc = check_inputs(h, {d_tv}, 1))) return rc;
     using V = fhe_dev::v2u64;
     const size_t halves = (size_t)batch * h->L * h->n * 2;
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        hipLaunchKernelGGL((fhe_dev::lwe_prepare_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)d_acc0, (V *)d_acc1, d_shifts, d_lwe, (const V *)d_tv, limbs,
+    return with_limbs(h, [&](auto *limbs) {
+        hipLaunchKernelGGL((fhe_dev::lwe_prepare_kernel<limb_of<decltype(limbs)>>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)d_acc0, (V *)d_acc1, d_shifts, d_lwe, (const V *)d_tv, limbs,
                            q_lwe, n_lwe, batch, h->L, h->log_n, halves);
         return post_launch(h->stream, "lwe_prepare_kernel");
-    };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+    });
 }
 
 extern "C" int fhe_rlwe_sample_extract(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t idx, uint32_t batch) {
-    int rc = check_call(h, batch, "rlwe_sample_extract"); if (rc) return rc;
-    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "rlwe_sample_extract: every modulus must be below 2^64");
+    int rc = check_word_call(h, batch, "rlwe_sample_extract", true); if (rc) return rc;
     if (!d_out || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: null argument");
     if ((rc = check_aligned({d_c0, d_c1}, "rlwe_sample_extract"))) return rc;
     if ((uintptr_t)d_out & 7) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: d_out must be 8-byte aligned");
-    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: n must be at least 8");
     if (idx >= h->n) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: idx must be below n");
     const size_t polys = (size_t)batch * h->L, in = polys * h->n * 32, out = polys * ((size_t)h->n + 1) * 8;
     if (overlaps(d_out, out, d_c0, in) || overlaps(d_out, out, d_c1, in)) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract: the output overlaps an input");
     if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
     using V = fhe_dev::v2u64;
     const unsigned bx = (unsigned)std::min<size_t>(((size_t)h->n + 1 + 255) / 256, 64), by = (unsigned)std::min<size_t>(polys, 65535);
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        hipLaunchKernelGGL((fhe_dev::sample_extract_kernel<LimbT>), dim3(bx, by), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, idx, h->L, h->log_n, polys);
+    return with_limbs(h, [&](auto *limbs) {
+        hipLaunchKernelGGL((fhe_dev::sample_extract_kernel<limb_of<decltype(limbs)>>), dim3(bx, by), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, idx, h->L, h->log_n, polys);
         return post_launch(h->stream, "sample_extract_kernel");
-    };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+    });
 }
 
 extern "C" int fhe_rlwe_sample_extract_strided(fhe_rns_ntt_t *h, uint64_t *d_out, const void *d_c0, const void *d_c1, uint32_t count, uint32_t batch) {
-    int rc = check_call(h, batch, "rlwe_sample_extract_strided"); if (rc) return rc;
-    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, "rlwe_sample_extract_strided: every modulus must be below 2^64");
+    int rc = check_word_call(h, batch, "rlwe_sample_extract_strided", true); if (rc) return rc;
     if (!d_out || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: null argument");
     if ((rc = check_aligned({d_c0, d_c1}, "rlwe_sample_extract_strided"))) return rc;
     if ((uintptr_t)d_out & 7) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: d_out must be 8-byte aligned");
-    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: n must be at least 8");
-    if (!count || (count & (count - 1)) || count > h->n) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: count must be a power of two in [1, n]");
-    if ((uint64_t)batch * count > 0xffffffffull || (uint64_t)batch * count * h->L > 0x7fffffffull)                   // what fhe_lwe_pack accepts
-        return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: batch * count * num_primes too large");
+    if ((rc = check_count(h, count, batch, "rlwe_sample_extract_strided"))) return rc;   // what fhe_lwe_pack accepts
     const size_t polys = (size_t)batch * h->L, in = polys * h->n * 32, out = polys * count * ((size_t)h->n + 1) * 8;
     if (overlaps(d_out, out, d_c0, in) || overlaps(d_out, out, d_c1, in)) return fail(FHE_ERR_INVALID_ARG, "rlwe_sample_extract_strided: the output overlaps an input");
     if ((rc = check_inputs(h, {d_c0, d_c1}, batch))) return rc;
@@ -86,12 +65,9 @@ extern "C" int fhe_rlwe_sample_extract_strided(fhe_rns_ntt_t *h, uint64_t *d_out
     const size_t want = (4096 + (size_t)bx * by - 1) / ((size_t)bx * by);
     const uint32_t runs = (uint32_t)std::max<size_t>(1, std::min<size_t>(want, std::max<uint32_t>(1, count / 8)));
     const uint32_t rows_per_block = (count + runs - 1) / runs, bz = (count + rows_per_block - 1) / rows_per_block;
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        hipLaunchKernelGGL((fhe_dev::sample_extract_strided_kernel<LimbT>), dim3(bx, by, bz), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, log_count,
+    return with_limbs(h, [&](auto *limbs) {
+        hipLaunchKernelGGL((fhe_dev::sample_extract_strided_kernel<limb_of<decltype(limbs)>>), dim3(bx, by, bz), dim3(256), 0, h->stream, d_out, (const V *)d_c0, (const V *)d_c1, limbs, log_count,
                            rows_per_block, h->L, h->log_n, polys);
         return post_launch(h->stream, "sample_extract_strided_kernel");
-    };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+    });
 }

@@ -95,10 +95,6 @@ static int check_ckks(const fhe_rns_ntt *h, const fhe_ckks_encoder *enc, double 
     if (!std::isfinite(scale) || !(scale > 0)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": scale must be finite and positive");
     return FHE_OK;
 }
-static bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 // fn(std::integral_constant<int, log_n>) for the encoder's size
 template <class Fn>
 static int with_ckks_size(const fhe_rns_ntt *h, Fn &&fn) {
@@ -119,8 +115,8 @@ extern "C" int fhe_ckks_encode(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, 
     if ((uintptr_t)d_slots & 7) return fail(FHE_ERR_INVALID_ARG, "ckks_encode: d_slots must be 8-byte aligned");
     if ((uintptr_t)d_coeff_bits & 3) return fail(FHE_ERR_INVALID_ARG, "ckks_encode: d_coeff_bits must be 4-byte aligned");
     const size_t count = (size_t)batch * h->n, out_bytes = count * h->L * 32;
-    if (overlap(d_out, out_bytes, d_slots, count * 8)) return fail(FHE_ERR_INVALID_ARG, "ckks_encode: the output must not alias the input");
-    if (d_coeff_bits && (overlap(d_coeff_bits, (size_t)batch * 4, d_slots, count * 8) || overlap(d_coeff_bits, (size_t)batch * 4, d_out, out_bytes)))
+    if (overlaps(d_out, out_bytes, d_slots, count * 8)) return fail(FHE_ERR_INVALID_ARG, "ckks_encode: the output must not alias the input");
+    if (d_coeff_bits && (overlaps(d_coeff_bits, (size_t)batch * 4, d_slots, count * 8) || overlaps(d_coeff_bits, (size_t)batch * 4, d_out, out_bytes)))
         return fail(FHE_ERR_INVALID_ARG, "ckks_encode: d_coeff_bits must not alias the slots or the output");
     const double scale_over_h = scale / (double)(h->n / 2);               // exact: h is a power of two
     return with_ckks_size(h, [&](auto logn) {
@@ -140,7 +136,7 @@ static int ckks_decode(fhe_rns_ntt *h, const fhe_ckks_encoder *enc, double *d_sl
     if (containers) { if ((rc = check_aligned({d_src}, what))) return rc; }
     else if ((uintptr_t)d_src & 7) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": d_m must be 8-byte aligned");
     const size_t count = (size_t)batch * h->n;
-    if (overlap(d_slots, count * 8, d_src, containers ? count * h->L * 32 : count * 8)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the output must not alias the input");
+    if (overlaps(d_slots, count * 8, d_src, containers ? count * h->L * 32 : count * 8)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the output must not alias the input");
     const double inv_scale = 1.0 / scale;
     return with_ckks_size(h, [&](auto logn) {
         constexpr int LOGN = decltype(logn)::value;

@@ -1,8 +1,8 @@
 // decrypt.hip -- secret-key decryption (fhe_ct_decrypt*; the keys: keys.hip).
 // Fused path (plan_fused_decrypt; kernels: decrypt.hip.h): the key is kept transformed, with its pointwise square, packed like one key row each;
-// a call is two launches, ntt_decrypt_kernel into the compact decryption workspace d_dec and decrypt_crt_kernel from it.  Composed path
+// a call is two launches, ntt_decrypt_kernel into the compact decryption workspace WS_DEC and decrypt_crt_kernel from it.  Composed path
 // (full-width class, sizes outside the LDS-resident range, FHE_HIP_NO_FUSED_DECRYPT=1): fhe_rns_ntt_multiply_bcast against s (and against the
-// s^2 built at import), fhe_rns_poly_add into container scratch in d_dec, then the CRT kernel on containers.
+// s^2 built at import), fhe_rns_poly_add into container scratch in WS_DEC, then the CRT kernel on containers.
 #include "engine.h"
 
 #include "ntt_word.hip.h"
@@ -14,15 +14,15 @@ static int decrypt_q_fits(fhe_rns_ntt *h, const char *what) {
     if (h->crt_state < 0) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": the product of the moduli must be below 2^255 (the noise bits need the integer itself, which has to fit a 256-bit container)");
     return FHE_OK;
 }
-// everything a call with `num_components` components and `batch` ciphertexts needs: the CRT tables and d_dec (compact residues on the fused
+// everything a call with `num_components` components and `batch` ciphertexts needs: the CRT tables and WS_DEC (compact residues on the fused
 // path; containers for c1 s and, with c2, c2 s^2 on the composed path, whose products also need the multiply workspaces)
 static int ensure_decrypt(fhe_rns_ntt *h, uint32_t num_components, uint32_t batch) {
     int rc;
     if (h->width != FHE_WIDTH_256 && (rc = ensure_from_rns_word(h))) return rc;
     const size_t polys = (size_t)batch * h->L;
-    if (plan_fused_decrypt(h)) return grow_ws(h, &h->d_dec, &h->dec_bytes, polys * h->n * residue_bytes(h));
+    if (plan_fused_decrypt(h)) return grow_ws(h, h->ws[WS_DEC], polys * h->n * residue_bytes(h));
     if ((rc = ensure_need(h, need_multiply(h, batch) | need_multiply(h, 1) | need_transform(h, polys)))) return rc;
-    return grow_ws(h, &h->d_dec, &h->dec_bytes, (num_components - 1) * polys * h->n * 32);
+    return grow_ws(h, h->ws[WS_DEC], (num_components - 1) * polys * h->n * 32);
 }
 extern "C" int fhe_ct_decrypt_reserve(fhe_rns_ntt_t *h, uint64_t t, uint32_t num_components, uint32_t batch) {
     int rc = check_call(h, batch, "ct_decrypt_reserve"); if (rc) return rc;
@@ -56,13 +56,13 @@ extern "C" int fhe_ct_decrypt(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint
     fhe_host::ModT M; fhe_host::modt_init(M, t);
     const size_t S = (size_t)h->L * h->n * 32, count = (size_t)batch * h->n;
     const bool fused = sk->d_packed && plan_fused_decrypt(h);
-    const void *res = h->d_dec;
+    const void *res = h->ws[WS_DEC].p;
     if (fused) {
         fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_DECRYPT, {}, batch * h->L);
-        A.r0 = h->d_dec; A.a0 = c[0]; A.a1 = c[1]; A.c2 = c[2]; A.kb = sk->d_packed; A.ka = (const char *)sk->d_packed + packed_row_bytes(h); A.out_compact = true;
+        A.r0 = h->ws[WS_DEC].p; A.a0 = c[0]; A.a1 = c[1]; A.c2 = c[2]; A.kb = sk->d_packed; A.ka = (const char *)sk->d_packed + packed_row_bytes(h); A.out_compact = true;
         if ((rc = lds_launch(h, A, "ntt_decrypt_kernel"))) return rc;
     } else {
-        char *p0 = (char *)h->d_dec, *p1 = p0 + (size_t)batch * S;
+        char *p0 = (char *)h->ws[WS_DEC].p, *p1 = p0 + (size_t)batch * S;
         if ((rc = fhe_rns_ntt_multiply_bcast(h, p0, c[1], sk->d_s, batch))) return rc;
         if (c[2]) {
             if ((rc = fhe_rns_ntt_multiply_bcast(h, p1, c[2], (const char *)sk->d_s + S, batch))) return rc;

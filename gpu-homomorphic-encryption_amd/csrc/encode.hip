@@ -17,7 +17,7 @@ struct fhe_batch_encoder {
     void *d_table = nullptr;                        // uint32_t[n]: position of the NTT domain -> slot index
     void *d_red = nullptr;                          // ModT[L]: reduction modulo q_l where t > q_l, t == 0 elsewhere
     bool reduces_limb0 = false;                     // t > q_0: limb 0 of a plaintext is not m (fhe_slots_decode_poly refuses)
-    void *d_scratch = nullptr; size_t scratch_bytes = 0;   // composed path: [batch][1][n] containers
+    Workspace scratch;                              // composed path: [batch][1][n] containers
 };
 
 // table[pos] = the slot i whose exponent e(i) is 2 bitrev(pos) + 1, the point position pos of the NTT domain holds
@@ -44,7 +44,7 @@ extern "C" int fhe_batch_encoder_slot_table(uint32_t n, int slot_order, uint32_t
 
 extern "C" int fhe_batch_encoder_destroy(fhe_batch_encoder_t *enc) {
     if (enc) {
-        if (enc->d_scratch) (void)hipFree(enc->d_scratch);
+        if (enc->scratch.p) (void)hipFree(enc->scratch.p);
         destroy_impl(enc->te);
         delete enc;
     }
@@ -76,7 +76,7 @@ extern "C" int fhe_batch_encoder_create(fhe_rns_ntt_t *h, fhe_batch_encoder_t **
 }
 extern "C" int fhe_batch_encoder_scratch_bytes(const fhe_batch_encoder_t *enc, uint64_t *bytes) {
     if (!enc || !bytes) return fail(FHE_ERR_INVALID_ARG, "batch_encoder_scratch_bytes: null argument");
-    *bytes = (uint64_t)enc->scratch_bytes + enc->te->ws_bytes + enc->te->ws2_bytes + enc->te->ws3_bytes;
+    *bytes = (uint64_t)enc->scratch.bytes + enc->te->ws[WS1].bytes + enc->te->ws[WS2].bytes + enc->te->ws[WS3].bytes;
     return FHE_OK;
 }
 
@@ -91,17 +91,13 @@ static int ensure_slots(fhe_rns_ntt *h, fhe_batch_encoder *enc, uint32_t batch) 
     enc->te->stream = h->stream;
     if (plan_fused_slots(enc->te)) return FHE_OK;
     int rc = ensure_need(enc->te, need_transform(enc->te, batch)); if (rc) return rc;
-    return grow_ws(enc->te, &enc->d_scratch, &enc->scratch_bytes, (size_t)batch * h->n * 32);
+    return grow_ws(enc->te, enc->scratch, (size_t)batch * h->n * 32);
 }
 extern "C" int fhe_batch_encoder_reserve(fhe_rns_ntt_t *h, fhe_batch_encoder_t *enc, uint32_t batch) {
     int rc = check_encoder(h, enc, batch, "batch_encoder_reserve"); if (rc) return rc;
     return ensure_slots(h, enc, batch);
 }
 
-static bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 
 extern "C" int fhe_slots_encode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc_c, void *d_out, const uint64_t *d_values, uint32_t batch) {
     fhe_batch_encoder *enc = const_cast<fhe_batch_encoder *>(enc_c);      // the scratch of the composed path is the encoder's
@@ -110,7 +106,7 @@ extern "C" int fhe_slots_encode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc
     if ((rc = check_aligned({d_out}, "slots_encode"))) return rc;
     if ((uintptr_t)d_values & 7) return fail(FHE_ERR_INVALID_ARG, "slots_encode: d_values must be 8-byte aligned");
     const size_t count = (size_t)batch * h->n;
-    if (overlap(d_out, count * h->L * 32, d_values, count * 8)) return fail(FHE_ERR_INVALID_ARG, "slots_encode: the output must not alias the input");
+    if (overlaps(d_out, count * h->L * 32, d_values, count * 8)) return fail(FHE_ERR_INVALID_ARG, "slots_encode: the output must not alias the input");
     if ((rc = ensure_slots(h, enc, batch))) return rc;                   // (no-op after fhe_batch_encoder_reserve)
     fhe_rns_ntt *te = enc->te;
     if (plan_fused_slots(te)) {
@@ -118,11 +114,11 @@ extern "C" int fhe_slots_encode(fhe_rns_ntt_t *h, const fhe_batch_encoder_t *enc
         A.r0 = d_out; A.a0 = d_values; A.kb = enc->d_table; A.ka = enc->d_red; A.L = h->L; A.in_compact = true;
         return lds_launch(te, A, "ntt_slots_encode_kernel");
     }
-    hipLaunchKernelGGL(fhe_dev::slots_gather_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)enc->d_scratch, d_values,
+    hipLaunchKernelGGL(fhe_dev::slots_gather_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)enc->scratch.p, d_values,
                        (const uint32_t *)enc->d_table, h->log_n, count);
     if ((rc = post_launch(h->stream, "slots_gather_kernel"))) return rc;
-    if ((rc = do_inverse(te, enc->d_scratch, batch))) return rc;
-    hipLaunchKernelGGL(fhe_dev::slots_spread_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)d_out, (const fhe_dev::v2u64 *)enc->d_scratch,
+    if ((rc = do_inverse(te, enc->scratch.p, batch))) return rc;
+    hipLaunchKernelGGL(fhe_dev::slots_spread_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)d_out, (const fhe_dev::v2u64 *)enc->scratch.p,
                        (const fhe_host::ModT *)enc->d_red, h->L, h->log_n, count);
     return post_launch(h->stream, "slots_spread_kernel");
 }
@@ -136,8 +132,8 @@ static int slots_decode(fhe_rns_ntt *h, fhe_batch_encoder *enc, uint64_t *d_valu
     const size_t count = (size_t)batch * h->n;
     if (containers) {
         if (enc->reduces_limb0) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": t exceeds the first modulus, so limb 0 holds m mod q_0 and not m");
-        if (overlap(d_values, count * 8, d_src, count * h->L * 32)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the output must not alias the plaintexts");
-    } else if ((const void *)d_values != d_src && overlap(d_values, count * 8, d_src, count * 8))
+        if (overlaps(d_values, count * 8, d_src, count * h->L * 32)) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the output must not alias the plaintexts");
+    } else if ((const void *)d_values != d_src && overlaps(d_values, count * 8, d_src, count * 8))
         return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": the output must be d_m itself (in place) or not overlap it");
     if ((rc = ensure_slots(h, enc, batch))) return rc;
     fhe_rns_ntt *te = enc->te;
@@ -146,11 +142,11 @@ static int slots_decode(fhe_rns_ntt *h, fhe_batch_encoder *enc, uint64_t *d_valu
         A.r0 = d_values; A.a0 = d_src; A.kb = enc->d_table; A.L = h->L; A.in_compact = !containers; A.out_compact = true;
         return lds_launch(te, A, "ntt_slots_decode_kernel");
     }
-    hipLaunchKernelGGL(fhe_dev::slots_lift_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)enc->d_scratch, d_src, containers ? 1u : 0u, h->L,
+    hipLaunchKernelGGL(fhe_dev::slots_lift_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::v2u64 *)enc->scratch.p, d_src, containers ? 1u : 0u, h->L,
                        h->log_n, count);
     if ((rc = post_launch(h->stream, "slots_lift_kernel"))) return rc;
-    if ((rc = do_forward(te, enc->d_scratch, batch))) return rc;
-    hipLaunchKernelGGL(fhe_dev::slots_scatter_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, d_values, (const fhe_dev::v2u64 *)enc->d_scratch,
+    if ((rc = do_forward(te, enc->scratch.p, batch))) return rc;
+    hipLaunchKernelGGL(fhe_dev::slots_scatter_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, d_values, (const fhe_dev::v2u64 *)enc->scratch.p,
                        (const uint32_t *)enc->d_table, h->log_n, count);
     return post_launch(h->stream, "slots_scatter_kernel");
 }

@@ -1,7 +1,7 @@
 // encrypt.hip -- public-key encryption (fhe_ct_encrypt*; the keys: keys.hip).
 // Fused path (plan_fused_encrypt; kernel: encrypt.hip.h): the key is kept transformed and packed like one key row, a call is one launch that
 // draws u, e0, e1 in registers.  Composed path (full-width class, sizes outside the LDS-resident range, N = 2^15, sigma > 85,
-// FHE_HIP_NO_FUSED_ENCRYPT=1): u by fhe_rns_sample_ternary into d_enc, two fhe_rns_ntt_multiply_bcast against the key as given, then
+// FHE_HIP_NO_FUSED_ENCRYPT=1): u by fhe_rns_sample_ternary into WS_ENC, two fhe_rns_ntt_multiply_bcast against the key as given, then
 // encrypt_add_kernel below, which draws e0, e1 and adds t e0 + m and t e1 to the two products.
 #include "engine.h"
 
@@ -41,7 +41,7 @@ static bool encrypt_fused(const fhe_rns_ntt *h, const fhe_public_key *pk) {
 static int ensure_encrypt_composed(fhe_rns_ntt *h, uint32_t batch) {
     int rc = ensure_need(h, need_multiply(h, batch) | need_transform(h, (size_t)batch * h->L)); if (rc) return rc;
     if ((rc = ensure_crt(h))) return rc;
-    return grow_ws(h, &h->d_enc, &h->enc_bytes, (size_t)batch * h->L * h->n * 32);
+    return grow_ws(h, h->ws[WS_ENC], (size_t)batch * h->L * h->n * 32);
 }
 extern "C" int fhe_ct_encrypt_reserve(fhe_rns_ntt_t *h, double sigma, uint32_t batch) {
     int rc = check_call(h, batch, "ct_encrypt_reserve"); if (rc) return rc;
@@ -71,9 +71,9 @@ extern "C" int fhe_ct_encrypt(fhe_rns_ntt_t *h, const fhe_public_key_t *pk, uint
     }
     if ((rc = ensure_encrypt_composed(h, batch))) return rc;                   // (no-op after fhe_ct_encrypt_reserve)
     const size_t S = (size_t)h->L * h->n * 32;
-    if ((rc = fhe_rns_sample_ternary(h, h->d_enc, 0.5, seeds[0], batch))) return rc;
-    if ((rc = fhe_rns_ntt_multiply_bcast(h, d_out0, h->d_enc, pk->d_pk, batch))) return rc;
-    if ((rc = fhe_rns_ntt_multiply_bcast(h, d_out1, h->d_enc, (const char *)pk->d_pk + S, batch))) return rc;
+    if ((rc = fhe_rns_sample_ternary(h, h->ws[WS_ENC].p, 0.5, seeds[0], batch))) return rc;
+    if ((rc = fhe_rns_ntt_multiply_bcast(h, d_out0, h->ws[WS_ENC].p, pk->d_pk, batch))) return rc;
+    if ((rc = fhe_rns_ntt_multiply_bcast(h, d_out1, h->ws[WS_ENC].p, (const char *)pk->d_pk + S, batch))) return rc;
     const size_t count = (size_t)batch * h->n;
     hipLaunchKernelGGL(fhe_dev::encrypt_add_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)d_out0, (fhe_dev::u256 *)d_out1,
                        (const fhe_dev::u256 *)d_m, (const fhe_dev::CrtLimb *)h->d_crt, h->L, h->log_n, seeds[1], seeds[2], t, (const uint64_t *)h->d_cdt, h->cdt_len, count);

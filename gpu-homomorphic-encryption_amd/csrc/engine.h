@@ -1,6 +1,6 @@
 // engine.h -- what the host sources of the C ABI (include/fhe_hip.h) share: the engine and key-set structs, error plumbing, the
-// width-class -> field-type dispatch, workspaces, and the few entry points one subsystem offers the others.  Internal: nothing
-// declared here is exported from the library.  Which source owns what:
+// width-class -> field-type and limb-table dispatch, the shared argument checks, the workspace table, and the few entry points one subsystem
+// offers the others.  Internal: nothing declared here is exported from the library.  Which source owns what:
 //   core.hip        last error, device / memory entry points, host number theory, timers
 //   literal.hip     the reference's single-modulus kernels as written (ntt256_literal.hip.h)
 //   sampling.hip    samplers, modulus switch, negacyclic fold (sampling.hip.h)
@@ -25,6 +25,9 @@
 //                   (lwe_pack.hip.h)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
+// What they share is written once, here: overlaps (the byte-range test), with_word_field / with_limbs (width class -> field type / typed limb
+// table), check_word_call and check_count (the engine and (count, batch) rules of the entry points around the blind rotation), and the
+// workspace table (WsId, Workspace, grow_ws).
 #pragma once
 #include "../../include/fhe_hip.h"
 
@@ -37,6 +40,7 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -69,6 +73,12 @@ inline int check_aligned(std::initializer_list<const void *> ptrs, const char *w
     return FHE_OK;
 }
 
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte: the range test of the entry points that take one
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
 inline fhe_dev::u256 to_dev(const uint64_t q[4]) { fhe_dev::u256 r; std::memcpy(r.l, q, 32); return r; }
 
 inline unsigned ew_grid(size_t items) {
@@ -90,6 +100,27 @@ struct EngineEnv {
     int ct_form_force = 0;
 };
 
+// Library-owned workspaces, per engine, grown on demand by grow_ws (never while the engine's stream is capturing) and freed with the engine.
+// This table is the one place that names them: destroy_impl and fhe_rns_ntt_workspace_bytes loop over it.
+enum WsId {
+    WS1,        // general paths (the reference mallocs/frees per multiply, src/ntt.cu:51-74) and the transformed b-side of the two-launch tensor product
+    WS2,        // c0, c1, c2 of the fused multiply + relinearise (compact or containers) and the compact accumulators of a blind-rotation loop;
+                // separate from WS1, which the general paths use
+    WS3,        // compact polynomials between the two launches of a two-pass transform (sub_top != 0: N beyond the LDS range)
+    WS_HOIST,   // hoisted rotations: the transformed digit polynomials of the c1 of the last fhe_ct_hoist; no other entry point touches it
+    WS_LIN,     // hoisted linear transform.  Fused path: c0^ (and c1^) of the call in the hoist layout; composed path: the two components of
+                // one weighted rotation before they are added to the outputs
+    WS_ENC,     // fhe_ct_encrypt, composed path: u of the call as containers
+    WS_DEC,     // fhe_ct_decrypt.  Fused path: the residues of c0 + c1 s + c2 s^2 as compact polynomials between the two launches; composed
+                // path: c1 s (and c2 s^2) as containers
+    WS_PACK,    // fhe_lwe_pack.  Fused path: three regions that rotate as (P, G, free) over the merge levels; composed path: the embedded
+                // ciphertexts and the operands of one level as containers
+    WS_COUNT
+};
+// whether fhe_rns_ntt_workspace_bytes counts it: all but the hoist buffer, which fhe_rns_ntt_hoist_bytes reports on its own
+constexpr bool ws_in_workspace_bytes(int id) { return id != WS_HOIST; }
+struct Workspace { void *p = nullptr; size_t bytes = 0; };   // one grow-on-demand device allocation (the encoder objects' scratch too)
+
 struct fhe_rns_ntt {
     int device = 0;
     uint32_t n = 0, log_n = 0, L = 0;
@@ -106,23 +137,8 @@ struct fhe_rns_ntt {
     int wide_nl = 0;                    // FHE_WIDTH_256: 64-bit limbs per residue in those kernels (2: q < 2^127, 4: q < 2^255)
     bool wide_lazy = false;             // FHE_WIDTH_256: every modulus below 2^(64 wide_nl - 6): the lazy tile kernels (unless FHE_HIP_NO_WIDE_LAZY)
     std::vector<void *> d_tables;
-    void *d_ws = nullptr; size_t ws_bytes = 0;
-    void *d_ws2 = nullptr; size_t ws2_bytes = 0;   // c2 of the fused multiply + relinearise (compact or containers); separate from d_ws, which the general paths use
-    void *d_ws3 = nullptr; size_t ws3_bytes = 0;   // compact polynomials between the two launches of a two-pass transform (sub_top != 0)
-    // Hoisted rotations: the transformed digit polynomials of the c1 of the last fhe_ct_hoist, a fourth allocation that no other entry point touches
-    void *d_hoist = nullptr; size_t hoist_bytes = 0;
-    struct { bool valid = false, fused = false; uint32_t w = 0, K = 0, batch = 0; } hoist;   // what d_hoist holds: digit width, digits per limb, ciphertexts
-    // Hoisted linear transform: a fifth allocation.  Fused path: c0^ (and c1^) of the call in the hoist layout; composed path: the two components
-    // of one weighted rotation before they are added to the outputs
-    void *d_lin = nullptr; size_t lin_bytes = 0;
-    // fhe_ct_encrypt, composed path: u of the call as containers, a sixth allocation
-    void *d_enc = nullptr; size_t enc_bytes = 0;
-    // fhe_ct_decrypt, a seventh allocation.  Fused path: the residues of c0 + c1 s + c2 s^2 as compact polynomials between the two launches;
-    // composed path: c1 s (and c2 s^2) as containers
-    void *d_dec = nullptr; size_t dec_bytes = 0;
-    // fhe_lwe_pack, an eighth allocation.  Fused path: three regions that rotate as (P, G, free) over the merge levels; composed path: the
-    // embedded ciphertexts and the operands of one level as containers
-    void *d_pack = nullptr; size_t pack_bytes = 0;
+    Workspace ws[WS_COUNT];             // the library-owned workspaces (the table above)
+    struct { bool valid = false, fused = false; uint32_t w = 0, K = 0, batch = 0; } hoist;   // what WS_HOIST holds: digit width, digits per limb, ciphertexts
     uint32_t *d_flag = nullptr;
     std::vector<U256> moduli;
     void *d_crt = nullptr;               // CrtLimb[L], built on first use of to_rns / from_rns (owned by d_tables)
@@ -176,6 +192,14 @@ int with_word_field(const fhe_rns_ntt *h, Fn &&fn) {
         default: return fail(FHE_ERR_UNSUPPORTED, "width class " + std::to_string(h->width) + " has no word-sized field (compact polynomials and the field kernels exist on the word-sized classes only)");
     }
 }
+// The one place that types the engine's limb table for the kernels that are templated on the limb-table type and not on the field (bootstrap.hip.h,
+// lwe_pack.hip.h): fn(const Limb<F> *) on the word-sized classes, fn(const Limb256 *) on FHE_WIDTH_256; in the body, limb_of<decltype(limbs)>.
+template <class P> using limb_of = std::remove_const_t<std::remove_pointer_t<P>>;
+template <class Fn>
+int with_limbs(const fhe_rns_ntt *h, Fn &&fn) {
+    if (h->width == FHE_WIDTH_256) return fn((const fhe_dev::Limb256 *)h->d_limbs);
+    return with_word_field(h, [&](auto f) { return fn((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
 // every modulus below 2^64: a word-sized class, or FHE_WIDTH_256 chosen for the SIZE (n < 2^11 has no word-sized kernels), not for a wide modulus
 inline bool word_sized_moduli(const fhe_rns_ntt *h) {
     for (const U256 &q : h->moduli) if (q.w[1] | q.w[2] | q.w[3]) return false;
@@ -200,19 +224,30 @@ int create_impl(fhe_rns_ntt **out, uint32_t n, const uint64_t (*moduli)[4], uint
 void destroy_impl(fhe_rns_ntt *h);
 int check_call(const fhe_rns_ntt *h, uint32_t batch, const char *what);
 int check_inputs(fhe_rns_ntt *h, std::initializer_list<const void *> operands, uint32_t batch);   // FHE_HIP_CHECK_INPUTS=1
-// Library-owned workspaces, per engine, grown on demand (never while the engine's stream is capturing):
-// d_ws : general paths (the reference mallocs/frees per multiply, src/ntt.cu:51-74) and the transformed b-side of the two-launch tensor product
-// d_ws2: c0, c1, c2 of the fused multiply + relinearise and the compact accumulators of a blind-rotation loop
-// d_ws3: the compact polynomials between the two launches of a two-pass transform (N beyond the LDS range)
-int grow_ws(fhe_rns_ntt *h, void **ws, size_t *have, size_t bytes);
+// check_call, then what the entry points around the blind rotation ask of the engine: every modulus below 2^64 (FHE_ERR_UNSUPPORTED, ahead of
+// the caller's null and alignment tests) and, with min_n8, n >= 8
+inline int check_word_call(const fhe_rns_ntt *h, uint32_t batch, const char *what, bool min_n8 = false) {
+    int rc = check_call(h, batch, what); if (rc) return rc;
+    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": every modulus must be below 2^64");
+    if (min_n8 && h->n < 8) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": n must be at least 8");
+    return FHE_OK;
+}
+// `count` samples per batch element (fhe_lwe_pack, fhe_rlwe_sample_extract_strided): a power of two in [1, n], and the sample rows are indexed in 32 bits
+inline int check_count(const fhe_rns_ntt *h, uint32_t count, uint32_t batch, const char *what) {
+    if (!count || (count & (count - 1)) || count > h->n) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": count must be a power of two in [1, n]");
+    if ((uint64_t)batch * count > 0xffffffffull) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": batch * count overflows 32 bits");
+    if ((uint64_t)batch * count * h->L > 0x7fffffffull) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": batch * count * num_primes too large");
+    return FHE_OK;
+}
+int grow_ws(fhe_rns_ntt *h, Workspace &w, size_t bytes);   // at least `bytes` in w (refused while h's stream is capturing)
 struct WsNeed {
-    size_t ws = 0, ws2 = 0, ws3 = 0;     // bytes of d_ws, d_ws2, d_ws3
+    size_t ws = 0, ws2 = 0, ws3 = 0;     // bytes of WS1, WS2, WS3
     WsNeed &operator|=(const WsNeed &o) { ws = std::max(ws, o.ws); ws2 = std::max(ws2, o.ws2); ws3 = std::max(ws3, o.ws3); return *this; }
     friend WsNeed operator|(WsNeed a, const WsNeed &b) { return a |= b; }
 };
 inline int ensure_need(fhe_rns_ntt *h, const WsNeed &n) {
-    int rc = grow_ws(h, &h->d_ws, &h->ws_bytes, n.ws); if (!rc) rc = grow_ws(h, &h->d_ws2, &h->ws2_bytes, n.ws2);
-    return rc ? rc : grow_ws(h, &h->d_ws3, &h->ws3_bytes, n.ws3);
+    int rc = grow_ws(h, h->ws[WS1], n.ws); if (!rc) rc = grow_ws(h, h->ws[WS2], n.ws2);
+    return rc ? rc : grow_ws(h, h->ws[WS3], n.ws3);
 }
 int ensure_aux_stream(fhe_rns_ntt *h);   // second stream + events of the chunked two-stage pipelines, created on first use
 
@@ -231,17 +266,17 @@ int upload(fhe_rns_ntt *h, const std::vector<T> &v, void **out) {    // a table 
 // form needs of the workspaces; need_* merges the plans of an entry point's calls, the entry point ensures that, and so does fhe_rns_ntt_reserve.
 struct LdsPlan {
     fhe_dev::LdsForm form = fhe_dev::LDS_ONE_LAUNCH;
-    int ws = 0;                          // the form's own workspace (LdsArgs::ws): 0 none, 1 d_ws, 3 d_ws3
+    int ws = 0;                          // the form's own workspace (LdsArgs::ws): 0 none, 1 WS1, 3 WS3
     size_t bytes = 0;
     bool compact = false;                // key switch: c2 is read compact (compacted first, or from the fused tensor product); external product: the
                                          // blind-rotation loop keeps the accumulator pair compact
     bool add_compact = false;            // key switch: separate compact addends (KS_FUSED) instead of accumulating in place
     bool prerot = false;                 // external product: the loop applies the monomial factor once per step (rotated digit sources rot0, rot1)
-    size_t ws2 = 0;                      // compact polynomials in d_ws2: 3 components (KS_FUSED), 1 (compacted KS_C2), 4 or 6 (compact external-product loop)
+    size_t ws2 = 0;                      // compact polynomials in WS2: 3 components (KS_FUSED), 1 (compacted KS_C2), 4 or 6 (compact external-product loop)
     WsNeed need() const { return {ws == 1 ? bytes : 0, ws2, ws == 3 ? bytes : 0}; }
 };
 // Key switch source.  KS_C2: c2 in containers, compacted first where that pays; KS_C2_AS_IS: containers that must stay where they are (c2 already
-// in d_ws2: the composed multiply + relinearise under a testing switch); KS_FUSED: c2 and the addends are compact polynomials
+// in WS2: the composed multiply + relinearise under a testing switch); KS_FUSED: c2 and the addends are compact polynomials
 enum KsSource { KS_C2, KS_C2_AS_IS, KS_FUSED };
 LdsPlan plan_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands);
 LdsPlan plan_ct_multiply(const fhe_rns_ntt *h, size_t polys, bool same_operands, bool compact_out, bool alone);
@@ -265,7 +300,7 @@ WsNeed need_apply_galois(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool 
 WsNeed need_blind_rotate(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed);
 inline fhe_dev::LdsArgs lds_args(fhe_rns_ntt *h, int op, const LdsPlan &p, uint32_t polys) {   // everything but the operands and layouts of the op
     fhe_dev::LdsArgs A;
-    A.op = op; A.form = p.form; A.ws = p.ws == 1 ? h->d_ws : p.ws == 3 ? h->d_ws3 : nullptr;
+    A.op = op; A.form = p.form; A.ws = p.ws == 1 ? h->ws[WS1].p : p.ws == 3 ? h->ws[WS3].p : nullptr;
     A.limbs = h->d_limbs; A.L = h->L; A.polys = polys; A.stream = h->stream;
     return A;
 }

@@ -9,14 +9,7 @@
 void destroy_impl(fhe_rns_ntt *h) {
     if (!h) return;
     for (void *p : h->d_tables) (void)hipFree(p);
-    if (h->d_ws) (void)hipFree(h->d_ws);
-    if (h->d_ws2) (void)hipFree(h->d_ws2);
-    if (h->d_ws3) (void)hipFree(h->d_ws3);
-    if (h->d_hoist) (void)hipFree(h->d_hoist);
-    if (h->d_lin) (void)hipFree(h->d_lin);
-    if (h->d_enc) (void)hipFree(h->d_enc);
-    if (h->d_dec) (void)hipFree(h->d_dec);
-    if (h->d_pack) (void)hipFree(h->d_pack);
+    for (Workspace &w : h->ws) if (w.p) (void)hipFree(w.p);
     if (h->d_cdt) (void)hipFree(h->d_cdt);
     if (h->d_flag) (void)hipFree(h->d_flag);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
@@ -294,17 +287,17 @@ int check_call(const fhe_rns_ntt *h, uint32_t batch, const char *what) {
 // A hipGraph captured from a call has the workspace addresses baked in, so growing (free + malloc) later would make every replay
 // touch freed memory: growth is refused while the engine's stream is capturing (call fhe_rns_ntt_reserve(h, max_batch) before the
 // capture; after it nothing here allocates), and a larger batch after a capture needs a re-capture -- see INTEGRATION.md.
-int grow_ws(fhe_rns_ntt *h, void **ws, size_t *have, size_t bytes) {
-    if (*have >= bytes) return FHE_OK;
+int grow_ws(fhe_rns_ntt *h, Workspace &w, size_t bytes) {
+    if (w.bytes >= bytes) return FHE_OK;
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(h->stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
         return fail(FHE_ERR_INVALID_ARG, "a library workspace would have to grow while the engine's stream is being captured into a graph: "
                                          "call fhe_rns_ntt_reserve(h, batch) for the largest batch before the capture");
     (void)hipGetLastError();
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*ws) { HIP_TRY(hipFree(*ws)); *ws = nullptr; *have = 0; }
-    HIP_TRY(hipMalloc(ws, bytes));
-    *have = bytes;
+    if (w.p) { HIP_TRY(hipFree(w.p)); w = Workspace{}; }
+    HIP_TRY(hipMalloc(&w.p, bytes));
+    w.bytes = bytes;
     return FHE_OK;
 }
 // second stream + events of the chunked two-stage pipelines (fhe_ct_multiply_relin, stand-alone relinearisation): created on first use
@@ -359,7 +352,8 @@ extern "C" int fhe_rns_ntt_reserve(fhe_rns_ntt_t *h, uint32_t batch) {
 }
 extern "C" int fhe_rns_ntt_workspace_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {
     if (!h || !bytes) return fail(FHE_ERR_INVALID_ARG, "workspace_bytes: null argument");
-    *bytes = (uint64_t)h->ws_bytes + h->ws2_bytes + h->ws3_bytes + h->lin_bytes + h->enc_bytes + h->dec_bytes + h->pack_bytes;
+    *bytes = 0;
+    for (int id = 0; id < WS_COUNT; id++) if (ws_in_workspace_bytes(id)) *bytes += h->ws[id].bytes;
     return FHE_OK;
 }
 extern "C" int fhe_rns_ntt_width_class(const fhe_rns_ntt_t *h) { return h ? h->width : fail(FHE_ERR_INVALID_ARG, "null handle"); }

@@ -95,7 +95,7 @@ struct Pipeline {
     uint32_t chunks = 1;
     struct { LdsPlan first, ks; } c[16]; // per chunk: tensor product (the relinearisation's first stage, the compaction, has no plan), key switch
     WsNeed need;                         // of the whole call
-    void add(const LdsPlan &p) { const size_t ws2 = need.ws2 + p.ws2; need |= p.need(); need.ws2 = ws2; }   // every chunk has its own slice of d_ws2
+    void add(const LdsPlan &p) { const size_t ws2 = need.ws2 + p.ws2; need |= p.need(); need.ws2 = ws2; }   // every chunk has its own slice of WS2
 };
 static uint32_t pipeline_chunks(const fhe_rns_ntt *h, uint32_t batch, uint32_t want) { while (want > 1 && ((size_t)batch * h->L / want < 1024 || batch < want)) want--; return want; }
 static uint32_t chunk_begin(uint32_t batch, uint32_t chunks, uint32_t c) { return c * (batch / chunks) + std::min(c, batch % chunks); }   // first ciphertext of chunk c
@@ -110,14 +110,14 @@ static Pipeline relin_pipeline(const fhe_rns_ntt *h, uint32_t batch, uint32_t K,
         pl.add(pl.c[c].ks = pl.chunks == 1 ? P : plan_keyswitch(h, (size_t)(chunk_begin(batch, pl.chunks, c + 1) - chunk_begin(batch, pl.chunks, c)) * h->L, K, KS_C2, false));
     return pl;
 }
-// The composed key switch (no packed tables): digit polynomials D[L K][chunk] + two accumulators in d_ws, bounded to ~1 GiB: ciphertexts per chunk
+// The composed key switch (no packed tables): digit polynomials D[L K][chunk] + two accumulators in WS1, bounded to ~1 GiB: ciphertexts per chunk
 static uint32_t composed_chunk(const fhe_rns_ntt *h, uint32_t batch, uint32_t K) {
     return (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / (((size_t)h->L * K + 2) * h->L * h->n * 32), 1), batch);
 }
 WsNeed need_relinearize(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed, KsSource src) {
     const size_t LK = (size_t)h->L * K, chunk = composed_chunk(h, batch, K);
     if (packed) return relin_pipeline(h, batch, K, src).need;
-    return {(LK + 2) * chunk * h->L * h->n * 32, 0, 0};   // (the transforms of the digit polynomials and accumulators ensure their own d_ws3, as before)
+    return {(LK + 2) * chunk * h->L * h->n * 32, 0, 0};   // (the transforms of the digit polynomials and accumulators ensure their own WS3, as before)
 }
 // Two-stream chunk pipeline: what the engine's stream has queued for chunk c is done -> the second stream may start on it; at the end the
 // engine's stream joins the second one, so the call stays ordered on the engine's stream (and can be captured: fork / join through events).
@@ -141,7 +141,7 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
     if ((rc = check_inputs(h, {d_c0, d_c1, d_c2}, batch))) return rc;
     if (rk->d_pkb) {   // word-sized paths: fused launches
         // (c2 already in the workspace: the composed multiply + relinearise under a testing switch -- it stays where it is)
-        const bool c2_in_ws2 = h->d_ws2 && (const char *)d_c2 >= (const char *)h->d_ws2 && (const char *)d_c2 < (const char *)h->d_ws2 + h->ws2_bytes;
+        const bool c2_in_ws2 = h->ws[WS2].p && (const char *)d_c2 >= (const char *)h->ws[WS2].p && (const char *)d_c2 < (const char *)h->ws[WS2].p + h->ws[WS2].bytes;
         const Pipeline pl = relin_pipeline(h, batch, rk->K, c2_in_ws2 ? KS_C2_AS_IS : KS_C2);
         const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * residue_bytes(h);
         if ((rc = ensure_need(h, pl.need)) || (pl.chunks > 1 && (rc = ensure_aux_stream(h)))) return rc;
@@ -150,7 +150,7 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
             const LdsPlan &Q = pl.c[c].ks;
             const void *c2 = (const char *)d_c2 + (size_t)b0 * S;
             if (Q.compact) {
-                char *c2c = (char *)h->d_ws2 + (size_t)b0 * Sc;
+                char *c2c = (char *)h->ws[WS2].p + (size_t)b0 * Sc;
                 if ((rc = compact_poly(h, c2c, c2, (size_t)nb * h->L * h->n))) return rc;
                 c2 = c2c;
             }
@@ -163,7 +163,7 @@ extern "C" int fhe_ct_relinearize(fhe_rns_ntt_t *h, const fhe_relin_keys_t *rk, 
     const uint32_t LK = h->L * rk->K, chunk = composed_chunk(h, batch, rk->K);
     const size_t S = (size_t)h->L * h->n * 32;
     if ((rc = ensure_need(h, need_relinearize(h, batch, rk->K, false, KS_C2)))) return rc;
-    char *D = (char *)h->d_ws, *acc0 = D + (size_t)LK * chunk * S, *acc1 = acc0 + (size_t)chunk * S;
+    char *D = (char *)h->ws[WS1].p, *acc0 = D + (size_t)LK * chunk * S, *acc1 = acc0 + (size_t)chunk * S;
     for (uint32_t done = 0; done < batch; done += chunk) {
         const uint32_t nb = batch - done < chunk ? batch - done : chunk;
         const char *c2 = (const char *)d_c2 + (size_t)done * S;
@@ -188,11 +188,11 @@ static Pipeline ct_relin_pipeline(const fhe_rns_ntt *h, uint32_t batch, uint32_t
     for (uint32_t c = 0; c < pl.chunks; c++) {
         const size_t polys = (size_t)(chunk_begin(batch, pl.chunks, c + 1) - chunk_begin(batch, pl.chunks, c)) * h->L;
         pl.add(pl.c[c].first = pl.chunks == 1 ? T : plan_ct_multiply(h, polys, false, true, false));
-        pl.add(pl.c[c].ks = plan_keyswitch(h, polys, K, KS_FUSED, pl.chunks == 1 && !two));   // (the few-ciphertext parts take d_ws: never beside the two-launch form)
+        pl.add(pl.c[c].ks = plan_keyswitch(h, polys, K, KS_FUSED, pl.chunks == 1 && !two));   // (the few-ciphertext parts take WS1: never beside the two-launch form)
     }
     return pl;
 }
-WsNeed need_ct_multiply_relin(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {   // composed: the tensor product's c2 as containers in d_ws2
+WsNeed need_ct_multiply_relin(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {   // composed: the tensor product's c2 as containers in WS2
     return plan_fused_ct_relin(h, packed) ? ct_relin_pipeline(h, batch, K).need
                                           : WsNeed{0, (size_t)batch * h->L * h->n * 32, 0} | need_ct_multiply(h, batch, false) | need_relinearize(h, batch, K, packed, KS_C2_AS_IS);
 }
@@ -222,7 +222,7 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
         const Pipeline pl = ct_relin_pipeline(h, batch, rk->K);             // (its need is need_ct_multiply_relin's)
         if ((rc = ensure_need(h, pl.need)) || (pl.chunks > 1 && (rc = ensure_aux_stream(h)))) return rc;
         const size_t eb = residue_bytes(h), cbytes = (size_t)batch * h->L * h->n * eb;       // one compact component
-        char *c0c = (char *)h->d_ws2, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
+        char *c0c = (char *)h->ws[WS2].p, *c1c = c0c + cbytes, *c2c = c1c + cbytes;
         const size_t S = (size_t)h->L * h->n * 32, Sc = (size_t)h->L * h->n * eb;   // bytes of one ciphertext component: containers / compact
         for (uint32_t c = 0; c < pl.chunks; c++) {
             const uint32_t b0 = chunk_begin(batch, pl.chunks, c), nb = chunk_begin(batch, pl.chunks, c + 1) - b0;
@@ -239,8 +239,8 @@ extern "C" int fhe_ct_multiply_relin(fhe_rns_ntt_t *h, const fhe_relin_keys_t *r
         return pl.chunks > 1 ? join_chunks(h) : FHE_OK;
     }
     if ((rc = ensure_need(h, need_ct_multiply_relin(h, batch, rk->K, rk->d_pkb != nullptr)))) return rc;
-    if ((rc = do_ct_multiply(h, d_c0, d_c1, h->d_ws2, d_a0, d_a1, d_b0, d_b1, batch))) return rc;
-    return fhe_ct_relinearize(h, rk, d_c0, d_c1, h->d_ws2, batch);
+    if ((rc = do_ct_multiply(h, d_c0, d_c1, h->ws[WS2].p, d_a0, d_a1, d_b0, d_b1, batch))) return rc;
+    return fhe_ct_relinearize(h, rk, d_c0, d_c1, h->ws[WS2].p, batch);
 }
 
 
@@ -308,9 +308,9 @@ extern "C" int fhe_rns_automorphism(fhe_rns_ntt_t *h, void *d_out, const void *d
 }
 // (c0, c1) -> (sigma(c0) + sum D(sigma(c1)) b, sum D(sigma(c1)) a): bit for bit fhe_ct_relinearize applied to (sigma(c0), 0, sigma(c1)).
 // Fused path (the LDS-resident word-sized sizes with packed keys, as plan_fused_ct_relin): the prologue writes sigma(c0), sigma(c1) and a zero
-// polynomial as compact polynomials into the three slices of d_ws2 that fhe_ct_multiply_relin uses, then ONE compact-operand key switch
+// polynomial as compact polynomials into the three slices of WS2 that fhe_ct_multiply_relin uses, then ONE compact-operand key switch
 // (KS_FUSED) reads them -- HBM traffic 2 S in + 2 S out plus the compact round trip.  Elsewhere: sigma(c0) -> out0, zero -> out1 and
-// sigma(c1) -> d_ws2 as containers in one launch, then fhe_ct_relinearize.
+// sigma(c1) -> WS2 as containers in one launch, then fhe_ct_relinearize.
 WsNeed need_apply_galois(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool packed) {
     if (plan_fused_ct_relin(h, packed) && !h->env.no_fused_galois) return plan_keyswitch(h, (size_t)batch * h->L, K, KS_FUSED, true).need();
     return WsNeed{0, (size_t)batch * h->L * h->n * 32, 0} | need_relinearize(h, batch, K, packed, KS_C2_AS_IS);
@@ -329,22 +329,22 @@ extern "C" int fhe_ct_apply_galois(fhe_rns_ntt_t *h, const fhe_relin_keys_t *gk,
     if ((rc = ensure_need(h, need_apply_galois(h, batch, gk->K, gk->d_pkb != nullptr)))) return rc;
     if (plan_fused_ct_relin(h, gk->d_pkb != nullptr) && !h->env.no_fused_galois) {
         const size_t cbytes = polys * h->n * residue_bytes(h);
-        char *s0 = (char *)h->d_ws2, *s1 = s0 + cbytes, *zero = s1 + cbytes;      // sigma(c0): addend of c0'; sigma(c1): digit source; 0: addend of c1'
+        char *s0 = (char *)h->ws[WS2].p, *s1 = s0 + cbytes, *zero = s1 + cbytes;      // sigma(c0): addend of c0'; sigma(c1): digit source; 0: addend of c1'
         const LdsPlan P = plan_keyswitch(h, polys, gk->K, KS_FUSED, true);
         if ((rc = do_galois(h, s0, s1, zero, d_c0, d_c1, galois_elt, polys, true))) return rc;
         return lds_launch(h, keyswitch_args(h, gk, P, d_out0, d_out1, s1, s0, zero, (uint32_t)polys, h->stream), "key switch (rotation)");
     }
-    if ((rc = do_galois(h, d_out0, h->d_ws2, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
-    return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->d_ws2, batch);
+    if ((rc = do_galois(h, d_out0, h->ws[WS2].p, d_out1, d_c0, d_c1, galois_elt, polys, false))) return rc;
+    return fhe_ct_relinearize(h, gk, d_out0, d_out1, h->ws[WS2].p, batch);
 }
 
 // ------------------------------------------------------------------------------------------------------
 // Hoisted rotations (Halevi-Shoup): fhe_ct_hoist decomposes and transforms c1 once, every fhe_ct_apply_galois_hoisted is a permuted
 // multiply-accumulate with the key rows, two inverse transforms and sigma_g(c0)   (semantics and pi_g: include/fhe_hip.h)
 // ------------------------------------------------------------------------------------------------------
-// Fused path (plan_fused_hoist; kernels: hoist.hip.h): c1 compacted into d_ws2, ntt_hoist_kernel writes the L K L kept polynomials as
-// residues; a rotation is the one-component automorphism of c0 into d_ws2 (compact) and ntt_hoist_apply_kernel.  Composed path: the
-// digit polynomials as containers [jk][b][i] (digit_embed + forward transform); a rotation is relin_mac_perm (first sum into d_ws, second
+// Fused path (plan_fused_hoist; kernels: hoist.hip.h): c1 compacted into WS2, ntt_hoist_kernel writes the L K L kept polynomials as
+// residues; a rotation is the one-component automorphism of c0 into WS2 (compact) and ntt_hoist_apply_kernel.  Composed path: the
+// digit polynomials as containers [jk][b][i] (digit_embed + forward transform); a rotation is relin_mac_perm (first sum into WS1, second
 // into out1), two inverse transforms, sigma_g(c0) into out0 and an addition.  A key set that kept only its packed tables (N = 2^15,
 // FHE_HIP_NO_FUSED_HOIST=1) is read from those (relin_mac_perm_packed_kernel): key import is the same with and without hoisting.
 static bool hoist_fused(const fhe_rns_ntt *h, uint32_t w, uint32_t K) { return plan_fused_hoist(h, keys_get_packed(h, w, K)); }
@@ -359,8 +359,8 @@ static WsNeed need_hoist(const fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool 
 static int ensure_hoist(fhe_rns_ntt *h, uint32_t batch, uint32_t K, bool fused) {
     int rc = ensure_need(h, need_hoist(h, batch, K, fused)); if (rc) return rc;
     const size_t bytes = hoist_size(h, batch, K, fused);
-    if (h->hoist_bytes < bytes) h->hoist.valid = false;                       // growing drops what was kept
-    return grow_ws(h, &h->d_hoist, &h->hoist_bytes, bytes);
+    if (h->ws[WS_HOIST].bytes < bytes) h->hoist.valid = false;                       // growing drops what was kept
+    return grow_ws(h, h->ws[WS_HOIST], bytes);
 }
 static int check_hoist_call(const fhe_rns_ntt *h, uint32_t decomp_bits, uint32_t batch, const char *what) {
     int rc = check_call(h, batch, what); if (rc) return rc;
@@ -375,7 +375,7 @@ extern "C" int fhe_rns_ntt_reserve_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits,
 }
 extern "C" int fhe_rns_ntt_hoist_bytes(const fhe_rns_ntt_t *h, uint64_t *bytes) {
     if (!h || !bytes) return fail(FHE_ERR_INVALID_ARG, "hoist_bytes: null argument");
-    *bytes = (uint64_t)h->hoist_bytes;
+    *bytes = (uint64_t)h->ws[WS_HOIST].bytes;
     return FHE_OK;
 }
 extern "C" int fhe_ct_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, const void *d_c1, uint32_t batch) {
@@ -388,13 +388,13 @@ extern "C" int fhe_ct_hoist(fhe_rns_ntt_t *h, uint32_t decomp_bits, const void *
     h->hoist.valid = false;
     if ((rc = ensure_hoist(h, batch, K, fused))) return rc;
     if (fused) {
-        if ((rc = compact_poly(h, h->d_ws2, d_c1, (size_t)batch * h->L * h->n))) return rc;
+        if ((rc = compact_poly(h, h->ws[WS2].p, d_c1, (size_t)batch * h->L * h->n))) return rc;
         fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST, {}, batch * h->L * h->L);
-        A.r0 = h->d_hoist; A.c2 = h->d_ws2; A.in_compact = true; A.K = K; A.w = decomp_bits;
+        A.r0 = h->ws[WS_HOIST].p; A.c2 = h->ws[WS2].p; A.in_compact = true; A.K = K; A.w = decomp_bits;
         if ((rc = lds_launch(h, A, "ntt_hoist_kernel"))) return rc;
     } else {
-        if ((rc = embed_digits(h, (char *)h->d_hoist, d_c1, K, decomp_bits, batch))) return rc;
-        if ((rc = do_forward(h, h->d_hoist, h->L * K * batch))) return rc;
+        if ((rc = embed_digits(h, (char *)h->ws[WS_HOIST].p, d_c1, K, decomp_bits, batch))) return rc;
+        if ((rc = do_forward(h, h->ws[WS_HOIST].p, h->L * K * batch))) return rc;
     }
     h->hoist.valid = true; h->hoist.fused = fused; h->hoist.w = decomp_bits; h->hoist.K = K; h->hoist.batch = batch;
     return FHE_OK;
@@ -405,16 +405,16 @@ static int relin_mac_perm(fhe_rns_ntt *h, const fhe_relin_keys *gk, void *acc0, 
     if (h->width != FHE_WIDTH_256) return with_word_field(h, [&](auto f) {
         using F = decltype(f); using V = typename F::V16;
         if (!gk->d_kb) {
-            hipLaunchKernelGGL((fhe_dev::relin_mac_perm_packed_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->d_hoist,
+            hipLaunchKernelGGL((fhe_dev::relin_mac_perm_packed_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->ws[WS_HOIST].p,
                                (const typename F::E *)gk->d_pkb, (const typename F::E *)gk->d_pka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, batch, g);
             return post_launch(h->stream, "relin_mac_perm_packed_kernel");
         }
-        hipLaunchKernelGGL((fhe_dev::relin_mac_perm_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->d_hoist,
+        hipLaunchKernelGGL((fhe_dev::relin_mac_perm_kernel<F>), dim3(ew_grid(count * 2)), dim3(256), 0, h->stream, (V *)acc0, (V *)acc1, (const V *)h->ws[WS_HOIST].p,
                            (const V *)gk->d_kb, (const V *)gk->d_ka, (const fhe_dev::Limb<F> *)h->d_limbs, h->L, h->log_n, LK, batch, g);
         return post_launch(h->stream, "relin_mac_perm_kernel");
     });
     hipLaunchKernelGGL(fhe_dev::relin_mac_perm256_kernel, dim3(ew_grid(count)), dim3(256), 0, h->stream, (fhe_dev::u256 *)acc0, (fhe_dev::u256 *)acc1,
-                       (const fhe_dev::u256 *)h->d_hoist, (const fhe_dev::u256 *)gk->d_kb, (const fhe_dev::u256 *)gk->d_ka,
+                       (const fhe_dev::u256 *)h->ws[WS_HOIST].p, (const fhe_dev::u256 *)gk->d_kb, (const fhe_dev::u256 *)gk->d_ka,
                        (const fhe_dev::Limb256 *)h->d_limbs, h->L, h->log_n, LK, batch, g);
     return post_launch(h->stream, "relin_mac_perm256_kernel");
 }
@@ -434,17 +434,17 @@ extern "C" int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_key
     if ((rc = ensure_hoist(h, batch, gk->K, h->hoist.fused))) return rc;       // (no-op after fhe_ct_hoist: the workspaces only ever grow)
     const size_t polys = (size_t)batch * h->L;
     if (h->hoist.fused) {
-        if ((rc = do_galois(h, h->d_ws2, nullptr, nullptr, d_c0, nullptr, galois_elt, polys, true))) return rc;
+        if ((rc = do_galois(h, h->ws[WS2].p, nullptr, nullptr, d_c0, nullptr, galois_elt, polys, true))) return rc;
         fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST_APPLY, {}, (uint32_t)polys);
-        A.r0 = d_out0; A.r1 = d_out1; A.c2 = h->d_hoist; A.add0 = h->d_ws2; A.in_compact = A.add_compact = true;
+        A.r0 = d_out0; A.r1 = d_out1; A.c2 = h->ws[WS_HOIST].p; A.add0 = h->ws[WS2].p; A.in_compact = A.add_compact = true;
         A.kb = gk->d_pkb; A.ka = gk->d_pka; A.K = gk->K; A.galois = galois_elt;
         return lds_launch(h, A, "ntt_hoist_apply_kernel");
     }
-    if ((rc = relin_mac_perm(h, gk, h->d_ws, d_out1, galois_elt, batch))) return rc;
-    if ((rc = do_inverse(h, h->d_ws, batch))) return rc;
+    if ((rc = relin_mac_perm(h, gk, h->ws[WS1].p, d_out1, galois_elt, batch))) return rc;
+    if ((rc = do_inverse(h, h->ws[WS1].p, batch))) return rc;
     if ((rc = do_inverse(h, d_out1, batch))) return rc;
     if ((rc = do_galois(h, d_out0, nullptr, nullptr, d_c0, nullptr, galois_elt, polys, false))) return rc;
-    return do_ew<1>(h, d_out0, d_out0, h->d_ws, batch, "hoisted rotation add");
+    return do_ew<1>(h, d_out0, d_out0, h->ws[WS1].p, batch, "hoisted rotation add");
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -452,8 +452,8 @@ extern "C" int fhe_ct_apply_galois_hoisted(fhe_rns_ntt_t *h, const fhe_relin_key
 // ------------------------------------------------------------------------------------------------------
 // Fused path (plan_fused_lincomb, every keyed term with packed tables; kernels: hoist_lincomb.hip.h): the plaintexts are kept transformed and
 // packed like key rows, the terms sit in a device table, and a call is two launches whatever G is: c0 (and c1, where a term has no key)
-// forward into d_lin in the hoist layout, then ntt_hoist_lincomb_kernel.  Composed path: the plaintexts are kept as given, and every term is
-// fhe_ct_apply_galois_hoisted into d_lin (the first term: into the outputs), fhe_rns_ntt_multiply_bcast and fhe_rns_poly_add.
+// forward into WS_LIN in the hoist layout, then ntt_hoist_lincomb_kernel.  Composed path: the plaintexts are kept as given, and every term is
+// fhe_ct_apply_galois_hoisted into WS_LIN (the first term: into the outputs), fhe_rns_ntt_multiply_bcast and fhe_rns_poly_add.
 struct fhe_linear_transform {
     fhe_rns_ntt *owner = nullptr;
     uint32_t decomp_bits = 0, K = 0;
@@ -519,14 +519,14 @@ extern "C" int fhe_linear_transform_create(fhe_rns_ntt_t *h, fhe_linear_transfor
     *out = lt;
     return FHE_OK;
 }
-// bytes of d_lin for `batch` ciphertexts: c0^ and c1^ as residues, or two container components
+// bytes of WS_LIN for `batch` ciphertexts: c0^ and c1^ as residues, or two container components
 static size_t lincomb_scratch(const fhe_rns_ntt *h, const fhe_linear_transform *lt, uint32_t batch) {
     return (size_t)batch * h->L * h->n * (lt->fused ? (lt->keyless ? 2 : 1) * residue_bytes(h) : 2 * 32);
 }
 static int ensure_lincomb(fhe_rns_ntt *h, const fhe_linear_transform *lt, uint32_t batch) {
     int rc = ensure_hoist(h, batch, lt->K, hoist_fused(h, lt->decomp_bits, lt->K)); if (rc) return rc;
     if (!lt->fused && (rc = ensure_need(h, need_multiply(h, batch)))) return rc;
-    return grow_ws(h, &h->d_lin, &h->lin_bytes, lincomb_scratch(h, lt, batch));
+    return grow_ws(h, h->ws[WS_LIN], lincomb_scratch(h, lt, batch));
 }
 extern "C" int fhe_linear_transform_reserve(fhe_rns_ntt_t *h, const fhe_linear_transform_t *lt, uint32_t batch) {
     if (!h || !lt) return fail(FHE_ERR_INVALID_ARG, "linear_transform_reserve: null argument");
@@ -553,16 +553,16 @@ extern "C" int fhe_ct_linear_transform_hoisted(fhe_rns_ntt_t *h, const fhe_linea
     const uint32_t polys = batch * h->L, G = (uint32_t)lt->g.size();
     if (lt->fused) {
         fhe_dev::LdsArgs A = lds_args(h, fhe_dev::LDS_HOIST_FWD, {}, polys);
-        A.r0 = h->d_lin; A.a0 = d_c0; A.a1 = lt->keyless ? d_c1 : nullptr; A.out_compact = true;
+        A.r0 = h->ws[WS_LIN].p; A.a0 = d_c0; A.a1 = lt->keyless ? d_c1 : nullptr; A.out_compact = true;
         if ((rc = lds_launch(h, A, "ntt_hoist_fwd_kernel"))) return rc;
         fhe_dev::LdsArgs B = lds_args(h, fhe_dev::LDS_HOIST_LINCOMB, {}, polys);
-        B.r0 = d_out0; B.r1 = d_out1; B.c2 = h->d_hoist; B.add0 = h->d_lin; B.in_compact = B.add_compact = true;
-        B.add1 = lt->keyless ? (const char *)h->d_lin + (size_t)polys * h->n * residue_bytes(h) : nullptr;
+        B.r0 = d_out0; B.r1 = d_out1; B.c2 = h->ws[WS_HOIST].p; B.add0 = h->ws[WS_LIN].p; B.in_compact = B.add_compact = true;
+        B.add1 = lt->keyless ? (const char *)h->ws[WS_LIN].p + (size_t)polys * h->n * residue_bytes(h) : nullptr;
         B.terms = lt->d_terms; B.num_terms = G; B.K = lt->K;
         return lds_launch(h, B, "ntt_hoist_lincomb_kernel");
     }
     const size_t S = (size_t)h->L * h->n * 32;
-    char *s0 = (char *)h->d_lin, *s1 = s0 + (size_t)batch * S;
+    char *s0 = (char *)h->ws[WS_LIN].p, *s1 = s0 + (size_t)batch * S;
     for (uint32_t t = 0; t < G; t++) {
         void *t0 = t ? (void *)s0 : d_out0, *t1 = t ? (void *)s1 : d_out1;    // the first term goes straight to the outputs
         const void *pt = (const char *)lt->d_plain + (size_t)t * S;
@@ -665,7 +665,7 @@ extern "C" int fhe_blind_rotate(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const 
         // polynomials; 2 more hold the pre-rotated pair of the current step), all but the last write compact output, the last one writes the
         // caller's containers.  The caller's scratch pair is not touched.
         const size_t cbytes = (size_t)batch * h->L * h->n * residue_bytes(h), count = (size_t)batch * h->L * h->n;
-        char *w0 = (char *)h->d_ws2;
+        char *w0 = (char *)h->ws[WS2].p;
         char *pp[2][2] = {{w0, w0 + cbytes}, {w0 + 2 * cbytes, w0 + 3 * cbytes}};
         char *rot0 = w0 + 4 * cbytes, *rot1 = w0 + 5 * cbytes;       // (X^a - 1) * acc of the current step
         if ((rc = compact_poly(h, pp[1][0], d_acc0, count))) return rc;

@@ -16,18 +16,10 @@ struct fhe_lwe_ksk {
     uint64_t *d_rows = nullptr;                            // [R][ncp], padding columns zero
 };
 
-static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 static uint32_t bit_length(uint64_t v) { return v ? 64 - (uint32_t)__builtin_clzll(v) : 0; }
 static uint32_t ksk_digits(uint64_t q, uint32_t w) { return (bit_length(q) + w - 1) / w; }
 
-// the checks every entry point that names an engine and a digit width shares; `what` prefixes the message
-static int check_engine(const fhe_rns_ntt *h, const char *what) {
-    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": every modulus must be below 2^64");
-    return FHE_OK;
-}
+// the checks every entry point that names a digit width shares; `what` prefixes the message
 static int check_shape(uint32_t decomp_bits, uint32_t n_out, const char *what) {
     if (decomp_bits < 1 || decomp_bits > 32) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": decomp_bits must be in [1, 32]");
     if (!n_out || n_out > 65536) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": n_out must be in [1, 65536]");
@@ -60,7 +52,7 @@ extern "C" int fhe_lwe_ksk_destroy(fhe_lwe_ksk_t *ksk) {
 
 extern "C" int fhe_lwe_ksk_num_digits(const fhe_rns_ntt_t *h, uint32_t decomp_bits, uint32_t *digits) {
     if (!h || !digits) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_num_digits: null argument");
-    if (int rc = check_engine(h, "lwe_ksk_num_digits")) return rc;
+    if (int rc = check_word_call(h, 1, "lwe_ksk_num_digits")) return rc;
     if (decomp_bits < 1 || decomp_bits > 32) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_num_digits: decomp_bits must be in [1, 32]");
     *digits = ksk_digits(h->moduli[0].w[0], decomp_bits);
     return FHE_OK;
@@ -79,8 +71,7 @@ static int repack(hipStream_t stream, uint64_t *dst, const uint64_t *src, const 
 }
 
 extern "C" int fhe_lwe_ksk_create(fhe_rns_ntt_t *h, fhe_lwe_ksk_t **out, uint32_t decomp_bits, uint32_t n_out, const uint64_t *d_rows) {
-    int rc = check_call(h, 1, "lwe_ksk_create"); if (rc) return rc;
-    if ((rc = check_engine(h, "lwe_ksk_create"))) return rc;
+    int rc = check_word_call(h, 1, "lwe_ksk_create"); if (rc) return rc;
     if (!out || !d_rows) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_create: null argument");
     if ((uintptr_t)d_rows & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_create: d_rows must be 8-byte aligned");
     if ((rc = check_shape(decomp_bits, n_out, "lwe_ksk_create"))) return rc;
@@ -94,8 +85,7 @@ extern "C" int fhe_lwe_ksk_create(fhe_rns_ntt_t *h, fhe_lwe_ksk_t **out, uint32_
 }
 
 extern "C" int fhe_lwe_ksk_export(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t *d_rows) {
-    int rc = check_call(h, 1, "lwe_ksk_export"); if (rc) return rc;
-    if ((rc = check_engine(h, "lwe_ksk_export"))) return rc;
+    int rc = check_word_call(h, 1, "lwe_ksk_export"); if (rc) return rc;
     if (!ksk || !d_rows) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_export: null argument");
     if ((uintptr_t)d_rows & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_export: d_rows must be 8-byte aligned");
     if (!key_matches(h, ksk)) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_export: the engine does not match the key (degree, limb-0 modulus, device)");
@@ -104,8 +94,7 @@ extern "C" int fhe_lwe_ksk_export(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, ui
 
 extern "C" int fhe_lwe_ksk_generate(fhe_rns_ntt_t *h, const fhe_secret_key_t *sk, uint32_t decomp_bits, uint32_t n_out, const int32_t *z,
                                     uint64_t noise_scale, double sigma, const uint64_t seeds[2], fhe_lwe_ksk_t **out) {
-    int rc = check_call(h, 1, "lwe_ksk_generate"); if (rc) return rc;
-    if ((rc = check_engine(h, "lwe_ksk_generate"))) return rc;
+    int rc = check_word_call(h, 1, "lwe_ksk_generate"); if (rc) return rc;
     if (!sk || !z || !seeds || !out) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_generate: null argument");
     if (sk->owner != h) return fail(FHE_ERR_INVALID_ARG, "lwe_ksk_generate: the key was imported for a different engine");
     if ((rc = check_shape(decomp_bits, n_out, "lwe_ksk_generate"))) return rc;
@@ -158,8 +147,7 @@ static void launch_keyswitch(hipStream_t stream, const fhe_lwe_ksk *k, uint64_t 
 }
 
 extern "C" int fhe_lwe_keyswitch(fhe_rns_ntt_t *h, const fhe_lwe_ksk_t *ksk, uint64_t q_out, uint64_t *d_out, const uint64_t *d_in, uint32_t batch) {
-    int rc = check_call(h, batch, "lwe_keyswitch"); if (rc) return rc;
-    if ((rc = check_engine(h, "lwe_keyswitch"))) return rc;
+    int rc = check_word_call(h, batch, "lwe_keyswitch"); if (rc) return rc;
     if (!ksk || !d_out || !d_in) return fail(FHE_ERR_INVALID_ARG, "lwe_keyswitch: null argument");
     if (((uintptr_t)d_out | (uintptr_t)d_in) & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_keyswitch: d_out and d_in must be 8-byte aligned");
     if (q_out == 1 || q_out > (1ull << 48)) return fail(FHE_ERR_INVALID_ARG, "lwe_keyswitch: q_out must be 0 or in [2, 2^48]");

@@ -3,20 +3,14 @@
 // accumulators, without the samples in between (fhe_rlwe_pack).  The ring packing of Chen, Dai, Kim and Song: log2(count) merge
 // levels and, with the trace, log2(n / count) more automorphisms, every one a batched fhe_ct_apply_galois.
 // Fused path (kernels: lwe_pack.hip.h): per level one streaming launch and one key switch.  The first level reads the samples (or the pairs) themselves, a later
-// one forms the "P + G" of the level before in registers; three regions of the packing workspace d_pack rotate as (P, G, free).
-// Composed path (FHE_HIP_NO_FUSED_PACK=1, read per call): the literal composition of entry points through container scratch in d_pack -- the
+// one forms the "P + G" of the level before in registers; three regions of the packing workspace WS_PACK rotate as (P, G, free).
+// Composed path (FHE_HIP_NO_FUSED_PACK=1, read per call): the literal composition of entry points through container scratch in WS_PACK -- the
 // embedding, fhe_rns_monomial_mul_sub, fhe_rns_poly_add / sub, fhe_ct_apply_galois -- one batch element at a time where the pairs are strided;
-// fhe_rlwe_pack runs fhe_rlwe_sample_extract(idx = 0) into sample scratch at the end of d_pack first.
+// fhe_rlwe_pack runs fhe_rlwe_sample_extract(idx = 0) into sample scratch at the end of WS_PACK first.
 #include "engine.h"
-
-#include <type_traits>
 
 #include "lwe_pack.hip.h"
 
-static bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 static bool pack_composed_env() { const char *e = std::getenv("FHE_HIP_NO_FUSED_PACK"); return e && e[0] == '1'; }
 
 extern "C" int fhe_lwe_pack_galois_elements(uint32_t n, uint32_t *elts) {
@@ -34,57 +28,38 @@ template <bool PAIR>
 static int launch_embed(fhe_rns_ntt *h, void *o0, void *o1, void *d0, void *d1, const PackSource &src, uint32_t half, uint32_t halvings, size_t entries) {
     using V = fhe_dev::v2u64;
     const size_t halves = entries * h->L * h->n * 2;
-    const uint64_t *d_lwe = src.lwe;
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        if (!d_lwe) {
-            hipLaunchKernelGGL((fhe_dev::rlwe_embed_merge_kernel<LimbT, PAIR>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1,
-                               (const V *)src.c0, (const V *)src.c1, limbs, half, halvings, h->L, h->log_n, halves);
-            return post_launch(h->stream, PAIR ? "rlwe_embed_merge_kernel (first level)" : "rlwe_embed_merge_kernel (embedding)");
-        }
-        hipLaunchKernelGGL((fhe_dev::lwe_embed_merge_kernel<LimbT, PAIR>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1, d_lwe, limbs,
-                           half, halvings, h->L, h->log_n, halves);
-        return post_launch(h->stream, PAIR ? "lwe_embed_merge_kernel (first level)" : "lwe_embed_merge_kernel (embedding)");
+    auto launch = [&](auto source, const char *what, auto... in) {           // in: the arrays the source reads
+        return with_limbs(h, [&](auto *limbs) {
+            hipLaunchKernelGGL((fhe_dev::embed_merge_kernel<limb_of<decltype(limbs)>, decltype(source), PAIR, limb_of<decltype(in)>...>), dim3(ew_grid(halves)), dim3(256), 0,
+                               h->stream, (V *)o0, (V *)o1, (V *)d0, (V *)d1, in..., limbs, half, halvings, h->L, h->log_n, halves);
+            return post_launch(h->stream, what);
+        });
     };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+    if (src.lwe) return launch(fhe_dev::SampleRows{}, PAIR ? "embed_merge_kernel (samples, first level)" : "embed_merge_kernel (samples, embedding)", src.lwe);
+    return launch(fhe_dev::RlwePairs{}, PAIR ? "embed_merge_kernel (pairs, first level)" : "embed_merge_kernel (pairs, embedding)", (const V *)src.c0, (const V *)src.c1);
 }
 static int launch_merge(fhe_rns_ntt *h, char *np0, char *np1, char *nd0, char *nd1, const char *p0, const char *p1, const char *g0, const char *g1, uint32_t half,
                         uint32_t m, size_t entries) {
     using V = fhe_dev::v2u64;
     const size_t halves = entries * h->L * h->n * 2;
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        hipLaunchKernelGGL((fhe_dev::lwe_merge_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)np0, (V *)np1, (V *)nd0, (V *)nd1, (const V *)p0,
+    return with_limbs(h, [&](auto *limbs) {
+        hipLaunchKernelGGL((fhe_dev::lwe_merge_kernel<limb_of<decltype(limbs)>>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)np0, (V *)np1, (V *)nd0, (V *)nd1, (const V *)p0,
                            (const V *)p1, (const V *)g0, (const V *)g1, limbs, half, m, h->L, h->log_n, halves);
         return post_launch(h->stream, "lwe_merge_kernel");
-    };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+    });
 }
 static int launch_sum(fhe_rns_ntt *h, void *o0, void *o1, const void *a0, const void *a1, const void *b0, const void *b1, size_t entries) {
     using V = fhe_dev::v2u64;
     const size_t halves = entries * h->L * h->n * 2;
-    auto launch = [&](auto *limbs) {
-        using LimbT = std::remove_const_t<std::remove_pointer_t<decltype(limbs)>>;
-        hipLaunchKernelGGL((fhe_dev::lwe_pack_sum_kernel<LimbT>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (const V *)a0, (const V *)a1,
+    return with_limbs(h, [&](auto *limbs) {
+        hipLaunchKernelGGL((fhe_dev::lwe_pack_sum_kernel<limb_of<decltype(limbs)>>), dim3(ew_grid(halves)), dim3(256), 0, h->stream, (V *)o0, (V *)o1, (const V *)a0, (const V *)a1,
                            (const V *)b0, (const V *)b1, limbs, h->L, h->log_n, halves);
         return post_launch(h->stream, "lwe_pack_sum_kernel");
-    };
-    if (h->width == FHE_WIDTH_256) return launch((const fhe_dev::Limb256 *)h->d_limbs);
-    return with_word_field(h, [&](auto f) { return launch((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
-}
-
-// what every packing entry point checks of the engine and the sizes
-static int check_pack_engine(const fhe_rns_ntt *h, uint32_t batch, const char *what) {
-    int rc = check_call(h, batch, what); if (rc) return rc;
-    if (!word_sized_moduli(h)) return fail(FHE_ERR_UNSUPPORTED, std::string(what) + ": every modulus must be below 2^64");
-    if (h->n < 8) return fail(FHE_ERR_INVALID_ARG, std::string(what) + ": n must be at least 8");
-    return FHE_OK;
+    });
 }
 
 extern "C" int fhe_lwe_to_rlwe(fhe_rns_ntt_t *h, void *d_c0, void *d_c1, const uint64_t *d_lwe, uint32_t batch) {
-    int rc = check_pack_engine(h, batch, "lwe_to_rlwe"); if (rc) return rc;
+    int rc = check_word_call(h, batch, "lwe_to_rlwe", true); if (rc) return rc;
     if (!d_c0 || !d_c1 || !d_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: null argument");
     if ((rc = check_aligned({d_c0, d_c1}, "lwe_to_rlwe"))) return rc;
     if ((uintptr_t)d_lwe & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_to_rlwe: d_lwe must be 8-byte aligned");
@@ -106,9 +81,7 @@ struct PackShape {
 // count, batch and the key sets of a call: everything fhe_lwe_pack and fhe_lwe_pack_reserve check alike
 static int check_pack_shape(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch, const char *what, PackShape *S) {
     const std::string w(what);
-    if (!count || (count & (count - 1)) || count > h->n) return fail(FHE_ERR_INVALID_ARG, w + ": count must be a power of two in [1, n]");
-    if ((uint64_t)batch * count > 0xffffffffull) return fail(FHE_ERR_INVALID_ARG, w + ": batch * count overflows 32 bits");
-    if ((uint64_t)batch * count * h->L > 0x7fffffffull) return fail(FHE_ERR_INVALID_ARG, w + ": batch * count * num_primes too large");
+    if (int rc = check_count(h, count, batch, what)) return rc;
     while ((1u << S->k) < count) S->k++;
     S->first_trace = S->k + 1; S->last_trace = trace ? h->log_n : S->k;
     if (S->last_trace >= 1 && !gks) return fail(FHE_ERR_INVALID_ARG, w + ": null key-set array");
@@ -122,7 +95,7 @@ static int check_pack_shape(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, 
     S->galois_batch = S->k ? batch * (count / 2) : (S->last_trace ? batch : 0);
     return FHE_OK;
 }
-// bytes of d_pack for a call.  Fused: three regions of batch count S (S = L n 32; a region holds both components of batch count / 2
+// bytes of WS_PACK for a call.  Fused: three regions of batch count S (S = L n 32; a region holds both components of batch count / 2
 // ciphertexts), or the trace's pair alone for count = 1.  Composed: R (batch count ciphertexts), X, P, D (half as many each) and the shift words,
 // then, from a 16-byte boundary (composed_samples_at), the batch count samples that fhe_rlwe_pack extracts first: fhe_lwe_pack_reserve cannot know
 // which of the two entries follows, so the composed size covers both.
@@ -138,12 +111,12 @@ static size_t pack_bytes(const fhe_rns_ntt *h, const PackShape &S, uint32_t coun
     return 3 * bc * poly;
 }
 static int ensure_pack(fhe_rns_ntt *h, const PackShape &S, uint32_t count, uint32_t batch, bool composed) {
-    int rc = grow_ws(h, &h->d_pack, &h->pack_bytes, pack_bytes(h, S, count, batch, composed)); if (rc) return rc;
+    int rc = grow_ws(h, h->ws[WS_PACK], pack_bytes(h, S, count, batch, composed)); if (rc) return rc;
     return S.galois_batch ? ensure_need(h, need_apply_galois(h, S.galois_batch, S.K, S.packed)) : FHE_OK;
 }
 
 extern "C" int fhe_lwe_pack_reserve(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, uint32_t count, int trace, uint32_t batch) {
-    int rc = check_pack_engine(h, batch, "lwe_pack_reserve"); if (rc) return rc;
+    int rc = check_word_call(h, batch, "lwe_pack_reserve", true); if (rc) return rc;
     PackShape S;
     if ((rc = check_pack_shape(h, gks, count, trace, batch, "lwe_pack_reserve", &S))) return rc;
     return ensure_pack(h, S, count, batch, pack_composed_env());
@@ -163,7 +136,7 @@ static int pack_trace(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const 
 static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, const PackSource &src, uint32_t count,
                       uint32_t halvings, uint32_t batch) {
     const size_t poly = (size_t)h->L * h->n * 32, region = (size_t)batch * count * poly;
-    char *base = (char *)h->d_pack;
+    char *base = (char *)h->ws[WS_PACK].p;
     int rc;
     if (!S.k) {
         if ((rc = launch_embed<false>(h, d_out0, d_out1, nullptr, nullptr, src, 0, halvings, batch))) return rc;
@@ -193,7 +166,7 @@ static int pack_fused(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const 
 static int pack_composed(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, const PackShape &S, void *d_out0, void *d_out1, PackSource src, uint32_t count,
                          uint32_t halvings, uint32_t batch) {
     const size_t poly = (size_t)h->L * h->n * 32, bc = (size_t)batch * count, hb = bc / 2 * poly;
-    char *base = (char *)h->d_pack;
+    char *base = (char *)h->ws[WS_PACK].p;
     int rc;
     if (!src.lwe) {                                                             // fhe_rlwe_pack: the literal extraction at idx = 0 of every pair first
         uint64_t *samples = (uint64_t *)(base + composed_samples_at(h, S, count, batch));
@@ -228,7 +201,7 @@ static int pack_composed(fhe_rns_ntt *h, const fhe_relin_keys_t *const *gks, con
 
 extern "C" int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const uint64_t *d_lwe, uint32_t count, int trace,
                             int normalize, uint32_t batch) {
-    int rc = check_pack_engine(h, batch, "lwe_pack"); if (rc) return rc;
+    int rc = check_word_call(h, batch, "lwe_pack", true); if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_lwe) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: null argument");
     if ((rc = check_aligned({d_out0, d_out1}, "lwe_pack"))) return rc;
     if ((uintptr_t)d_lwe & 7) return fail(FHE_ERR_INVALID_ARG, "lwe_pack: d_lwe must be 8-byte aligned");
@@ -246,7 +219,7 @@ extern "C" int fhe_lwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks
 
 extern "C" int fhe_rlwe_pack(fhe_rns_ntt_t *h, const fhe_relin_keys_t *const *gks, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, uint32_t count,
                              int trace, int normalize, uint32_t batch) {
-    int rc = check_pack_engine(h, batch, "rlwe_pack"); if (rc) return rc;
+    int rc = check_word_call(h, batch, "rlwe_pack", true); if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1) return fail(FHE_ERR_INVALID_ARG, "rlwe_pack: null argument");
     if ((rc = check_aligned({d_out0, d_out1, d_c0, d_c1}, "rlwe_pack"))) return rc;
     PackShape S;

@@ -17,80 +17,55 @@ __device__ __forceinline__ uint64_t pk_halve(uint64_t a, uint64_t q, uint32_t k)
     for (uint32_t i = 0; i < k; i++) a = (a >> 1) + ((a & 1) ? (q >> 1) + 1 : 0);
     return a;
 }
-// coefficient x of c1 of the embedding of the sample row (a_0 .. a_{n-1}, b): a_0 at x = 0, -a_{n-x} elsewhere
-__device__ __forceinline__ uint64_t pk_embed_c1(const uint64_t *__restrict__ row, uint32_t x, uint32_t n, uint64_t q) {
-    const uint64_t v = __builtin_nontemporal_load(row + ((n - x) & (n - 1)));
-    return x ? pk_neg(v, q) : v;
-}
-
-// PAIR = false: the embedding of `entries` samples, (o0, o1) = (c0, c1), times 2^-halvings.  lwe is [entries][L][n + 1].
-// PAIR = true : the first merge level straight from the samples.  Output entry e = b half + r (r < half) pairs sample b 2 half + r (E)
-//   with sample b 2 half + r + half (O); with m = n / 2:  (o0, o1) = P = E + X^m O,  (d0, d1) = D = E - X^m O, all [entries][L][n]
-//   containers.  c0 of an embedding is the constant b, so P0 / D0 are zero except at x = 0 (b_E) and x = m (+- b_O); c1 is two reversed
-//   contiguous runs of the sample rows (descending 8-byte loads: the same whole cache lines as ascending ones).
-template <class LimbT, bool PAIR>
-__global__ void __launch_bounds__(256)
-lwe_embed_merge_kernel(v2u64 *__restrict__ o0, v2u64 *__restrict__ o1, v2u64 *__restrict__ d0, v2u64 *__restrict__ d1, const uint64_t *__restrict__ lwe,
-                       const LimbT *__restrict__ limbs, uint32_t half, uint32_t halvings, uint32_t L, uint32_t log_n, size_t halves /* entries L n 2 */) {
-    const uint32_t n = 1u << log_n, m = n >> 1;
-    const size_t stride = (size_t)gridDim.x * blockDim.x, row_len = (size_t)n + 1;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < halves; g += stride) {
-        uint64_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
-        if (!(g & 1)) {
-            const size_t c = g >> 1, poly = c >> log_n, e = poly / L;            // container, polynomial e L + l, output entry
-            const uint32_t x = (uint32_t)(c & (n - 1)), l = (uint32_t)(poly - e * L);
-            const uint64_t q = limb_q64(limbs[l]);
-            const size_t se = PAIR ? (e / half) * 2 * half + e % half : e;      // sample of E
-            const uint64_t *rowE = lwe + (se * L + l) * row_len;
-            const uint64_t e1 = pk_halve(pk_embed_c1(rowE, x, n, q), q, halvings);
-            const uint64_t e0 = x ? 0 : pk_halve(__builtin_nontemporal_load(rowE + n), q, halvings);
-            if (PAIR) {
-                const uint64_t *rowO = lwe + ((se + half) * L + l) * row_len;
-                const uint32_t y = (x - m) & (n - 1);                            // (X^m O)[x] = O[x - m], negated where x < m
-                uint64_t r1 = pk_halve(pk_embed_c1(rowO, y, n, q), q, halvings);
-                uint64_t r0 = y ? 0 : pk_halve(__builtin_nontemporal_load(rowO + n), q, halvings);
-                if (x < m) { r1 = pk_neg(r1, q); r0 = pk_neg(r0, q); }
-                p0 = pk_add(e0, r0, q); p1 = pk_add(e1, r1, q);
-                q0 = pk_sub(e0, r0, q); q1 = pk_sub(e1, r1, q);
-            } else { p0 = e0; p1 = e1; }
-        }
-        const v2u64 a = {p0, 0ull}, b = {p1, 0ull};
-        __builtin_nontemporal_store(a, o0 + g);
-        __builtin_nontemporal_store(b, o1 + g);
-        if (PAIR) {
-            const v2u64 c = {q0, 0ull}, d = {q1, 0ull};
-            __builtin_nontemporal_store(c, d0 + g);
-            __builtin_nontemporal_store(d, d1 + g);
-        }
+// What the embedding reads.  A source gives, of input entry se and limb l -- at(se L + l, ...) says where that is -- c1 of the embedded
+// ciphertext at coefficient x, and the constant b that is its c0; each source keeps its own load flavour.
+// SampleRows: LWE samples, lwe is [entries][L][n + 1], a row (a_0 .. a_{n-1}, b).  c1 is a_0 at x = 0 and -a_{n-x} elsewhere: a reversed
+// contiguous run of the row (descending 8-byte loads: the same whole cache lines as ascending ones).
+struct SampleRows {
+    const uint64_t *lwe;
+    __device__ __forceinline__ const uint64_t *at(size_t poly, uint32_t n, uint32_t) const { return lwe + poly * ((size_t)n + 1); }
+    __device__ __forceinline__ uint64_t c1(const uint64_t *row, uint32_t x, uint32_t n, uint64_t q) const {
+        const uint64_t v = __builtin_nontemporal_load(row + ((n - x) & (n - 1)));
+        return x ? pk_neg(v, q) : v;
     }
-}
+    __device__ __forceinline__ uint64_t b(const uint64_t *row, uint32_t n) const { return __builtin_nontemporal_load(row + n); }
+};
+// RlwePairs: coefficient 0 of RLWE pairs (fhe_rlwe_pack), in0, in1 are [entries][L][n] containers.  Extraction at idx = 0 followed by the embedding
+// is the identity on c1 and keeps c0[0] alone, so c1 is read in place, ascending and not negated, and c0 contributes its container 0: the bits
+// of SampleRows on the extracted samples, which are never written.  The rest of c0 is not read.
+struct RlwePairs {
+    const v2u64 *in0, *in1;
+    __device__ __forceinline__ size_t at(size_t poly, uint32_t, uint32_t log_n) const { return (poly << log_n) * 2; }   // container 0 of the polynomial, in halves
+    __device__ __forceinline__ uint64_t c1(size_t at, uint32_t x, uint32_t, uint64_t) const { return __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in1 + at + (size_t)(2 * x))); }   // x < n <= 2^31
+    __device__ __forceinline__ uint64_t b(size_t at, uint32_t) const { return __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in0 + at)); }
+};
 
-// The same two forms straight from RLWE pairs (fhe_rlwe_pack): in0, in1 are [entries or 2 entries][L][n] containers, and what is packed is
-// coefficient 0 of each pair.  Extraction at idx = 0 followed by the embedding is the identity on c1 and keeps c0[0] alone, so c1 is read in
-// place, ascending and not negated, and c0 contributes its container 0: the bits of lwe_embed_merge_kernel on the extracted samples, which are
-// never written.  The rest of c0 is not read.
-template <class LimbT, bool PAIR>
+// PAIR = false: the embedding of `entries` inputs of the source, (o0, o1) = (c0, c1), times 2^-halvings.
+// PAIR = true : the first merge level straight from the source.  Output entry e = b half + r (r < half) pairs input b 2 half + r (E)
+//   with input b 2 half + r + half (O); with m = n / 2:  (o0, o1) = P = E + X^m O,  (d0, d1) = D = E - X^m O, all [entries][L][n]
+//   containers.  c0 of an embedding is the constant b, so P0 / D0 are zero except at x = 0 (b_E) and x = m (+- b_O).
+template <class LimbT, class Source, bool PAIR, class... In>
 __global__ void __launch_bounds__(256)
-rlwe_embed_merge_kernel(v2u64 *__restrict__ o0, v2u64 *__restrict__ o1, v2u64 *__restrict__ d0, v2u64 *__restrict__ d1, const v2u64 *__restrict__ in0,
-                        const v2u64 *__restrict__ in1, const LimbT *__restrict__ limbs, uint32_t half, uint32_t halvings, uint32_t L, uint32_t log_n,
-                        size_t halves /* entries L n 2 */) {
+embed_merge_kernel(v2u64 *__restrict__ o0, v2u64 *__restrict__ o1, v2u64 *__restrict__ d0, v2u64 *__restrict__ d1, const In *__restrict__... in,
+                   const LimbT *__restrict__ limbs, uint32_t half, uint32_t halvings, uint32_t L, uint32_t log_n, size_t halves /* entries L n 2 */) {
     const uint32_t n = 1u << log_n, m = n >> 1;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const Source src{in...};
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < halves; g += stride) {
         uint64_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
         if (!(g & 1)) {
             const size_t c = g >> 1, poly = c >> log_n, e = poly / L;            // container, polynomial e L + l, output entry
             const uint32_t x = (uint32_t)(c & (n - 1)), l = (uint32_t)(poly - e * L);
             const uint64_t q = limb_q64(limbs[l]);
-            const size_t se = PAIR ? (e / half) * 2 * half + e % half : e;      // input pair of E
-            const size_t atE = ((se * L + l) << log_n) * 2;                      // its container 0, in halves
-            const uint64_t e1 = pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in1 + atE + (size_t)x * 2)), q, halvings);
-            const uint64_t e0 = x ? 0 : pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in0 + atE)), q, halvings);
+            const size_t se = PAIR ? (e / half) * 2 * half + e % half : e;      // input entry of E
+            const auto E = src.at(se * L + l, n, log_n);
+            const uint64_t e1 = pk_halve(src.c1(E, x, n, q), q, halvings);
+            const uint64_t e0 = x ? 0 : pk_halve(src.b(E, n), q, halvings);
             if (PAIR) {
-                const size_t atO = (((se + half) * L + l) << log_n) * 2;
+                const auto O = src.at((se + half) * L + l, n, log_n);
                 const uint32_t y = (x - m) & (n - 1);                            // (X^m O)[x] = O[x - m], negated where x < m
-                uint64_t r1 = pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in1 + atO + (size_t)y * 2)), q, halvings);
-                uint64_t r0 = y ? 0 : pk_halve(__builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(in0 + atO)), q, halvings);
+                uint64_t r1 = pk_halve(src.c1(O, y, n, q), q, halvings);
+                uint64_t r0 = y ? 0 : pk_halve(src.b(O, n), q, halvings);
                 if (x < m) { r1 = pk_neg(r1, q); r0 = pk_neg(r0, q); }
                 p0 = pk_add(e0, r0, q); p1 = pk_add(e1, r1, q);
                 q0 = pk_sub(e0, r0, q); q1 = pk_sub(e1, r1, q);

@@ -96,7 +96,7 @@ static int run256_ew(fhe_rns_ntt *h, void *r, const void *a, const void *b, uint
 
 // ---- LDS-resident path launchers (kernels live in lds_inst.hip, one object per (field, log2 n)) ---------
 // Two-pass transforms of the word-sized classes (log2 n = 13 + sub_top): one launch of the LOGN = 13 instance per pass.  Between the
-// two launches the polynomials are COMPACT (sizeof(residue) bytes per coefficient, d_ws3); *_compact tell which pointers are.
+// two launches the polynomials are COMPACT (sizeof(residue) bytes per coefficient, WS3); *_compact tell which pointers are.
 int lds_launch(fhe_rns_ntt *h, const fhe_dev::LdsArgs &A, const char *what, int log_n) {
     if (!log_n) log_n = (int)h->log_n;
     fhe_dev::lds_launch_fn fn = fhe_dev::lds_lookup(lds_width_id(h), log_n);
@@ -127,13 +127,13 @@ static int lds_big(fhe_rns_ntt *h, int op, void *dst, bool dst_compact, const vo
 WsNeed need_transform(const fhe_rns_ntt *h, size_t polys) { return {0, 0, h->sub_top ? polys * h->n * residue_bytes(h) : 0}; }
 static int big_forward(fhe_rns_ntt *h, void *dst, const void *src, uint32_t polys) {
     int rc = ensure_need(h, need_transform(h, polys)); if (rc) return rc;
-    if ((rc = lds_big(h, fhe_dev::LDS_PASS_FWD, h->d_ws3, true, src, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
-    return lds_big(h, fhe_dev::LDS_SUB_FORWARD, dst, false, h->d_ws3, true, nullptr, polys, false, "ntt_sub_kernel");
+    if ((rc = lds_big(h, fhe_dev::LDS_PASS_FWD, h->ws[WS3].p, true, src, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
+    return lds_big(h, fhe_dev::LDS_SUB_FORWARD, dst, false, h->ws[WS3].p, true, nullptr, polys, false, "ntt_sub_kernel");
 }
 static int big_inverse(fhe_rns_ntt *h, void *data, uint32_t polys) {
     int rc = ensure_need(h, need_transform(h, polys)); if (rc) return rc;
-    if ((rc = lds_big(h, fhe_dev::LDS_SUB_INVERSE, h->d_ws3, true, data, false, nullptr, polys, false, "ntt_sub_kernel"))) return rc;
-    return lds_big(h, fhe_dev::LDS_PASS_INV, data, false, h->d_ws3, true, nullptr, polys, false, "word_pass_kernel");
+    if ((rc = lds_big(h, fhe_dev::LDS_SUB_INVERSE, h->ws[WS3].p, true, data, false, nullptr, polys, false, "ntt_sub_kernel"))) return rc;
+    return lds_big(h, fhe_dev::LDS_PASS_INV, data, false, h->ws[WS3].p, true, nullptr, polys, false, "word_pass_kernel");
 }
 
 // ---- kernel forms of the LDS-resident ops (LdsPlan: engine.h) ---------------------------------------------------------------
@@ -215,7 +215,7 @@ bool plan_fused_slots(const fhe_rns_ntt *te) {
 // (ciphertext, limb): L times the workgroups for a device that the ciphertexts alone do not fill.  Same kernel, same bits.
 bool plan_encrypt_per_ct(const fhe_rns_ntt *h, uint32_t batch) { return h->L > 1 && batch >= h->env.encrypt_per_ct_batch; }
 // Key switch of `polys` limb polynomials with K digits (KsSource: engine.h).  alone: no other chunk of the call runs beside it (the
-// few-ciphertext parts take d_ws).
+// few-ciphertext parts take WS1).
 LdsPlan plan_keyswitch(const fhe_rns_ntt *h, size_t polys, uint32_t K, KsSource src, bool alone) {
     const int eb = (int)residue_bytes(h), ln = (int)h->log_n;
     const bool joint3 = use_joint3(h, false, src == KS_FUSED);
@@ -343,7 +343,7 @@ static int wide_multiply_t(fhe_rns_ntt *h, void *d_r, const void *d_a, const voi
     const u256 *A = (const u256 *)d_a, *B = (const u256 *)d_b;
     if (!h->log_n) return run256_ew<0>(h, d_r, d_a, d_b, polys, "pointwise");     // degree 1: the product in Z_q
     if (top) {
-        u256 *wa = (u256 *)h->d_ws, *wb = (u256 *)((char *)h->d_ws + bytes);
+        u256 *wa = (u256 *)h->ws[WS1].p, *wb = (u256 *)((char *)h->ws[WS1].p + bytes);
         wide_forward_top<NL>(h, wa, A, polys);
         if (d_b != d_a) wide_forward_top<NL>(h, wb, B, polys);
         B = d_b != d_a ? wb : wa; A = wa;
@@ -363,7 +363,7 @@ static int wide_ct_multiply_t(fhe_rns_ntt *h, void *c0, void *c1, void *c2, cons
     using fhe_dev::u256;
     // 4 forward transforms into the workspace (no copies), one pass for the three NTT-domain products, 3 inverse transforms
     const size_t bytes = (size_t)polys * h->n * 32;
-    char *ws = (char *)h->d_ws;
+    char *ws = (char *)h->ws[WS1].p;
     const void *src[4] = {a0, a1, b0, b1};
     int rc;
     for (int i = 0; i < 4; i++)
@@ -395,7 +395,7 @@ static int do_multiply(fhe_rns_ntt *h, void *d_r, const void *d_a, const void *d
     // workgroup loads both of its operand polynomials completely before its first store, and the general path works on copies.
     if (h->sub_top) {   // two-pass: the top stages of both operands go to the COMPACT workspace, one fused launch over the 2^13 blocks (compact in and out), last pass into the result
         const size_t cbytes = (size_t)polys * h->n * residue_bytes(h);
-        char *wa = (char *)h->d_ws3, *wb = d_b != d_a ? wa + cbytes : wa;
+        char *wa = (char *)h->ws[WS3].p, *wb = d_b != d_a ? wa + cbytes : wa;
         if ((rc = lds_big(h, fhe_dev::LDS_PASS_FWD, wa, true, d_a, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
         if (d_b != d_a && (rc = lds_big(h, fhe_dev::LDS_PASS_FWD, wb, true, d_b, false, nullptr, polys, false, "word_pass_kernel"))) return rc;
         if ((rc = lds_big(h, fhe_dev::LDS_SUB_MULTIPLY, wa, true, wa, true, wb, polys, false, "ntt_sub_kernel"))) return rc;
@@ -410,7 +410,7 @@ int do_ct_multiply(fhe_rns_ntt *h, void *c0, void *c1, void *c2, const void *a0,
     int rc = ensure_need(h, need_ct_multiply(h, batch, a0 == b0 && a1 == b1)); if (rc) return rc;
     if (h->sub_top) {   // 4 forward transforms into the workspace, NTT-domain products on the field type, 3 inverse transforms
         const size_t bytes = (size_t)polys * h->n * 32;
-        char *ws = (char *)h->d_ws, *T = ws + 4 * bytes;
+        char *ws = (char *)h->ws[WS1].p, *T = ws + 4 * bytes;
         const void *src[4] = {a0, a1, b0, b1};
         for (int i = 0; i < 4; i++) if ((rc = big_forward(h, ws + i * bytes, src[i], polys))) return rc;
         if ((rc = do_ew<0>(h, c0, ws, ws + 2 * bytes, batch, "ct pointwise"))) return rc;

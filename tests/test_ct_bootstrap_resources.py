@@ -1,6 +1,6 @@
 """CPU test (hipcc cross-compiles without a GPU): the streaming kernels of FHEContext::bootstrap(Ciphertext&) -- the strided sample extraction
-and the first packing level from RLWE pairs -- use no scratch memory and spill nothing, on both limb-table types.  The remarks are parsed with
-the helper of test_kernel_resources.py."""
+and the embedding / first packing level from either source (RLWE pairs, sample rows) -- use no scratch memory and spill nothing, on both
+limb-table types.  The remarks are parsed with the helper of test_kernel_resources.py."""
 import os
 import subprocess
 
@@ -12,8 +12,10 @@ SRC = """#include "lwe_pack.hip.h"
 using namespace fhe_dev;
 #define INST(T) \\
     template __global__ void fhe_dev::sample_extract_strided_kernel<T>(uint64_t*, const v2u64*, const v2u64*, const T*, uint32_t, uint32_t, uint32_t, uint32_t, size_t); \\
-    template __global__ void fhe_dev::rlwe_embed_merge_kernel<T, false>(v2u64*, v2u64*, v2u64*, v2u64*, const v2u64*, const v2u64*, const T*, uint32_t, uint32_t, uint32_t, uint32_t, size_t); \\
-    template __global__ void fhe_dev::rlwe_embed_merge_kernel<T, true>(v2u64*, v2u64*, v2u64*, v2u64*, const v2u64*, const v2u64*, const T*, uint32_t, uint32_t, uint32_t, uint32_t, size_t);
+    EMBED(T, false) EMBED(T, true)
+#define EMBED(T, PAIR) \\
+    template __global__ void fhe_dev::embed_merge_kernel<T, RlwePairs, PAIR, v2u64, v2u64>(v2u64*, v2u64*, v2u64*, v2u64*, const v2u64*, const v2u64*, const T*, uint32_t, uint32_t, uint32_t, uint32_t, size_t); \\
+    template __global__ void fhe_dev::embed_merge_kernel<T, SampleRows, PAIR, uint64_t>(v2u64*, v2u64*, v2u64*, v2u64*, const uint64_t*, const T*, uint32_t, uint32_t, uint32_t, uint32_t, size_t);
 INST(Limb<F32>) INST(Limb<F64X>) INST(Limb256)
 """
 
@@ -29,7 +31,7 @@ def kernels(tmp_path_factory):
     return _parse(res.stderr)[0]
 
 
-@pytest.mark.parametrize("needle,instances", [("sample_extract_strided_kernel", 3), ("rlwe_embed_merge_kernel", 6)])
+@pytest.mark.parametrize("needle,instances", [("sample_extract_strided_kernel", 3), ("embed_merge_kernel", 12)])
 def test_the_new_streaming_kernels_use_no_scratch(kernels, needle, instances):
     hits = {k: v for k, v in kernels.items() if needle in k}
     assert len(hits) == instances, (needle, sorted(kernels))

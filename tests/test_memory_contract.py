@@ -582,7 +582,7 @@ def test_large_then_small_then_other_forms_on_one_engine(eng, oracle, reserve):
 
 
 def test_two_pass_transforms_share_one_workspace(eng, oracle):
-    """N = 65536: multiply at batch 2 (two compact operands per polynomial in d_ws3), then forward at batch 1 and inverse at batch 2 on what it left."""
+    """N = 65536: multiply at batch 2 (two compact operands per polynomial in the workspace WS3), then forward at batch 1 and inverse at batch 2 on what it left."""
     n = 65536
     moduli = _primes(30, n, 1)
     R = _transform_ref(oracle, 30, 1, n, 2)
