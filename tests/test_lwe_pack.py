@@ -79,22 +79,25 @@ CASES = ([(2048, 30, c, tr, nz, b) for c in (1, 2, 8) for tr in (0, 1) for nz in
 _ctx, _fused = {}, {}
 
 
-def _context(pkg, n, bits):
-    """engine, ternary ring key and the log2(n) Galois key sets of 2^j + 1, once per (n, bits)"""
-    if (n, bits) not in _ctx:
-        moduli = _primes(bits, n, 2)
+def _context(pkg, n, bits, moduli=None, w=None):
+    """engine, ternary ring key and the log2(n) Galois key sets of 2^j + 1, once per (n, moduli, w); by default the two primes of `bits` bits and
+    the digit width W_OF[bits]"""
+    moduli = list(moduli) if moduli is not None else _primes(bits, n, 2)
+    w = W_OF[bits] if w is None else w
+    key = (n, tuple(moduli), w)
+    if key not in _ctx:
         eng = pkg.RnsNttEngine(n, moduli)
         s = np.random.default_rng(9).integers(-1, 2, n).astype(object)
         ds = pkg.DeviceBuffer.from_numpy(_embed(s[None], moduli)[0])
         sk = eng.import_secret_key(ds)
-        keys = eng.generate_keyswitch_keys(sk, W_OF[bits], pkg.capi.lwe_pack_galois_elements(n), 1, SIGMA, KEY_SEEDS)
-        _ctx[(n, bits)] = dict(moduli=moduli, eng=eng, keep=(ds, sk), keys=keys, s=s)
-    return _ctx[(n, bits)]
+        keys = eng.generate_keyswitch_keys(sk, w, pkg.capi.lwe_pack_galois_elements(n), 1, SIGMA, KEY_SEEDS)
+        _ctx[key] = dict(moduli=moduli, eng=eng, keep=(ds, sk), keys=keys, s=s, w=w)
+    return _ctx[key]
 
 
-def _case_samples(case):
+def _case_samples(case, moduli=None):
     n, bits, count, trace, normalize, batch = case
-    return _samples(_primes(bits, n, 2), n, batch * count, 100 + count + 7 * batch)
+    return _samples(moduli if moduli is not None else _primes(bits, n, 2), n, batch * count, 100 + count + 7 * batch)
 
 
 def _pack(pkg, case, reserve=False):
@@ -117,13 +120,14 @@ def _fused_result(pkg, case):
     return _fused[case]
 
 
-def _compose(pkg, case):
+def _compose(pkg, case, moduli=None, w=None, lwe=None):
     """The definition through capi: fhe_lwe_to_rlwe, then per level fhe_rns_monomial_mul_sub + fhe_rns_poly_add (X^m O), poly_add / poly_sub (P, D),
-    fhe_ct_apply_galois (G) and poly_add (P + G); then the trace.  F^-1 is applied in numpy before the upload."""
+    fhe_ct_apply_galois (G) and poly_add (P + G); then the trace.  F^-1 is applied in numpy before the upload.  moduli, w: another context than
+    the case's bits name (any number of limbs); lwe: other samples than _case_samples, [batch count][L][n + 1]."""
     n, bits, count, trace, normalize, batch = case
-    C = _context(pkg, n, bits)
-    eng, moduli, keys, L = C["eng"], C["moduli"], C["keys"], 2
-    lwe = _case_samples(case)
+    C = _context(pkg, n, bits, moduli, w)
+    eng, moduli, keys, L = C["eng"], C["moduli"], C["keys"], len(C["moduli"])
+    lwe = _case_samples(case, moduli) if lwe is None else lwe
     if normalize:
         F = n if trace else count
         lwe = np.stack([((lwe[:, l].astype(object) * pow(F, -1, q)) % q).astype(np.uint64) for l, q in enumerate(moduli)], axis=1)

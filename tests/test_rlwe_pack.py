@@ -24,10 +24,11 @@ CASES = ([(64, 30, 64, 0, 1, 2), (64, 30, 64, 0, 0, 1)]
 _fused = {}
 
 
-def _pairs(case, other_c0=False):
-    """[batch count][L][n][4] pairs with 0 and q - 1 among the values read; other_c0: the same c0[.][0] and c1, every other coefficient of c0 changed"""
+def _pairs(case, other_c0=False, moduli=None):
+    """[batch count][L][n][4] pairs with 0 and q - 1 among the values read; other_c0: the same c0[.][0] and c1, every other coefficient of c0 changed;
+    moduli: another basis than the two primes the case's bits name"""
     n, bits, count, trace, normalize, batch = case
-    moduli, entries = _primes(bits, n, L), batch * count
+    moduli, entries = (list(moduli) if moduli is not None else _primes(bits, n, L)), batch * count
     c0, c1 = rns_poly(300 + count + 7 * batch, moduli, n, entries), rns_poly(301 + count + 7 * batch, moduli, n, entries)
     c1[:, :, 0, 0] = 0; c1[0, :, n // 2, 0] = 0; c0[0, :, 0, 0] = 0
     for l, q in enumerate(moduli):
