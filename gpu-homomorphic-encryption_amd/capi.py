@@ -155,6 +155,15 @@ def lib():
         "fhe_ckks_encode": ([vp, vp, vp, vp, vp, ctypes.c_double, u32], ci),
         "fhe_ckks_decode": ([vp, vp, vp, vp, u64, ctypes.c_double, u32], ci),
         "fhe_ckks_decode_poly": ([vp, vp, vp, vp, ctypes.c_double, u32], ci),
+        "fhe_bfv_multiplier_create": ([vp, P(vp), u64, P(u64), u32], ci),
+        "fhe_bfv_multiplier_destroy": ([vp], ci),
+        "fhe_bfv_multiplier_engine": ([vp, P(vp)], ci),
+        "fhe_bfv_multiplier_reserve": ([vp, u32, vp], ci),
+        "fhe_bfv_multiplier_workspace_bytes": ([vp, P(u64)], ci),
+        "fhe_bfv_lift": ([vp, vp, vp, u32], ci),
+        "fhe_bfv_scale_round": ([vp, P(vp), P(vp), u32, u32], ci),
+        "fhe_bfv_multiply": ([vp, vp, vp, vp, vp, vp, vp, vp, u32], ci),
+        "fhe_bfv_multiply_relin": ([vp, vp, vp, vp, vp, vp, vp, vp, u32], ci),
         "fhe_timer_create": ([P(vp)], ci),
         "fhe_timer_destroy": ([vp], ci),
         "fhe_rns_timer_start": ([vp, vp], ci),
@@ -383,7 +392,14 @@ class RnsNttEngine:
             _check(lib().fhe_rns_base_create(ctypes.byref(h), ctypes.cast(arr, ctypes.c_void_p), L)); n = 1
         else:
             _check(lib().fhe_rns_ntt_create(ctypes.byref(h), n, ctypes.cast(arr, ctypes.c_void_p), L))
-        self.h, self.n, self.L, self.moduli = h, n, L, list(moduli)
+        self.h, self.n, self.L, self.moduli, self.borrowed = h, n, L, list(moduli), False
+
+    @classmethod
+    def _borrow(cls, handle, n, moduli):
+        """A view of an engine that another object owns (the extended engine of a BfvMultiplier): close() lets go of it without destroying it."""
+        e = cls.__new__(cls)
+        e.h, e.n, e.L, e.moduli, e.borrowed = handle, n, len(moduli), list(moduli), True
+        return e
 
     @property
     def width_class(self):
@@ -667,7 +683,9 @@ class RnsNttEngine:
 
     def close(self):
         if self.h:
-            lib().fhe_rns_ntt_destroy(self.h); self.h = None
+            if not self.borrowed:                         # (the extended engine of a BfvMultiplier belongs to the multiplier)
+                lib().fhe_rns_ntt_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:
@@ -847,6 +865,63 @@ class CkksEncoder:
     def close(self):
         if self.h:
             lib().fhe_ckks_encoder_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BfvMultiplier:
+    """BFV multiplication on the engine `eng` (primes Q) for the plaintext modulus t: an extended engine on Q u P (P = the auxiliary NTT
+    primes `aux_moduli`, of the same size as eng's, with P > 32 t n Q), the exact centred lift Q -> Q u P and scale-and-round by t / Q."""
+
+    def __init__(self, eng, t, aux_moduli):
+        self.h = None
+        self.eng = eng
+        aux = (ctypes.c_uint64 * max(len(aux_moduli), 1))(*[int(p) for p in aux_moduli])
+        out = ctypes.c_void_p()
+        _check(lib().fhe_bfv_multiplier_create(eng.h, ctypes.byref(out), t, aux, len(aux_moduli)))
+        self.h, self.t, self.aux_moduli = out, t, [int(p) for p in aux_moduli]
+        e = ctypes.c_void_p()
+        _check(lib().fhe_bfv_multiplier_engine(self.h, ctypes.byref(e)))
+        self._qp = RnsNttEngine._borrow(e, eng.n, list(eng.moduli) + self.aux_moduli)
+
+    @property
+    def engine(self):
+        """The borrowed engine on Q u P (valid while the multiplier lives): tensor products of your own, scaled once by scale_round."""
+        return self._qp
+
+    def reserve(self, batch, rk=None):
+        """Pre-size every workspace of multiply (and, with a key set, multiply_relin) for up to `batch` ciphertexts: afterwards no call allocates."""
+        _check(lib().fhe_bfv_multiplier_reserve(self.h, batch, None if rk is None else rk.h))
+
+    def workspace_bytes(self):
+        b = ctypes.c_uint64(0); _check(lib().fhe_bfv_multiplier_workspace_bytes(self.h, ctypes.byref(b))); return b.value
+
+    def lift(self, d_out, d_in, batch=1):
+        """[batch][L][n] -> [batch][L + L'][n]: the Q limbs copied, the P limbs from the centred lift."""
+        _check(lib().fhe_bfv_lift(self.h, _ptr(d_out), _ptr(d_in), batch))
+
+    def scale_round(self, outs, ins, batch=1):
+        """round(t x / Q) of 1 to 3 components `ins` ([batch][L + L'][n] each) into `outs` ([batch][L][n]), one launch."""
+        arr = lambda xs: (ctypes.c_void_p * max(len(xs), 1))(*[None if x is None else _ptr(x) for x in xs])   # None: a null pointer (rejected)
+        po, pi = arr(outs), arr(ins)
+        _check(lib().fhe_bfv_scale_round(self.h, po, pi, len(ins), batch))
+
+    def multiply(self, d_c0, d_c1, d_c2, d_a0, d_a1, d_b0, d_b1, batch=1):
+        """(c0, c1, c2) = round(t / Q (a (x) b)) with the tensor product over the integers."""
+        _check(lib().fhe_bfv_multiply(self.h, _ptr(d_c0), _ptr(d_c1), _ptr(d_c2), _ptr(d_a0), _ptr(d_a1), _ptr(d_b0), _ptr(d_b1), batch))
+
+    def multiply_relin(self, rk, d_c0, d_c1, d_a0, d_a1, d_b0, d_b1, batch=1):
+        """multiply followed by the relinearisation of c2 with the key set rk of eng: two components out."""
+        _check(lib().fhe_bfv_multiply_relin(self.h, rk.h, _ptr(d_c0), _ptr(d_c1), _ptr(d_a0), _ptr(d_a1), _ptr(d_b0), _ptr(d_b1), batch))
+
+    def close(self):
+        if self.h:
+            self._qp.h = None
+            lib().fhe_bfv_multiplier_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

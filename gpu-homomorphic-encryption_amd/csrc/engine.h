@@ -24,9 +24,11 @@
 //   lwe_pack.hip    the way back: LWE samples under the ring key into one RLWE ciphertext, merge levels and trace around fhe_ct_apply_galois
 //                   (lwe_pack.hip.h)
 //   rns.hip         CRT tables, to / from RNS, rescale, BGV modulus switch, base conversion (ntt256_rns.hip.h; conversion kernels of ntt_word.hip.h)
+//   bfv.hip         BFV multiplication: the multiplier object (an owned engine on Q u P, the conversion tables, one workspace), centred lift,
+//                   scale-and-round, the one-call product around do_ct_multiply and fhe_ct_relinearize (bfv.hip.h)
 // Every kernel (template instantiations included) is launched, and therefore compiled, by its owning source only.
 // What they share is written once, here: overlaps (the byte-range test), with_word_field / with_limbs (width class -> field type / typed limb
-// table), check_word_call and check_count (the engine and (count, batch) rules of the entry points around the blind rotation), and the
+// table), word_operand / inv_mod_u64 (the constants of the streaming conversion kernels), check_word_call and check_count (the engine and (count, batch) rules of the entry points around the blind rotation), and the
 // workspace table (WsId, Workspace, grow_ws).
 #pragma once
 #include "../../include/fhe_hip.h"
@@ -199,6 +201,21 @@ template <class Fn>
 int with_limbs(const fhe_rns_ntt *h, Fn &&fn) {
     if (h->width == FHE_WIDTH_256) return fn((const fhe_dev::Limb256 *)h->d_limbs);
     return with_word_field(h, [&](auto f) { return fn((const fhe_dev::Limb<decltype(f)> *)h->d_limbs); });
+}
+// "pw operand" of the constant c for limb modulus q of a word-sized class: c * 2^W mod q for the integer fields (so that the
+// Montgomery product with it is the plain product), c itself for the FP64 field
+template <class F> inline typename F::E word_operand(uint64_t c, uint64_t q) {
+    using E = typename F::E;
+    if (std::is_same<F, fhe_dev::F52>::value) return (E)c;
+    const unsigned W = 8 * sizeof(E);
+    fhe_host::u128 v = (fhe_host::u128)(c % q);
+    for (unsigned k = 0; k < W; k++) v = (v << 1) % q;
+    return (E)(uint64_t)v;
+}
+inline uint64_t inv_mod_u64(uint64_t a, uint64_t q) {       // a^(q-2) mod q, q prime
+    fhe_host::u128 acc = 1, b = a % q; uint64_t e = q - 2;
+    for (; e; e >>= 1) { if (e & 1) acc = acc * b % q; b = b * b % q; }
+    return (uint64_t)acc;
 }
 // every modulus below 2^64: a word-sized class, or FHE_WIDTH_256 chosen for the SIZE (n < 2^11 has no word-sized kernels), not for a wide modulus
 inline bool word_sized_moduli(const fhe_rns_ntt *h) {

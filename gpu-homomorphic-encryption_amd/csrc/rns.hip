@@ -52,21 +52,6 @@ int ensure_crt(fhe_rns_ntt *h) {
     h->crt_state = fits ? 1 : -1;
     return FHE_OK;
 }
-// "pw operand" of the constant c for limb modulus q of a word-sized class: c * 2^W mod q for the integer fields (so that the
-// Montgomery product with it is the plain product), c itself for the FP64 field
-template <class F> static typename F::E word_operand(uint64_t c, uint64_t q) {
-    using E = typename F::E;
-    if (std::is_same<F, fhe_dev::F52>::value) return (E)c;
-    const unsigned W = 8 * sizeof(E);
-    fhe_host::u128 v = (fhe_host::u128)(c % q);
-    for (unsigned k = 0; k < W; k++) v = (v << 1) % q;
-    return (E)(uint64_t)v;
-}
-static uint64_t inv_mod_u64(uint64_t a, uint64_t q) {       // a^(q-2) mod q, q prime
-    fhe_host::u128 acc = 1, b = a % q; uint64_t e = q - 2;
-    for (; e; e >>= 1) { if (e & 1) acc = acc * b % q; b = b * b % q; }
-    return (uint64_t)acc;
-}
 template <class F>
 static int to_rns_word(fhe_rns_ntt *h, void *d_rns, const void *d_values, uint32_t batch) {
     using E = typename F::E; using V = typename F::V16;

@@ -103,6 +103,21 @@ struct PackingKeys {
     ~PackingKeys() { clear(); }
 };
 
+// The engine-side object of FHEContext::multiply_bfv (fhe_bfv_multiplier_create): the extended engine on Q u P and the tables of the exact
+// lift and scale-and-round, for the context's level-0 basis and plaintext modulus.  FHEContext::bfv_multiplier_gen fills it; the context keeps
+// one of its own for multiply_bfv.  Destroy it before the context.
+struct BFVMultiplier {
+    fhe_bfv_multiplier_t *handle = nullptr;
+    std::vector<uint64_t> aux_moduli;      // the auxiliary primes P it was made with
+    uint64_t t = 0;
+    const void *made_for = nullptr;        // the engine whose multiplier this is
+    BFVMultiplier() = default;
+    BFVMultiplier(const BFVMultiplier &) = delete;
+    BFVMultiplier &operator=(const BFVMultiplier &) = delete;
+    void clear() { fhe_bfv_multiplier_destroy(handle); handle = nullptr; aux_moduli.clear(); made_for = nullptr; }
+    ~BFVMultiplier() { clear(); }
+};
+
 struct Plaintext {                                            // include/fhe.cuh:72-75
     Polynomial *poly = nullptr;
     bool is_ntt_form = false;
@@ -143,7 +158,7 @@ public:
     }
     // Explicit RNS basis (e.g. BASELINE config 4: N = 16384, 6 limbs).
     FHEContext(const SecurityParams &params, const std::vector<uint256_t> &rns_moduli) { init(params, rns_moduli); }
-    ~FHEContext() { delete params_.rns_ntt; }
+    ~FHEContext() { bfv_.clear(); delete params_.rns_ntt; }
     FHEContext(const FHEContext &) = delete;
     FHEContext &operator=(const FHEContext &) = delete;
 
@@ -380,7 +395,7 @@ public:
     }
 
     void relinkey_gen(RelinKeys &rlk, const SecretKey &sk, uint32_t decomp_bits = 16) {    // src/fhe.cu:76 signature
-        relinkey_gen(rlk, sk, decomp_bits, rng_, params_.t);
+        relinkey_gen(rlk, sk, decomp_bits, rng_, noise_scale());
     }
 
     // ---- Galois keys and slot rotations (include/fhe.cuh:58-61, 86, 112-116; declared, never defined in the reference) ------------------
@@ -1003,6 +1018,108 @@ public:
         return (float)std::max(0, bit_length(Q) - 2 - (int)bits);
     }
 
+    // ---- BFV: the scale-invariant encoding Delta m + e, Delta = floor(Q / t), of the reference's keygen / encrypt / decrypt (src/fhe.cu:54-185) ----
+    // multiply, encrypt and decrypt above are the BGV-flavoured ones and stay as they are.  A BFV context calls set_noise_scale(1) BEFORE key
+    // generation: keygen, relinkey_gen(rlk, sk, w) and encrypt then draw e instead of t e (as a CKKS context sets the plaintext modulus first).
+    // Level 0 only, correction 1.
+    void set_noise_scale(uint64_t s) {
+        if (!s) throw std::runtime_error("FHEContext::set_noise_scale: the scale must be at least 1");
+        noise_scale_ = s;
+    }
+    uint64_t noise_scale() const { return noise_scale_ ? noise_scale_ : params_.t; }
+    // The multiplier for this context's basis and t.  With no auxiliary primes given they are chosen: NTT primes of the ciphertext primes' size
+    // outside the basis, as few as P > 32 t n Q takes (fhe_bfv_multiplier_create checks that bound).
+    void bfv_multiplier_gen(BFVMultiplier &bm, const std::vector<uint64_t> &aux_moduli = {}) {
+        bm.clear();
+        fhe_rns_ntt_t *h = params_.rns_ntt->handle();
+        const uint32_t L = num_levels();
+        int rc = FHE_ERR_INVALID_ARG;
+        if (!aux_moduli.empty()) {
+            rc = fhe_bfv_multiplier_create(h, &bm.handle, params_.t, aux_moduli.data(), (uint32_t)aux_moduli.size());
+            bm.aux_moduli = aux_moduli;
+        } else {
+            for (const uint256_t &q : params_.rns_moduli)
+                if (q.limbs[1] | q.limbs[2] | q.limbs[3]) throw std::runtime_error("FHEContext::bfv_multiplier_gen: word-sized RNS primes are needed");
+            const uint32_t bits = 64 - (uint32_t)__builtin_clzll(params_.rns_moduli[0].limbs[0]);
+            for (uint32_t Lp = 1; Lp <= 16 && rc == FHE_ERR_INVALID_ARG; Lp++) {          // INVALID_ARG here: the bound needs one more prime
+                std::vector<uint64_t> cand(L + Lp), aux;
+                check(fhe_find_ntt_primes(bits, params_.n, L + Lp, cand.data()), "FHEContext::bfv_multiplier_gen: prime search");
+                for (uint64_t p : cand) {
+                    bool in_basis = false;
+                    for (const uint256_t &q : params_.rns_moduli) in_basis |= q.limbs[0] == p;
+                    if (!in_basis && aux.size() < Lp) aux.push_back(p);
+                }
+                rc = fhe_bfv_multiplier_create(h, &bm.handle, params_.t, aux.data(), (uint32_t)aux.size());
+                bm.aux_moduli = aux;
+            }
+        }
+        if (rc) bm.aux_moduli.clear();
+        check(rc, "FHEContext::bfv_multiplier_gen");
+        bm.t = params_.t; bm.made_for = params_.rns_ntt;
+    }
+    // (c0, c1) = relin(round(t / Q (a (x) b))) with the tensor product over the integers: ONE fhe_bfv_multiply_relin; with an empty RelinKeys
+    // the three components of fhe_bfv_multiply.  The context's own multiplier is made on first use (and again after set_plain_modulus).
+    void multiply_bfv(Ciphertext &result, const Ciphertext &a, const Ciphertext &b, const RelinKeys &rlk) {
+        if (!bfv_.handle || bfv_.t != params_.t || bfv_.made_for != params_.rns_ntt) bfv_multiplier_gen(bfv_);
+        multiply_bfv(result, a, b, rlk, bfv_);
+    }
+    void multiply_bfv(Ciphertext &result, const Ciphertext &a, const Ciphertext &b, const RelinKeys &rlk, const BFVMultiplier &bm) {
+        if (a.components.size() != 2 || b.components.size() != 2) throw std::runtime_error("FHEContext::multiply_bfv: 2-component ciphertexts expected");
+        if (a.level || b.level || a.correction != 1 || b.correction != 1) throw std::runtime_error("FHEContext::multiply_bfv: level-0 ciphertexts with correction 1 expected");
+        if (!bm.handle || bm.made_for != params_.rns_ntt || bm.t != params_.t) throw std::runtime_error("FHEContext::multiply_bfv: the multiplier was made for another context or plaintext modulus");
+        const float nb = a.noise_budget + b.noise_budget + 10;
+        if (rlk.rlk_keys.empty()) {
+            ensure_components(result, 3, 0);
+            check(fhe_bfv_multiply(bm.handle, result.components[0]->coeffs, result.components[1]->coeffs, result.components[2]->coeffs, a.components[0]->coeffs,
+                                   a.components[1]->coeffs, b.components[0]->coeffs, b.components[1]->coeffs, 1), "FHEContext::multiply_bfv");
+        } else {
+            fhe_relin_keys_t *keys = relin_keys_at(rlk, 0);
+            ensure_components(result, 2, 0);
+            while (result.components.size() > 2) { delete result.components.back(); result.components.pop_back(); }
+            check(fhe_bfv_multiply_relin(bm.handle, keys, result.components[0]->coeffs, result.components[1]->coeffs, a.components[0]->coeffs,
+                                         a.components[1]->coeffs, b.components[0]->coeffs, b.components[1]->coeffs, 1), "FHEContext::multiply_bfv");
+        }
+        device_synchronize();
+        result.noise_budget = nb; result.level = 0; result.correction = 1;
+    }
+    // encrypt of Delta pt: the constant Delta mod q_l times the encoded plaintext in every limb (fhe_rns_ntt_multiply_bcast), then the
+    // existing encryption, whose errors carry noise_scale() (1 in a BFV context)
+    void encrypt_bfv(Ciphertext &ct, const Plaintext &pt, const PublicKey &pk) {
+        if (!pt.poly || pt.poly->num_limbs != num_levels()) throw std::runtime_error("FHEContext::encrypt_bfv: a level-0 plaintext is needed");
+        const uint32_t n = params_.n, L = num_levels();
+        uint64_t Q[4] = {1, 0, 0, 0}, delta[4];
+        for (uint32_t l = 0; l < L; l++) mul_small(Q, params_.rns_moduli[l].limbs[0]);
+        div_small(delta, Q, params_.t);
+        std::vector<uint256_t> h((size_t)L * n);
+        for (uint32_t l = 0; l < L; l++) h[(size_t)l * n] = uint256_t(mod_small(delta, params_.rns_moduli[l].limbs[0]));
+        std::unique_ptr<Polynomial> dpoly(new_polynomial());
+        Plaintext scaled; scaled.poly = new_polynomial();
+        copy_to_device(dpoly->coeffs, h.data(), h.size());
+        params_.rns_ntt->multiply_rns_bcast(scaled.poly->coeffs, pt.poly->coeffs, dpoly->coeffs, 1);
+        try { encrypt(ct, scaled, pk); } catch (...) { delete scaled.poly; throw; }
+        device_synchronize();
+        delete scaled.poly;
+    }
+    // v = c0 + c1 s (+ c2 s^2) centred modulo Q through fhe_rns_from_rns, then m = round(t v / Q) mod t on the host, exactly
+    void decrypt_bfv(Plaintext &pt, const Ciphertext &ct, const SecretKey &sk) {
+        if (ct.level || ct.correction != 1) throw std::runtime_error("FHEContext::decrypt_bfv: a level-0 ciphertext with correction 1 is needed");
+        const uint32_t n = params_.n;
+        uint64_t Q[4], half[4];
+        const std::vector<uint256_t> v = decrypt_values(ct, sk, Q, half);
+        const uint64_t t = params_.t;
+        std::vector<long long> m(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const bool neg = greater(v[i].limbs, half);
+            uint64_t mag[4];
+            if (neg) sub4(mag, Q, v[i].limbs); else std::memcpy(mag, v[i].limbs, 32);
+            const uint64_t r = round_scaled(mag, t, Q) % t;
+            m[i] = (long long)(neg ? (t - r) % t : r);
+        }
+        if (!pt.poly) pt.poly = new_polynomial();
+        upload_signed(*pt.poly, m);
+        pt.is_ntt_form = false;
+    }
+
     // ---- CKKS: approximate arithmetic on the same ciphertexts (fhe_ckks_encode / fhe_ckks_decode; class CKKSEncoder below) -------------------
     // multiply, relinearize, rotate_rows and the level engines are used as they are; they do not look at `scale`, so after a multiply the
     // caller sets result.scale = a.scale * b.scale.  Keys carry noise t e (keygen, relinkey_gen): a CKKS context sets the plaintext modulus to 2
@@ -1125,6 +1242,8 @@ private:
     std::mt19937_64 rng_{0x5EED0000ull};
     bool device_sampling_ = false;
     std::vector<std::unique_ptr<RNS_NTTEngine>> level_engines_;   // index = level; entry 0 unused (params_.rns_ntt)
+    BFVMultiplier bfv_;                    // multiply_bfv's own multiplier, made on first use
+    uint64_t noise_scale_ = 0;             // 0: the plaintext modulus t (BGV-style noise); set_noise_scale
     std::vector<std::shared_ptr<fhe_batch_encoder_t>> encoders_;  // index = 2 level + slot order (encoder_at)
     std::vector<std::shared_ptr<fhe_ckks_encoder_t>> ckks_encoders_;   // index = level (ckks_encoder_at)
     size_t slot_words() const { return ((size_t)params_.n * sizeof(uint64_t) + sizeof(uint256_t) - 1) / sizeof(uint256_t); }   // n 8-byte words in containers
@@ -1166,7 +1285,7 @@ private:
     // one fhe_keyswitch_keys_generate on the top-level engine: noise scale t, sigma = security.sigma, seeds from the context generator
     void generate_key_sets(const SecretKey &sk, uint32_t decomp_bits, const uint32_t *elts, uint32_t num_sets, fhe_relin_keys_t **sets) {
         const uint64_t seeds[2] = {rng_(), rng_()};
-        check(fhe_keyswitch_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, elts, num_sets, params_.t, (double)params_.security.sigma,
+        check(fhe_keyswitch_keys_generate(params_.rns_ntt->handle(), secret_key_at(sk, 0), decomp_bits, elts, num_sets, noise_scale(), (double)params_.security.sigma,
                                           seeds, sets), "FHEContext: key-switching key generation");
     }
     // appends the `levels` rows of a key set to `rows` as coefficient-form polynomials (fhe_relin_keys_export)
@@ -1275,15 +1394,15 @@ private:
     // ---- where keygen / encrypt get their random polynomials: host generator (default) or the device samplers --------------
     void draw_ternary(Polynomial &p) { if (device_sampling_) sample_ternary_polynomial(p); else upload_signed(p, sample_small(1)); }
     void draw_uniform(Polynomial &p) { if (device_sampling_) sample_uniform_polynomial(p); else upload_uniform(p); }
-    // t * e, e small: BGV-style noise (a multiple of the plaintext modulus)
+    // noise_scale() * e, e small: t e by default, BGV-style noise (a multiple of the plaintext modulus); e itself in a BFV context
     void draw_scaled_error(Polynomial &p) {
-        if (!device_sampling_) { upload_signed(p, sample_small(3), params_.t); return; }
+        if (!device_sampling_) { upload_signed(p, sample_small(3), noise_scale()); return; }
         sample_error_polynomial(p);
         const uint32_t n = params_.n, L = (uint32_t)params_.rns_moduli.size();
         for (uint32_t l = 0; l < L; l++) {   // limb l *= t: literal Montgomery product with the scalar t * 2^256 mod q_l (poly_mul_scalar_kernel)
             const uint256_t &q = params_.rns_moduli[l];
             if (q.limbs[1] | q.limbs[2] | q.limbs[3]) throw std::runtime_error("FHEContext: device sampling expects word-sized RNS primes");
-            const uint64_t q0 = q.limbs[0], tr = (uint64_t)((unsigned __int128)(params_.t % q0) * pow_mod(2, 256, q0) % q0);
+            const uint64_t q0 = q.limbs[0], tr = (uint64_t)((unsigned __int128)(noise_scale() % q0) * pow_mod(2, 256, q0) % q0);
             uint64_t inv[4]; check(fhe_montgomery_inverse(q.limbs, inv), "montgomery inverse");
             const uint256_t scalar(tr);
             check(fhe_u256_mont_mul_scalar(p.coeffs + (size_t)l * n, p.coeffs + (size_t)l * n, scalar.limbs, q.limbs, inv[0], n, nullptr),   // legacy default stream: ordered with the engine's blocking stream
@@ -1346,6 +1465,35 @@ private:
             }
         }
         if (inverse) { uint64_t pw = 1; for (uint32_t i = 0; i < n; i++) { a[i] = mulm(mulm(a[i], ninv), pw); pw = mulm(pw, ipsi); } }   // untwist, scale
+    }
+    static void div_small(uint64_t q[4], const uint64_t x[4], uint64_t m) {         // q = floor(x / m)
+        unsigned __int128 r = 0;
+        for (int i = 3; i >= 0; i--) { const unsigned __int128 cur = (r << 64) | x[i]; q[i] = (uint64_t)(cur / m); r = cur % m; }
+    }
+    static void mul5(uint64_t out[5], const uint64_t x[4], uint64_t m) {             // the 320-bit product x m
+        unsigned __int128 c = 0;
+        for (int i = 0; i < 4; i++) { c += (unsigned __int128)x[i] * m; out[i] = (uint64_t)c; c >>= 64; }
+        out[4] = (uint64_t)c;
+    }
+    // round(t mag / Q) = floor((2 t mag + Q) / (2 Q)) for mag <= Q / 2 < 2^254: at most t / 2 + 1, found bit by bit (Q is odd: no tie)
+    static uint64_t round_scaled(const uint64_t mag[4], uint64_t t, const uint64_t Q[4]) {
+        uint64_t num[5], Q2[4];
+        mul5(num, mag, t);
+        for (int i = 4; i > 0; i--) num[i] = (num[i] << 1) | (num[i - 1] >> 63);
+        num[0] <<= 1;
+        unsigned __int128 c = 0;
+        for (int i = 0; i < 5; i++) { c += (unsigned __int128)num[i] + (i < 4 ? Q[i] : 0); num[i] = (uint64_t)c; c >>= 64; }
+        for (int i = 3; i > 0; i--) Q2[i] = (Q[i] << 1) | (Q[i - 1] >> 63);
+        Q2[0] = Q[0] << 1;
+        uint64_t r = 0;
+        for (int b = 63; b >= 0; b--) {
+            uint64_t p[5];
+            mul5(p, Q2, r | (1ull << b));
+            bool above = false;
+            for (int i = 4; i >= 0; i--) if (p[i] != num[i]) { above = p[i] > num[i]; break; }
+            if (!above) r |= 1ull << b;
+        }
+        return r;
     }
     static void mul_small(uint64_t x[4], uint64_t m) {
         unsigned __int128 c = 0;

@@ -768,6 +768,52 @@ int fhe_ckks_encode(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, void *d_out
 int fhe_ckks_decode(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, double *d_slots, const uint64_t *d_m, uint64_t t, double scale, uint32_t batch);
 int fhe_ckks_decode_poly(fhe_rns_ntt_t *h, const fhe_ckks_encoder_t *enc, double *d_slots, const void *d_poly, double scale, uint32_t batch);
 
+/* ---- BFV multiplication: exact RNS lift, scale-and-round by t / Q, one call ------------------------------------------------------------------
+ * The scale-invariant encoding Delta m + e, Delta = floor(Q / t), of the reference's keygen / encrypt / decrypt (include/fhe/fhe.hpp:302, 353)
+ * cannot be multiplied by fhe_ct_multiply, the tensor product modulo Q: a BFV product is the tensor product over the integers, scaled by t / Q
+ * and rounded.  Halevi, Polyakov and Shoup's "simple scaling", with the floating-point sums replaced by 128-bit fixed point so that every call
+ * is a deterministic integer function of its inputs.  Q = prod q_i (i < L) the primes of the ciphertext engine hq, P = prod p_j (j < L') the
+ * auxiliary NTT primes for the same n, t the plaintext modulus; every modulus below 2^64; containers and layouts as everywhere else.
+ *   centred lift of a base B = prod b_i (k primes) to a base C, for residues x_i:
+ *       y_i = [x_i (B / b_i)^-1]_{b_i},  r_i = floor(2^128 / b_i),  V = sum y_i r_i,  alpha = floor((V + 2^127) / 2^128)
+ *       out_j = (sum_i y_i ((B / b_i) mod c_j) - alpha (B mod c_j)) mod c_j
+ *     the centred representative of x, or that +- B for a coefficient with x / B within k 2^-64 of 1/2 modulo 1; the definition decides.
+ *   scale and round, base Q u P -> base P: y_m = [x_m (Q P / m)^-1]_m for every prime m; theta_i = t P mod q_i,
+ *       rho_i = floor(2^128 theta_i / q_i),  W = sum_i y_i rho_i,  R = floor((W + 2^127) / 2^128)
+ *       s_j = (R + sum_i y_i (floor(t P / q_i) mod p_j) + y_{p_j} t (P / p_j)) mod p_j
+ *     round(t x / Q) mod p_j for the centred x, up to +-1 where the fractional part is within L 2^-64 of 1/2.
+ * fhe_bfv_multiplier_create  the object owns an engine on (q_0 .. q_{L-1}, p_0 .. p_{L'-1}) and the tables above (word-sized host arithmetic, built
+ *     once).  FHE_ERR_INVALID_ARG: a null argument; t < 2; num_aux == 0; an auxiliary prime that equals a q_i or another p_j, or is not 1 modulo 2n;
+ *     P <= 32 t n Q (checked exactly: the factor 32 covers operands the lift left at +- Q and costs at most one auxiliary prime).
+ *     FHE_ERR_UNSUPPORTED: a modulus of 2^64 or more or an hq without a word-sized width class (n < 2^11); L or L' above 16; an extended engine of
+ *     another width class than hq (pick auxiliary primes of the ciphertext primes' size).  FHE_ERR_BAD_MODULUS: an auxiliary modulus that is
+ *     not prime.  *out stays untouched on failure; fhe_bfv_multiplier_destroy(NULL) is FHE_OK.  Destroy the multiplier BEFORE hq.
+ * fhe_bfv_multiplier_engine  the borrowed engine on Q u P: run tensor products of your own there and scale a sum of products once.  Every call
+ *     below sets that engine's stream to hq's current stream before it launches.
+ * fhe_bfv_lift         [batch][L][n] -> [batch][L + L'][n]: the Q limbs copied, the P limbs from the centred lift.  One launch.
+ * fhe_bfv_scale_round  host arrays of 1 to 3 device pointers, inputs [batch][L + L'][n], outputs [batch][L][n]: s as above, then its centred
+ *     lift from base P to base Q in the same kernel (s never touches memory).  One launch for all components.
+ * fhe_bfv_multiply     lift of the four inputs into the workspace, the tensor product on the extended engine, scale-and-round into c0, c1, c2:
+ *     bit for bit that composition through the public calls.  a and b the same buffers: the squaring path of the tensor product.
+ * fhe_bfv_multiply_relin  the same with c2 kept in the workspace, then fhe_ct_relinearize on hq: bit for bit fhe_bfv_multiply + fhe_ct_relinearize.
+ * fhe_bfv_multiplier_reserve  sizes the multiplier's workspace (7 [batch][L + L'][n] + 1 [batch][L][n] polynomials) and the extended engine's
+ *     for `batch`; with a key set also fhe_rns_ntt_reserve(hq, batch).  Afterwards the calls above allocate nothing and can be captured into a
+ *     hipGraph.  fhe_bfv_multiplier_workspace_bytes reports the multiplier's and the extended engine's workspaces.
+ * FHE_ERR_INVALID_ARG with nothing launched: a null handle or buffer, batch == 0, a container pointer not 16-byte aligned, an output that
+ * aliases an input or another output, keys of another engine.  All calls on one multiplier must be ordered on one stream. */
+typedef struct fhe_bfv_multiplier fhe_bfv_multiplier_t;
+int fhe_bfv_multiplier_create(fhe_rns_ntt_t *hq, fhe_bfv_multiplier_t **out, uint64_t t, const uint64_t *aux_moduli, uint32_t num_aux);
+int fhe_bfv_multiplier_destroy(fhe_bfv_multiplier_t *m);
+int fhe_bfv_multiplier_engine(const fhe_bfv_multiplier_t *m, fhe_rns_ntt_t **engine);
+int fhe_bfv_multiplier_reserve(fhe_bfv_multiplier_t *m, uint32_t batch, const fhe_relin_keys_t *rk_or_null);
+int fhe_bfv_multiplier_workspace_bytes(const fhe_bfv_multiplier_t *m, uint64_t *bytes);
+int fhe_bfv_lift(fhe_bfv_multiplier_t *m, void *d_out, const void *d_in, uint32_t batch);
+int fhe_bfv_scale_round(fhe_bfv_multiplier_t *m, void *const *d_out, const void *const *d_in, uint32_t num_components, uint32_t batch);
+int fhe_bfv_multiply(fhe_bfv_multiplier_t *m, void *d_c0, void *d_c1, void *d_c2, const void *d_a0, const void *d_a1, const void *d_b0,
+                     const void *d_b1, uint32_t batch);
+int fhe_bfv_multiply_relin(fhe_bfv_multiplier_t *m, const fhe_relin_keys_t *rk, void *d_c0, void *d_c1, const void *d_a0, const void *d_a1,
+                           const void *d_b0, const void *d_b1, uint32_t batch);
+
 /* Scan a [batch][L][n] buffer for coefficients that are not canonical (>= q_limb, or non-zero
  * upper limbs on the narrow paths).  Synchronises.  FHE_OK or FHE_ERR_NONCANONICAL. */
 int fhe_rns_check_canonical(fhe_rns_ntt_t *h, const void *d_data, uint32_t batch);
